@@ -67,3 +67,28 @@ def test_byte_cost_model_prices_the_two_directions_apart():
     assert b.byte_cost_model("c3", 8, (read, copy), 1.0) is None      # PMC passes exist for one GPU only
     assert b.byte_cost_model("c1", 1, (read, copy), 1.0) is None      # no pass for this workload
     assert b.byte_cost_model("c3", 1, (6000.0, 13000.0), 1.0) is None  # rates that imply a negative write cost: no model
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: the basis sample is the same for the same (K, n), holds the first and the last column it can reach,
+    distinct rows in range, and stays within 64 MB however many steps are timed"""
+    b = _bench()
+    for k, n in ((1, 10), (12, 10_000), (50, 10_000_000), (1024, 10_000), (2130, 10_000_000), (5000, 100_000_000)):
+        cols, rows = b.dump_sample(k, n)
+        cols2, rows2 = b.dump_sample(k, n)
+        assert list(cols) == list(cols2) and list(rows) == list(rows2)
+        c = min(k, b.DUMP_COL_REACH)   # lzx_multout_f64 reaches column j with k = j + 1 coefficients: at least 1028 on MI355X
+        assert b.DUMP_COL_REACH <= 1028
+        assert cols[0] == 0 and cols[-1] == c - 1 and len(cols) == min(c, b.DUMP_COLS) and (len(cols) == 1 or (cols[1:] > cols[:-1]).all())
+        assert len(rows) == min(n, b.DUMP_ROWS) and rows.min() >= 0 and rows.max() < n and (rows[1:] > rows[:-1]).all()
+        assert 8 * (len(cols) * len(rows) + 2 * k + 1) <= 64 << 20
+
+
+def test_bench_options():
+    """the plain run and its two options are on the command line"""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
+        assert opt in out.stdout, opt

@@ -136,7 +136,7 @@ def test_final_cli(tmp_path):
 
 def test_bench_contract_small_workload():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "20",
-                          "--warmup", "2"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "2", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -146,6 +146,52 @@ def test_bench_contract_small_workload():
     assert j["steps"] == 20 and j["n_gpus"] == 1 and j["dtype"] == "f64" and j["value"] > 0
     assert j["roofline"]["bound"] == "hbm" and 0 < j["roofline"]["frac"] < 1
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["cores"] == 1
+    assert j["roofline"]["measured_stream_read_GBps"] > 0 and j["config"]["lanczos_coefficients_finite"]
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run (no --full): the headline line without the CPU baselines or the streaming probe, exactly --steps timed
+    iterations, and --dump-outputs writing what those iterations computed -- the same from run to run.  x0 = ones, so
+    ||x0|| = sqrt(n), q_0 = 1 / sqrt(n) everywhere and alpha_0 = nnz / n exactly."""
+    import bench
+    K, lines, dumps = 12, [], []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c1", "--steps", str(K),
+                              "--warmup", "3", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    j, o = lines[0], dumps[0]
+    assert j["metric"] == "lanczos_iterations_per_sec" and j["unit"] == "iter/s" and j["higher_is_better"] and j["dtype"] == "f64"
+    assert j["steps"] == K and j["warmup"] == 3 and abs(j["ms_per_step"] * j["value"] - 1e3) < 1e-6 * 1e3
+    assert "cpu_baseline" not in j and "measured_stream_read_GBps" not in j["roofline"] and 0 < j["roofline"]["frac"] < 1
+    n, nnz = j["config"]["n"], j["config"]["nnz"]
+    cols, rows = bench.dump_sample(K, n)
+    assert set(o) == {"alpha", "beta", "x_norm", "basis_sample"}
+    assert all(a.dtype == np.float64 for a in o.values()) and sum(a.nbytes for a in o.values()) <= 64 << 20
+    assert o["alpha"].shape == (K,) and o["beta"].shape == (K - 1,) and o["basis_sample"].shape == (len(cols), len(rows))
+    assert np.isfinite(o["alpha"]).all() and np.isfinite(o["beta"]).all() and np.isfinite(o["basis_sample"]).all()
+    assert abs(o["x_norm"][0] - np.sqrt(n)) <= 1e-12 * np.sqrt(n)
+    assert abs(o["alpha"][0] * n / nnz - 1.0) < 1e-14
+    assert np.allclose(o["basis_sample"][0], 1.0 / np.sqrt(n), rtol=1e-14, atol=0)
+    for name, a in o.items():   # the same inputs give the same outputs
+        assert np.allclose(dumps[1][name], a, rtol=1e-12, atol=1e-15), name
+    # more steps than the basis columns lzx_multout_f64 can reach (k + 1 > 1028): every step's coefficients, the reachable
+    # columns of the basis -- and the same first steps as the short run
+    K = 1100
+    d = tmp_path / "long"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c1", "--steps", str(K),
+                          "--warmup", "3", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == K and j["config"]["k"] == K
+    long = {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+    cols, rows = bench.dump_sample(K, n)
+    assert cols[-1] == bench.DUMP_COL_REACH - 1
+    assert long["alpha"].shape == (K,) and long["beta"].shape == (K - 1,) and long["basis_sample"].shape == (len(cols), len(rows))
+    assert np.isfinite(long["alpha"]).all() and np.isfinite(long["basis_sample"]).all()
+    assert np.allclose(long["alpha"][:12], o["alpha"], rtol=1e-12, atol=0) and np.allclose(long["basis_sample"][0], o["basis_sample"][0], rtol=1e-14, atol=0)
 
 
 def test_convergence_monitor_device(pkg, tmp_path):
