@@ -216,6 +216,41 @@ int lzx_multout_f64_local(lzx_handle *hs, int world, const double *t, uint32_t k
 int lzx_multout_change_f64(lzx_handle h, const double *t, uint32_t k, double *rel_change);
 int lzx_multout_change_f64_local(lzx_handle *hs, int world, const double *t, uint32_t k, double *rel_change);
 
+/* ---- batched, independent Lanczos (one GPU) -----------------------------------------------------
+ * b separate three-term recurrences, one per column of X = [x_1 .. x_b], that share ONE SpMM per iteration: with the b
+ * vectors stored interleaved per vertex ([n][B], B = b padded to 2, 4, 8 or 16) one col_idx read and one gathered row of X
+ * serve every column.  Not block Lanczos (no QR of a block, no coupling between columns): each column runs the recurrence of
+ * lzx_lanczos_f64, plus a breakdown stop of its own, decided on the device -- after beta_{c,j} (j < k-1) column c stops when
+ *     beta_{c,j} <= 2^-40 * max_{i<=j} (|alpha_{c,i}| + beta_{c,i-1}),   beta_{c,-1} = 0;
+ * its beta_{c,j} and later alpha / beta are then returned as 0, its later basis vectors are zero, k_used[c] = j+1, and the
+ * other columns go on.  (Without it a seed vector e_v of a small component -- communicability of a seed vertex -- would
+ * divide by a rounding-level beta.)  Column c's alpha, beta, k_used, basis and answer are bit-identical whatever else is in
+ * the batch (every reduction's shape depends on n alone).  The SpMM works on the caller-order CSR the handle keeps: every row
+ * of at most 2048 entries is summed with one accumulator in ascending column order (bit-identical to lzx_spmv_f64's
+ * reference, serial/lib/SPMV.cc:19-28); a longer row is cut into chunks of 2048 entries whose totals are added in chunk
+ * order.  The work list behind it is built on first use and lives as long as the graph.
+ * The batch state (basis, work vectors) is separate from the single-vector state: a batched call neither voids a prepared or
+ * chunked single-vector decomposition nor touches its resident basis.  One rank only: a handle with a communicator gets
+ * LZX_ERR_STATE.  A new graph and lzx_destroy free the batch state too.
+ *
+ * lzx_lanczos_multi_f64: b in [1, 16]; X0: b contiguous vectors of n (caller order); alpha, beta: [b][k] (beta[c][k-1]
+ * unused, returned 0); k_used[b], x_norm[b] (||x_c||, left-to-right sum of squares as lzx_lanczos_prepare_f64 forms it);
+ * Q (may be NULL): [b][k][n].  The basis stays resident for lzx_multout_multi_f64.  Errors: LZX_ERR_ARG for null pointers,
+ * k == 0, b == 0 or an all-zero column; LZX_ERR_LIMIT for b > 16; LZX_ERR_NOMEM when the basis (k * n * B * 8 bytes) does
+ * not fit -- the message states the bytes and no batch state is left behind.  stats: loop_ms (host clock around the k
+ * iterations), spmv_ms (SpMM + the split-row / alpha-partial launch), vec_ms (the update and scale launches), spmv_kernels
+ * = launches per iteration (4), spmv_bytes = the algorithmic bytes of ONE SpMM, 4*nnz + 8*(n+1) + 8*b*n (X once) + 8*b*n (Y). */
+int lzx_lanczos_multi_f64(lzx_handle h, uint32_t b, const double *X0, uint32_t k, double *alpha, double *beta,
+                          uint32_t *k_used, double *x_norm, double *Q, lzx_stats *stats);
+/* ans[b][n] = per column Q_c t_c on the resident batch basis; T: [b][k] (entries >= k_used[c] ignored).  b must be the
+ * resident batch's, k at most its k (LZX_ERR_ARG otherwise; LZX_ERR_STATE when no batch is resident).                  */
+int lzx_multout_multi_f64(lzx_handle h, uint32_t b, const double *T, uint32_t k, double *ans);
+/* Y[b][n] = A X[b][n]: kernel-level parity hook of the batched SpMM, like lzx_spmv_f64.  Leaves a resident batch basis
+ * and a prepared single-vector decomposition alone.                                                                    */
+int lzx_spmm_f64(lzx_handle h, uint32_t b, const double *X, double *Y);
+/* Give back the batch basis and work vectors (they are also freed by a new graph and by lzx_destroy). */
+int lzx_multi_release(lzx_handle h);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -23,7 +23,8 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # test-only shapes the product library accepts through lzx_test_set_shape (csrc/lzx_test_hooks.h): they select among code
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
-                 "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish")
+                 "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
+                 "multi_row_chunk")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -100,6 +101,11 @@ SYMBOLS = [
     ("lzx_bench_spmv", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, _f64p]),
     ("lzx_bench_stream", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, _f64p, _f64p]),
     ("lzx_set_option", ctypes.c_int, [_h, ctypes.c_char_p, ctypes.c_int64]),
+    ("lzx_lanczos_multi_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, _f64p, _f64p, _u32p, _f64p, _f64p,
+                                             ctypes.POINTER(LzxStats)]),
+    ("lzx_multout_multi_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, _f64p]),
+    ("lzx_spmm_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, _f64p]),
+    ("lzx_multi_release", ctypes.c_int, [_h]),
 ]
 
 _LIB = None
@@ -350,6 +356,45 @@ class Engine:
         _check(self.L.lzx_multout_f64(self.h, _p(t, _f64p), len(t), _p(ans, _f64p)), "lzx_multout_f64", self.L)
         return ans
 
+    # ---- batched, independent Lanczos (include/lzx.h: up to 16 starting vectors, one SpMM per iteration) ----
+    def _batch(self, X, what):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.n:
+            raise ValueError(f"{what}: X must be a (b, n) array with n = {self.n}, got shape {X.shape}")
+        return X
+
+    def lanczos_multi(self, X0, k: int, want_q: bool = False):
+        """Returns (alpha[b,k], beta[b,k] (beta[:, k-1] = 0), k_used[b], x_norm[b], Q (b, k, n) or None, stats dict)."""
+        X0 = self._batch(X0, "lanczos_multi")
+        b = X0.shape[0]
+        alpha, beta = np.zeros((b, k)), np.zeros((b, k))
+        k_used, xn = np.zeros(b, dtype=np.uint32), np.zeros(b)
+        Q = np.empty((b, k, self.n)) if want_q else None
+        st = LzxStats()
+        _check(self.L.lzx_lanczos_multi_f64(self.h, b, _p(X0, _f64p), k, _p(alpha, _f64p), _p(beta, _f64p), _p(k_used, _u32p),
+                                           _p(xn, _f64p), _p(Q, _f64p) if want_q else None, ctypes.byref(st)),
+               "lzx_lanczos_multi_f64", self.L)
+        return alpha, beta, k_used, xn, Q, st.as_dict()
+
+    def multout_multi(self, T):
+        """ans[b, n] = Q_c t_c per column on the resident batch basis (T: (b, k))."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 2:
+            raise ValueError(f"multout_multi: T must be a (b, k) array, got shape {T.shape}")
+        ans = np.empty((T.shape[0], self.n))
+        _check(self.L.lzx_multout_multi_f64(self.h, T.shape[0], _p(T, _f64p), T.shape[1], _p(ans, _f64p)), "lzx_multout_multi_f64", self.L)
+        return ans
+
+    def spmm(self, X):
+        """Y[b, n] = A X[b, n] (the batched SpMM)."""
+        X = self._batch(X, "spmm")
+        Y = np.empty_like(X)
+        _check(self.L.lzx_spmm_f64(self.h, X.shape[0], _p(X, _f64p), _p(Y, _f64p)), "lzx_spmm_f64", self.L)
+        return Y
+
+    def multi_release(self):
+        _check(self.L.lzx_multi_release(self.h), "lzx_multi_release", self.L)
+
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()
         _check(self.L.lzx_bench_stream(self.h, nbytes, reps, ctypes.byref(rd), ctypes.byref(cp)), "lzx_bench_stream", self.L)
@@ -432,6 +477,10 @@ class LocalGroup:
         ans = np.empty(self.n)
         _check(self.L.lzx_multout_f64_local(self.arr, self.world, _p(t, _f64p), len(t), _p(ans, _f64p)), "lzx_multout_f64_local", self.L)
         return ans
+
+    def lanczos_multi(self, X0, k: int, want_q: bool = False):
+        """The batched path is one-GPU: the library refuses a handle of a communicator (LzxError naming the group's size)."""
+        return self.engines[0].lanczos_multi(X0, k, want_q)
 
     def close(self):
         for e in self.engines:

@@ -193,6 +193,8 @@ extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
     else if (!strcmp(name, "start_vector_scan")) c->x0_scan_opt = value;
     // 0: the blocked SpMV always launches k_pb_finish (default: the lazy loop's vector kernel stands in for it)
     else if (!strcmp(name, "defer_finish")) c->defer_opt = value;
+    // entries per chunk of a split row in the batched SpMM (lzx_multi.hip; default LZX_MULTI_CHUNK)
+    else if (!strcmp(name, "multi_row_chunk")) c->multi_chunk_opt = value;
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: unknown shape '%s'", name);
     return LZX_OK;
 }

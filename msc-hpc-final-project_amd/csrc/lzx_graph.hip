@@ -92,6 +92,7 @@ int lzx_graph_release(lzx_ctx *c)
     dev_free(c->d_partials2);
     dev_free(c->d_partials3);
     lzx_pb_release(c);
+    lzx_multi_free(c, true);
     c->q_cols = 0;
     c->k_last = 0;
     c->k_prep = 0;   // a prepared start vector lived in the buffers just freed

@@ -345,11 +345,19 @@ struct lzx_ctx {
     u32 spmv_grid = 0;
     u32 fin_grid = 0;
     size_t spmv_lds = 0;
+
+    // batched independent Lanczos (lzx_multi.hip): its own work list, basis and work vectors, apart from everything above
+    struct lzx_multi_state *multi = nullptr;
+    int64_t multi_chunk_opt = -1;      // test shape multi_row_chunk: entries per chunk of a split row in the batched SpMM (-1: LZX_MULTI_CHUNK)
 };
 
 // ---- lzx_graph.hip ----
 int lzx_graph_release(lzx_ctx *c);
 int lzx_graph_prepare(lzx_ctx *c);   // builds this rank's share from d_row_ptr/d_col_idx (sharded hand-over: from c->shard)
+
+// ---- lzx_multi.hip ----
+// with_tables: the per-graph work list goes too (a new graph, lzx_destroy); otherwise only the batch basis and work vectors
+void lzx_multi_free(lzx_ctx *c, bool with_tables);
 
 // ---- lzx_pb.hip ----
 // Builds the propagation-blocked structure for this rank's non-hub entries. d_nh_off: exclusive prefix of the

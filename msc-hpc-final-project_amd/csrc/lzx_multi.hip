@@ -1,0 +1,748 @@
+// lzx_multi.hip -- batched, independent Lanczos: b <= 16 separate three-term recurrences (one per column of X) that share
+// one SpMM per iteration (include/lzx.h: lzx_lanczos_multi_f64, lzx_multout_multi_f64, lzx_spmm_f64, lzx_multi_release).
+//
+// Not block Lanczos: no QR of a block, no coupling between columns.  Each column runs serial/lib/lanczos.cc:9-56 (the
+// arithmetic of lzx_lanczos_f64) plus a breakdown stop of its own.
+//
+// Layout.  Working vectors are vertex-major and interleaved, [n][B] fp64, B = the batch width padded to 2, 4, 8 or 16: one
+// vertex's values are 16-128 bytes, so one gathered row of X fills at most one 128-byte line, and one col_idx read serves all
+// B columns.  The path works on the caller-order CSR the handle keeps (d_row_ptr / d_col_idx); the sliced-ELL and
+// propagation-blocked tables of the single-vector path are neither used nor touched.  Padded columns start as zero vectors
+// and stop at iteration 0.
+//
+// One iteration is four launches:
+//   k_multi_spmm    V = A Q_j.  A wavefront serves 64 / B segments of the work list, lane (segment, column); a segment is a
+//                   whole row or an L-entry chunk of a longer row, summed with ONE accumulator in ascending CSR order (a row
+//                   that is not split comes out bit-identical to serial/lib/SPMV.cc:19-28).  The work list is sorted by
+//                   length, longest first, so the lanes of a wavefront carry about the same number of entries.
+//   k_multi_alpha   the chunk totals of split rows added in chunk order into V, and per-(row segment, column) partials of
+//                   alpha_c = v_c . q_{j,c}
+//   k_multi_update  every workgroup closes alpha from the partials (fixed order); u = v - alpha q_j - beta_{j-1} q_{j-1} (two
+//                   rounded updates, as serial/); partials of ||u||^2
+//   k_multi_scale   every workgroup closes beta; breakdown stop; q_{j+1} = u / beta into the basis
+// Reductions: a row segment of LZX_MULTI_SEG rows yields one partial per column.  Inside it, runs of LZX_MULTI_RUN rows are
+// summed left to right by one thread, the runs' totals by a fixed wavefront tree; the segments' partials are closed
+// by the fixed-order block sum of lzx_reduce.h's shape.  Nothing in that shape depends on B, on b or on the column's place in
+// X, so a column's alpha, beta, basis and answer are bit-identical whatever else is in the batch.
+//
+// Breakdown (decided on the device, per column): after beta_{c,j} (j < k - 1) the column stops when
+//   beta_{c,j} <= 2^-40 * max_{i <= j} (|alpha_{c,i}| + beta_{c,i-1}),   beta_{c,-1} = 0.
+// Its beta_j is then stored as 0 and its later basis vectors are zero, so its later alpha / beta come out 0; "stopped before
+// iteration j" is read from beta_{c,j-1} == 0, which every workgroup of a later launch sees complete -- no flag round trip.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <vector>
+
+#include "lzx_internal.h"
+#include "lzx_spmv_body.h"
+#include "lzx_reduce.h"
+
+static constexpr u32 LZX_MULTI_CHUNK = 2048;   // entries per chunk of a split row (test shape multi_row_chunk)
+static constexpr u32 LZX_MULTI_RUN = 32;       // rows one thread sums left to right per column
+static constexpr u32 LZX_MULTI_SEG = 2048;     // rows per partial (64 runs: one per lane of the closing wavefront)
+static constexpr u32 LZX_MULTI_RUNS = LZX_MULTI_SEG / LZX_MULTI_RUN;
+static constexpr u32 LZX_MULTI_BLOCK = 256;
+static constexpr u32 LZX_MULTI_PAD = 0xffffffffu;   // work-list entry without output (padding)
+static constexpr u32 LZX_MULTI_PART = 0x80000000u;  // work-list dst flag: a chunk total, slot = dst & ~flag
+
+struct lzx_multi_state {
+    // per graph: the work list (built on first use, freed with the graph)
+    u32 chunk = 0;                     // L the list was built with
+    u64 n_wl = 0;                      // entries, padded to a multiple of 32 (the most segments one wavefront takes)
+    uint4 *d_wl = nullptr;             // {first entry lo, hi, length, dst}, longest first
+    u32 n_split = 0, n_parts = 0;
+    u32 *d_split_row = nullptr;        // [n_split] split rows, ascending
+    u32 *d_split_first = nullptr;      // [n_split + 1] their first chunk slot
+    u32 *d_run_split = nullptr;        // [runs + 1] first split row at or behind the run's first row
+    u32 n_seg = 0;                     // partials per column
+    // work vectors (width wB)
+    u32 wB = 0;
+    double *d_V = nullptr, *d_X = nullptr;   // [n][wB] each
+    double *d_part = nullptr;          // [n_parts][wB] chunk totals
+    double *d_pa = nullptr, *d_pn = nullptr; // [n_seg][wB]
+    // batch basis
+    u32 B = 0, b = 0, k = 0;
+    bool resident = false;             // a decomposition's basis is there
+    double *d_Q = nullptr;             // [k][n][B]
+    double *d_alpha = nullptr, *d_beta = nullptr, *d_T = nullptr;   // [B][k]
+    double *d_mx = nullptr;            // [k][B] running max of |alpha_i| + beta_{i-1}
+    u32 *d_kused = nullptr;            // [B]
+    std::vector<u32> h_kused;
+    std::vector<hipEvent_t> ev;
+};
+
+template <typename T>
+static void mfree(T *&p)
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
+template <typename T>
+static int malloc_n(T **p, u64 count, const char *what)
+{
+    *p = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * std::max<u64>(count, 1));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        lzx_set_error("batched Lanczos: allocation of %llu bytes (%s) failed: %s", (unsigned long long)(sizeof(T) * count), what,
+                      hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP;
+    }
+    return LZX_OK;
+}
+
+static void free_work(lzx_multi_state *m)
+{
+    mfree(m->d_V); mfree(m->d_X); mfree(m->d_part); mfree(m->d_pa); mfree(m->d_pn);
+    m->wB = 0;
+}
+
+static void free_basis(lzx_multi_state *m)
+{
+    mfree(m->d_Q); mfree(m->d_alpha); mfree(m->d_beta); mfree(m->d_T); mfree(m->d_mx); mfree(m->d_kused);
+    m->B = m->b = m->k = 0;
+    m->resident = false;
+    m->h_kused.clear();
+}
+
+void lzx_multi_free(lzx_ctx *c, bool with_tables)
+{
+    lzx_multi_state *m = c->multi;
+    if (!m) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    free_basis(m);
+    free_work(m);
+    if (!with_tables) return;
+    mfree(m->d_wl); mfree(m->d_split_row); mfree(m->d_split_first); mfree(m->d_run_split);
+    for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
+    delete m;
+    c->multi = nullptr;
+}
+
+// ==================================================================================================== kernels
+// in [b][n] (caller's vectors) -> out [n][B], column c divided by div[c]; padded columns 0
+struct MultiDiv { double v[16]; };
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_pack(const double *in, u32 b, u64 n, MultiDiv div, double *out)
+{
+    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (i >= n * B) return;
+    const u32 c = (u32)(i % B);
+    const u64 r = i / B;
+    out[i] = c < b ? in[(u64)c * n + r] / div.v[c] : 0.0;
+}
+
+// in [n][B] -> out [b][n]
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_unpack(const double *in, u32 b, u64 n, double *out)
+{
+    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (i >= n * B) return;
+    const u32 c = (u32)(i % B);
+    if (c < b) out[(u64)c * n + i / B] = in[i];
+}
+
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_spmm(const uint4 *__restrict__ wl, u64 n_waves, const u32 *__restrict__ col, const double *__restrict__ X, double *Y, double *part)
+{
+    constexpr u32 G = 64 / B;
+    const u64 w = (u64)blockIdx.x * (LZX_MULTI_BLOCK / 64) + (threadIdx.x >> 6);
+    if (w >= n_waves) return;
+    const u32 lane = threadIdx.x & 63, s = lane / B, c = lane % B;
+    const uint4 e = wl[w * G + s];
+    const u64 beg = (u64)e.x | ((u64)e.y << 32);
+    const u32 len = e.z;
+    double acc = 0.0;
+    u32 i = 0;
+    // eight gathers in flight, then added in entry order (the sum's order is the entries' whatever the loads do)
+    for (; i + 8 <= len; i += 8) {
+        u32 j[8];
+        double t[8];
+#pragma unroll
+        for (u32 u = 0; u < 8; ++u) j[u] = col[beg + i + u];
+#pragma unroll
+        for (u32 u = 0; u < 8; ++u) t[u] = X[(u64)j[u] * B + c];
+#pragma unroll
+        for (u32 u = 0; u < 8; ++u) acc += t[u];
+    }
+    for (; i < len; ++i) acc += X[(u64)col[beg + i] * B + c];
+    if (e.w == LZX_MULTI_PAD) return;
+    if (e.w & LZX_MULTI_PART) part[(u64)(e.w & ~LZX_MULTI_PART) * B + c] = acc;
+    else Y[(u64)e.w * B + c] = acc;
+}
+
+// Per row segment and column: LZX_MULTI_RUNS run totals in sh[run * B + c] -> one partial out[c], by a tree whose shape does
+// not depend on B (lane l holds run l, then wave_sum).  Call with all threads; ends with a barrier.
+template <u32 B>
+__device__ __forceinline__ void seg_partials(double *sh, double *out)
+{
+    static_assert(LZX_MULTI_RUNS == 64, "one run per lane");
+    __syncthreads();
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (u32 c = wave; c < B; c += LZX_MULTI_BLOCK / 64) {
+        const double x = wave_sum(sh[lane * B + c]);
+        if (lane == 0) out[c] = x;
+    }
+    __syncthreads();
+}
+
+// All B columns' totals of p[0 .. np) ([np][B]) closed identically in every workgroup: per column the shape of
+// block_sum_fixed_256 (thread t adds entries t, t + 256, ... in index order, then wave_sum, then the four waves in order).
+template <u32 B>
+__device__ __forceinline__ void close_cols(const double *p, u32 np, double *shw /* [4][B] */, double *out /* [B], LDS */)
+{
+    double s[B];
+#pragma unroll
+    for (u32 c = 0; c < B; ++c) s[c] = 0.0;
+    for (u32 i = threadIdx.x; i < np; i += LZX_MULTI_BLOCK) {
+        double t[B];
+#pragma unroll
+        for (u32 c = 0; c < B; c += 2) {
+            const double2 v = *reinterpret_cast<const double2 *>(p + (u64)i * B + c);
+            t[c] = v.x;
+            t[c + 1] = v.y;
+        }
+#pragma unroll
+        for (u32 c = 0; c < B; ++c) s[c] += t[c];
+    }
+#pragma unroll
+    for (u32 c = 0; c < B; ++c) {
+        const double w = wave_sum(s[c]);
+        if ((threadIdx.x & 63) == 0) shw[(threadIdx.x >> 6) * B + c] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < B) {
+        const u32 c = threadIdx.x;
+        out[c] = ((shw[c] + shw[B + c]) + shw[2 * B + c]) + shw[3 * B + c];
+    }
+    __syncthreads();
+}
+
+// Split rows: V[r] = their chunk totals added in chunk order; with Q: partials of alpha = v . q per (row segment, column).
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_alpha(double *V, const double *__restrict__ part, const u32 *__restrict__ split_row, const u32 *__restrict__ split_first,
+                const u32 *__restrict__ run_split, u32 n_split, const double *__restrict__ Q, double *pa, u64 n, u32 n_seg)
+{
+    __shared__ double sh[LZX_MULTI_RUNS * B];
+    for (u32 seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {
+        for (u32 u = threadIdx.x; u < LZX_MULTI_RUNS * B; u += LZX_MULTI_BLOCK) {
+            const u32 run = u / B, c = u % B;
+            const u64 r0 = (u64)seg * LZX_MULTI_SEG + (u64)run * LZX_MULTI_RUN;
+            const u64 r1 = std::min<u64>(r0 + LZX_MULTI_RUN, n);
+            double s = 0.0;
+            u32 ks = r0 < n ? run_split[r0 / LZX_MULTI_RUN] : n_split;
+            if (r0 < n && r1 == r0 + LZX_MULTI_RUN && (ks >= n_split || split_row[ks] >= r1)) {
+                // no split row in this run (nearly every run): eight rows' loads in flight, products added in row order
+                if (Q) {
+                    for (u64 r = r0; r < r1; r += 8) {
+                        double v[8], q[8];
+#pragma unroll
+                        for (u32 t = 0; t < 8; ++t) { v[t] = V[(r + t) * B + c]; q[t] = Q[(r + t) * B + c]; }
+#pragma unroll
+                        for (u32 t = 0; t < 8; ++t) s += v[t] * q[t];
+                    }
+                }
+            } else if (r0 < n) {
+                for (u64 r = r0; r < r1; ++r) {
+                    double v;
+                    if (ks < n_split && split_row[ks] == r) {
+                        v = 0.0;
+                        for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) v += part[(u64)p * B + c];
+                        V[r * B + c] = v;
+                        ++ks;
+                    } else {
+                        v = V[r * B + c];
+                    }
+                    if (Q) s += v * Q[r * B + c];
+                }
+            }
+            sh[u] = s;
+        }
+        if (Q) seg_partials<B>(sh, pa + (u64)seg * B);
+    }
+}
+
+// alpha_c closed from pa by every workgroup; u = v - alpha q_j - beta_{j-1} q_{j-1} in place of v; partials of ||u||^2.
+// A column that stopped before iteration j (beta_{c,j-1} == 0) has alpha = 0 and u = 0.  last: alpha only (grid of one).
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_update(double *V, const double *__restrict__ Qj, const double *__restrict__ Qjm1, const double *pa, u32 n_seg,
+               double *alpha, const double *beta, u32 k, u32 j, double *pn, u64 n, int last)
+{
+    __shared__ double sh[LZX_MULTI_RUNS * B];
+    __shared__ double shw[4 * B], sa[B], sb[B];
+    __shared__ int sstop[B];
+    close_cols<B>(pa, n_seg, shw, sa);
+    if (threadIdx.x < B) {
+        const u32 c = threadIdx.x;
+        const double bp = j > 0 ? beta[(u64)c * k + j - 1] : 0.0;
+        const int stop = j > 0 && bp == 0.0;
+        if (stop) sa[c] = 0.0;
+        sb[c] = bp;
+        sstop[c] = stop;
+        if (blockIdx.x == 0) alpha[(u64)c * k + j] = sa[c];
+    }
+    __syncthreads();
+    if (last) return;
+    for (u32 seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {
+        for (u32 u = threadIdx.x; u < LZX_MULTI_RUNS * B; u += LZX_MULTI_BLOCK) {
+            const u32 run = u / B, c = u % B;
+            const u64 r0 = (u64)seg * LZX_MULTI_SEG + (u64)run * LZX_MULTI_RUN;
+            const u64 r1 = std::min<u64>(r0 + LZX_MULTI_RUN, n);
+            const double a = sa[c], bp = sb[c];
+            const int stop = sstop[c];
+            double s = 0.0;
+            u64 r = r0;
+            // eight rows' loads in flight, then the same operations row by row
+            for (; r + 8 <= r1; r += 8) {
+                double w[8], q[8], p[8];
+#pragma unroll
+                for (u32 t = 0; t < 8; ++t) {
+                    w[t] = V[(r + t) * B + c];
+                    q[t] = Qj[(r + t) * B + c];
+                    p[t] = j > 0 ? Qjm1[(r + t) * B + c] : 0.0;
+                }
+#pragma unroll
+                for (u32 t = 0; t < 8; ++t) {
+                    w[t] -= a * q[t];
+                    if (j > 0) w[t] -= bp * p[t];
+                    if (stop) w[t] = 0.0;
+                    V[(r + t) * B + c] = w[t];
+                    s += w[t] * w[t];
+                }
+            }
+            for (; r < r1; ++r) {
+                const u64 i = r * B + c;
+                double w = V[i];
+                w -= a * Qj[i];
+                if (j > 0) w -= bp * Qjm1[i];
+                if (stop) w = 0.0;
+                V[i] = w;
+                s += w * w;
+            }
+            sh[u] = s;
+        }
+        seg_partials<B>(sh, pn + (u64)seg * B);
+    }
+}
+
+// beta_c = sqrt(closed ||u||^2); the breakdown stop; q_{j+1} = u / beta_c (0 for a column that stopped).  Workgroup 0 stores
+// beta_{c,j} and the running max of |alpha_i| + beta_{i-1} for iteration j (read at j + 1: other slots, no race).
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_scale(const double *__restrict__ V, const double *pn, u32 n_seg, const double *alpha, double *beta, double *mx, u32 k, u32 j,
+              double *Qn, u64 n)
+{
+    __shared__ double shw[4 * B], sq[B], sd[B];
+    close_cols<B>(pn, n_seg, shw, sq);
+    if (threadIdx.x < B) {
+        const u32 c = threadIdx.x;
+        double bt = sqrt(sq[c]);
+        const double bp = j > 0 ? beta[(u64)c * k + j - 1] : 0.0;
+        const double m = fmax(j > 0 ? mx[(u64)(j - 1) * B + c] : 0.0, fabs(alpha[(u64)c * k + j]) + bp);
+        const bool stop = (j > 0 && bp == 0.0) || bt <= 0x1p-40 * m;
+        if (stop) bt = 0.0;
+        sd[c] = bt;
+        if (blockIdx.x == 0) {
+            beta[(u64)c * k + j] = bt;
+            mx[(u64)j * B + c] = m;
+        }
+    }
+    __syncthreads();
+    const u64 total = n * B;
+    for (u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x; i < total; i += (u64)gridDim.x * LZX_MULTI_BLOCK) {
+        const double d = sd[i % B];
+        Qn[i] = d == 0.0 ? 0.0 : V[i] / d;
+    }
+}
+
+// out[r][c] = sum over j < min(k, k_used[c]) of T[c][j] q_{j,c}[r], j ascending
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_multout(const double *__restrict__ Q, u32 k, u64 n, const double *__restrict__ T, const u32 *__restrict__ kused, double *out)
+{
+    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (i >= n * B) return;
+    const u32 c = (u32)(i % B);
+    const u32 kc = std::min(k, kused[c]);
+    double acc = 0.0;
+    for (u32 j = 0; j < kc; ++j) acc += T[(u64)c * k + j] * Q[(u64)j * n * B + i];
+    out[i] = acc;
+}
+
+// ==================================================================================================== host side
+static u32 pad_width(u32 b) { return b <= 2 ? 2 : b <= 4 ? 4 : b <= 8 ? 8 : 16; }
+
+static inline u32 grid_of(u64 threads) { return (u32)((threads + LZX_MULTI_BLOCK - 1) / LZX_MULTI_BLOCK); }
+
+static int check_handle(lzx_ctx *c, const char *fn)
+{
+    if (c->comm_kind != 0 || c->world > 1)
+        LZX_FAIL(LZX_ERR_STATE, "%s: the batched path runs on one GPU handle; this handle is rank %d of a communicator of %d", fn, c->rank, c->world);
+    if (!c->d_row_ptr || !c->d_v) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
+    if (c->n >= LZX_MULTI_PART) LZX_FAIL(LZX_ERR_LIMIT, "%s: %llu vertices (the batched path takes fewer than 2^31)", fn, (unsigned long long)c->n);
+    if (!c->multi) {
+        c->multi = new (std::nothrow) lzx_multi_state;
+        if (!c->multi) LZX_FAIL(LZX_ERR_NOMEM, "%s: host allocation failed", fn);
+    }
+    LZX_HIP(hipSetDevice(c->device));
+    return LZX_OK;
+}
+
+// The work list, once per graph: every row of at most L entries is one segment, a longer row ceil(len / L) chunks of L
+// entries (the last one shorter) whose totals go to slots of d_part; all segments stably sorted by length, longest first.
+static int build_tables(lzx_ctx *c)
+{
+    lzx_multi_state *m = c->multi;
+    const u32 L = c->multi_chunk_opt > 0 ? (u32)std::min<int64_t>(c->multi_chunk_opt, 1 << 30) : LZX_MULTI_CHUNK;
+    if (m->d_wl && m->chunk == L) return LZX_OK;
+    mfree(m->d_wl); mfree(m->d_split_row); mfree(m->d_split_first); mfree(m->d_run_split);
+    const u64 n = c->n;
+    std::vector<u64> rp(n + 1);
+    LZX_HIP(hipMemcpy(rp.data(), c->d_row_ptr, sizeof(u64) * (n + 1), hipMemcpyDeviceToHost));
+    std::vector<u32> split_row, split_first(1, 0);
+    std::vector<u64> count(L + 2, 0);   // segments per length
+    u64 segs = 0;
+    for (u64 r = 0; r < n; ++r) {
+        const u64 len = rp[r + 1] - rp[r];
+        if (len <= L) {
+            ++count[len];
+            ++segs;
+            continue;
+        }
+        const u64 nch = (len + L - 1) / L;
+        if ((u64)split_first.back() + nch >= LZX_MULTI_PART) LZX_FAIL(LZX_ERR_LIMIT, "batched SpMM: too many row chunks");
+        split_row.push_back((u32)r);
+        split_first.push_back(split_first.back() + (u32)nch);
+        count[L] += nch - 1;
+        ++count[len - (nch - 1) * L];
+        segs += nch;
+    }
+    // bucket offsets, longest first
+    std::vector<u64> at(L + 2, 0);
+    u64 acc = 0;
+    for (u64 len = L + 1; len-- > 0;) { at[len] = acc; acc += count[len]; }
+    const u64 n_wl = (segs + 31) / 32 * 32;
+    std::vector<uint4> wl(std::max<u64>(n_wl, 1), make_uint4(0, 0, 0, LZX_MULTI_PAD));
+    auto put = [&](u64 beg, u32 len, u32 dst) { wl[at[len]++] = make_uint4((u32)beg, (u32)(beg >> 32), len, dst); };
+    u32 ks = 0;
+    for (u64 r = 0; r < n; ++r) {
+        const u64 len = rp[r + 1] - rp[r];
+        if (len <= L) { put(rp[r], (u32)len, (u32)r); continue; }
+        for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) {
+            const u64 off = (u64)(p - split_first[ks]) * L;
+            put(rp[r] + off, (u32)std::min<u64>(L, len - off), p | LZX_MULTI_PART);
+        }
+        ++ks;
+    }
+    const u64 runs = (n + LZX_MULTI_RUN - 1) / LZX_MULTI_RUN;
+    std::vector<u32> run_split(runs + 1);
+    {
+        u32 s = 0;
+        for (u64 q = 0; q <= runs; ++q) {
+            while (s < split_row.size() && split_row[s] < q * LZX_MULTI_RUN) ++s;
+            run_split[q] = s;
+        }
+    }
+    m->n_split = (u32)split_row.size();
+    m->n_parts = split_first.back();
+    m->n_wl = n_wl;
+    m->n_seg = (u32)((n + LZX_MULTI_SEG - 1) / LZX_MULTI_SEG);
+    int rc;
+    if ((rc = malloc_n(&m->d_wl, wl.size(), "work list")) || (rc = malloc_n(&m->d_split_row, std::max<size_t>(split_row.size(), 1), "split rows")) ||
+        (rc = malloc_n(&m->d_split_first, split_first.size(), "split rows")) || (rc = malloc_n(&m->d_run_split, run_split.size(), "split rows"))) {
+        mfree(m->d_wl); mfree(m->d_split_row); mfree(m->d_split_first); mfree(m->d_run_split);
+        return rc;
+    }
+    LZX_HIP(hipMemcpy(m->d_wl, wl.data(), sizeof(uint4) * wl.size(), hipMemcpyHostToDevice));
+    if (!split_row.empty()) LZX_HIP(hipMemcpy(m->d_split_row, split_row.data(), sizeof(u32) * split_row.size(), hipMemcpyHostToDevice));
+    LZX_HIP(hipMemcpy(m->d_split_first, split_first.data(), sizeof(u32) * split_first.size(), hipMemcpyHostToDevice));
+    LZX_HIP(hipMemcpy(m->d_run_split, run_split.data(), sizeof(u32) * run_split.size(), hipMemcpyHostToDevice));
+    m->chunk = L;
+    return LZX_OK;
+}
+
+static int ensure_work(lzx_ctx *c, u32 B)
+{
+    lzx_multi_state *m = c->multi;
+    if (m->wB == B && m->d_V) return LZX_OK;
+    free_work(m);
+    const u64 n = c->n;
+    int rc;
+    if ((rc = malloc_n(&m->d_V, n * B, "work vector")) || (rc = malloc_n(&m->d_X, n * B, "work vector")) ||
+        (rc = malloc_n(&m->d_part, (u64)m->n_parts * B, "chunk totals")) || (rc = malloc_n(&m->d_pa, (u64)m->n_seg * B, "partials")) ||
+        (rc = malloc_n(&m->d_pn, (u64)m->n_seg * B, "partials"))) {
+        free_work(m);
+        return rc;
+    }
+    m->wB = B;
+    return LZX_OK;
+}
+
+static int ensure_basis(lzx_ctx *c, u32 k, u32 B)
+{
+    lzx_multi_state *m = c->multi;
+    m->resident = false;
+    if (m->d_Q && m->k == k && m->B == B) return LZX_OK;
+    free_basis(m);
+    const u64 bytes = (u64)k * c->n * B * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > (u64)total_b) {
+        free_work(m);
+        LZX_FAIL(LZX_ERR_NOMEM, "lzx_lanczos_multi_f64: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8), the device has %llu",
+                 (unsigned long long)bytes, k, (unsigned long long)c->n, B, (unsigned long long)total_b);
+    }
+    (void)hipGetLastError();
+    int rc;
+    if ((rc = malloc_n(&m->d_Q, (u64)k * c->n * B, "batch basis")) || (rc = malloc_n(&m->d_alpha, (u64)B * k, "coefficients")) ||
+        (rc = malloc_n(&m->d_beta, (u64)B * k, "coefficients")) || (rc = malloc_n(&m->d_T, (u64)B * k, "coefficients")) ||
+        (rc = malloc_n(&m->d_mx, (u64)k * B, "coefficients")) || (rc = malloc_n(&m->d_kused, B, "coefficients"))) {
+        free_basis(m);
+        free_work(m);
+        if (rc == LZX_ERR_NOMEM)
+            lzx_set_error("lzx_lanczos_multi_f64: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8) and does not fit",
+                          (unsigned long long)bytes, k, (unsigned long long)c->n, B);
+        return rc;
+    }
+    m->k = k;
+    m->B = B;
+    return LZX_OK;
+}
+
+// Y = A X on [n][B] vectors, split rows finished into Y; with Q: alpha partials into pa (the loop's first two launches)
+template <u32 B>
+static int launch_spmm(lzx_ctx *c, const double *X, double *Y, const double *Q)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n_waves = m->n_wl / (64 / B);
+    if (n_waves)
+        hipLaunchKernelGGL(k_multi_spmm<B>, dim3((u32)((n_waves + 3) / 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_wl, n_waves,
+                           c->d_col_idx, X, Y, m->d_part);
+    if (m->n_seg && (Q || m->n_split))
+        hipLaunchKernelGGL(k_multi_alpha<B>, dim3(std::min<u32>(m->n_seg, (u32)c->cu_count * 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, Y,
+                           m->d_part, m->d_split_row, m->d_split_first, m->d_run_split, m->n_split, Q, m->d_pa, c->n, m->n_seg);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+template <u32 B>
+static int multi_loop(lzx_ctx *c, u32 b, const double *X0, u32 k, double *alpha, double *beta, uint32_t *k_used, double *x_norm,
+                      double *Q, lzx_stats *stats)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n = c->n, nB = n * B;
+    // ||x_c||: left-to-right sum of squares, then sqrt (serial/lib/lanczos.cc:155-161), as lzx_lanczos_prepare_f64 forms it
+    MultiDiv div{};
+    for (u32 col = 0; col < 16; ++col) div.v[col] = 1.0;
+    for (u32 col = 0; col < b; ++col) {
+        double s = 0.0;
+        const double *x = X0 + (u64)col * n;
+        for (u64 i = 0; i < n; ++i) s += x[i] * x[i];
+        div.v[col] = std::sqrt(s);
+        x_norm[col] = div.v[col];
+    }
+    int rc = ensure_basis(c, k, B);
+    if (rc == LZX_OK) rc = ensure_work(c, B);
+    if (rc != LZX_OK) {   // nothing half-built is left behind
+        free_basis(m);
+        free_work(m);
+        return rc;
+    }
+    // x0 staged in the work vector as [b][n], packed into column 0 of the basis
+    LZX_HIP(hipMemcpyAsync(m->d_V, X0, sizeof(double) * b * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_multi_pack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, div, m->d_Q);
+    LZX_HIP(hipGetLastError());
+
+    // timing marks: every 4th iteration (every one when k < 8); each mark is a barrier packet
+    const u32 every = k < 8 ? 1 : 4;
+    const u32 marked = (k + every - 1) / every;
+    while (m->ev.size() < 3 * (size_t)marked) {
+        hipEvent_t e;
+        LZX_HIP(hipEventCreate(&e));
+        m->ev.push_back(e);
+    }
+    const u32 vgrid = std::min<u32>(std::max<u32>(m->n_seg, 1), (u32)c->cu_count * 4);
+    const u32 sgrid = std::min<u32>(grid_of(nB), (u32)c->cu_count * 8);
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (u32 j = 0; j < k; ++j) {
+        const bool mark = j % every == 0;
+        hipEvent_t *e = m->ev.data() + 3 * (j / every);
+        double *qj = m->d_Q + (u64)j * nB;
+        if (mark) LZX_HIP(hipEventRecord(e[0], c->stream));
+        LZX_TRY(launch_spmm<B>(c, qj, m->d_V, qj));
+        if (mark) LZX_HIP(hipEventRecord(e[1], c->stream));
+        const bool last = j + 1 == k;
+        hipLaunchKernelGGL(k_multi_update<B>, dim3(last ? 1 : vgrid), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, qj,
+                           j ? qj - nB : qj, m->d_pa, m->n_seg, m->d_alpha, m->d_beta, k, j, m->d_pn, n, last ? 1 : 0);
+        if (!last)
+            hipLaunchKernelGGL(k_multi_scale<B>, dim3(sgrid), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, m->d_pn, m->n_seg,
+                               m->d_alpha, m->d_beta, m->d_mx, k, j, qj + nB, n);
+        LZX_HIP(hipGetLastError());
+        if (mark) LZX_HIP(hipEventRecord(e[2], c->stream));
+    }
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    const double loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+
+    std::vector<double> ha((u64)B * k), hb((u64)B * k);
+    LZX_HIP(hipMemcpy(ha.data(), m->d_alpha, sizeof(double) * ha.size(), hipMemcpyDeviceToHost));
+    LZX_HIP(hipMemcpy(hb.data(), m->d_beta, sizeof(double) * hb.size(), hipMemcpyDeviceToHost));
+    m->h_kused.assign(B, 0);
+    for (u32 col = 0; col < b; ++col) {
+        u32 ku = k;
+        for (u32 j = 0; j + 1 < k; ++j)
+            if (hb[(u64)col * k + j] == 0.0) { ku = j + 1; break; }
+        m->h_kused[col] = ku;
+        k_used[col] = ku;
+        for (u32 j = 0; j < k; ++j) {
+            alpha[(u64)col * k + j] = ha[(u64)col * k + j];
+            beta[(u64)col * k + j] = j + 1 < k ? hb[(u64)col * k + j] : 0.0;
+        }
+    }
+    LZX_HIP(hipMemcpy(m->d_kused, m->h_kused.data(), sizeof(u32) * B, hipMemcpyHostToDevice));
+    if (Q) {
+        // column j of every vector: [n][B] -> [b][n] in the work vector, then b rows of n with a stride of k * n on the host
+        for (u32 j = 0; j < k; ++j) {
+            hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q + (u64)j * nB, b, n, m->d_X);
+            LZX_HIP(hipGetLastError());
+            LZX_HIP(hipMemcpy2DAsync(Q + (u64)j * n, sizeof(double) * k * n, m->d_X, sizeof(double) * n, sizeof(double) * n, b,
+                                     hipMemcpyDeviceToHost, c->stream));
+        }
+        LZX_HIP(hipStreamSynchronize(c->stream));
+    }
+    m->b = b;
+    m->resident = true;
+    if (stats) {
+        double spmm = 0, vec = 0, mn = 1e300;
+        for (u32 q = 0; q < marked; ++q) {
+            float a = 0.f, v = 0.f;
+            hipEvent_t *e = m->ev.data() + 3 * q;
+            LZX_HIP(hipEventElapsedTime(&a, e[0], e[1]));
+            LZX_HIP(hipEventElapsedTime(&v, e[1], e[2]));
+            spmm += a;
+            vec += v;
+            mn = std::min(mn, (double)a);
+        }
+        const double scale = (double)k / marked;
+        stats->loop_ms = loop_ms;
+        stats->spmv_ms = spmm * scale;
+        stats->spmv_ms_min = mn;
+        stats->vec_ms = vec * scale;
+        stats->comm_ms = 0.0;
+        stats->iters = k;
+        stats->spmv_kernels = 4;   // launches per iteration: SpMM, split rows + alpha partials, update, scale
+        stats->spmv_bytes = 4ull * c->nnz + 8ull * (n + 1) + 16ull * b * n;
+    }
+    return LZX_OK;
+}
+
+template <u32 B>
+static int spmm_run(lzx_ctx *c, u32 b, const double *X, double *Y)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n = c->n, nB = n * B;
+    LZX_TRY(ensure_work(c, B));
+    MultiDiv one{};
+    for (u32 col = 0; col < 16; ++col) one.v[col] = 1.0;
+    LZX_HIP(hipMemcpyAsync(m->d_V, X, sizeof(double) * b * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_multi_pack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, one, m->d_X);
+    LZX_HIP(hipGetLastError());
+    LZX_TRY(launch_spmm<B>(c, m->d_X, m->d_V, nullptr));
+    hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
+    LZX_HIP(hipGetLastError());
+    LZX_HIP(hipMemcpyAsync(Y, m->d_X, sizeof(double) * b * n, hipMemcpyDeviceToHost, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    return LZX_OK;
+}
+
+template <u32 B>
+static int multout_run(lzx_ctx *c, u32 b, const double *T, u32 k, double *ans)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n = c->n, nB = n * B;
+    LZX_TRY(ensure_work(c, B));
+    std::vector<double> t((u64)B * k, 0.0);
+    for (u32 col = 0; col < b; ++col)
+        for (u32 j = 0; j < std::min(k, m->h_kused[col]); ++j) t[(u64)col * k + j] = T[(u64)col * k + j];
+    LZX_HIP(hipMemcpyAsync(m->d_T, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_multi_multout<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q, k, n, m->d_T, m->d_kused, m->d_V);
+    hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
+    LZX_HIP(hipGetLastError());
+    LZX_HIP(hipMemcpyAsync(ans, m->d_X, sizeof(double) * b * n, hipMemcpyDeviceToHost, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    return LZX_OK;
+}
+
+#define LZX_MULTI_DISPATCH(B, fn, ...)     \
+    switch (B) {                           \
+    case 2: return fn<2>(__VA_ARGS__);     \
+    case 4: return fn<4>(__VA_ARGS__);     \
+    case 8: return fn<8>(__VA_ARGS__);     \
+    default: return fn<16>(__VA_ARGS__);   \
+    }
+
+// ==================================================================================================== C ABI
+extern "C" int lzx_lanczos_multi_f64(lzx_handle h, uint32_t b, const double *X0, uint32_t k, double *alpha, double *beta,
+                                     uint32_t *k_used, double *x_norm, double *Q, lzx_stats *stats)
+{
+    static const char *fn = "lzx_lanczos_multi_f64";
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    if (b == 0) LZX_FAIL(LZX_ERR_ARG, "%s: b == 0", fn);
+    if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
+    if (!X0) LZX_FAIL(LZX_ERR_ARG, "%s: null X0", fn);
+    if (!alpha || !beta) LZX_FAIL(LZX_ERR_ARG, "%s: null alpha / beta", fn);
+    if (!k_used || !x_norm) LZX_FAIL(LZX_ERR_ARG, "%s: null k_used / x_norm", fn);
+    if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
+    LZX_TRY(check_handle(h, fn));
+    for (u32 col = 0; col < b; ++col) {
+        const double *x = X0 + (u64)col * h->n;
+        if (std::all_of(x, x + h->n, [](double v) { return v == 0.0; }))
+            LZX_FAIL(LZX_ERR_ARG, "%s: column %u of X0 is all zero", fn, col);
+    }
+    int rc = build_tables(h);
+    if (rc) return rc;
+    const u32 B = pad_width(b);
+    LZX_MULTI_DISPATCH(B, multi_loop, h, b, X0, k, alpha, beta, k_used, x_norm, Q, stats);
+}
+
+extern "C" int lzx_multout_multi_f64(lzx_handle h, uint32_t b, const double *T, uint32_t k, double *ans)
+{
+    static const char *fn = "lzx_multout_multi_f64";
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    if (b == 0) LZX_FAIL(LZX_ERR_ARG, "%s: b == 0", fn);
+    if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
+    if (!T || !ans) LZX_FAIL(LZX_ERR_ARG, "%s: null T / ans", fn);
+    if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
+    LZX_TRY(check_handle(h, fn));
+    lzx_multi_state *m = h->multi;
+    if (!m->resident) LZX_FAIL(LZX_ERR_STATE, "%s: no batched decomposition is resident", fn);
+    if (b != m->b || k > m->k)
+        LZX_FAIL(LZX_ERR_ARG, "%s: the resident batch has b = %u columns of k = %u vectors (asked b = %u, k = %u)", fn, m->b, m->k, b, k);
+    LZX_MULTI_DISPATCH(m->B, multout_run, h, b, T, k, ans);
+}
+
+extern "C" int lzx_spmm_f64(lzx_handle h, uint32_t b, const double *X, double *Y)
+{
+    static const char *fn = "lzx_spmm_f64";
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    if (b == 0) LZX_FAIL(LZX_ERR_ARG, "%s: b == 0", fn);
+    if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
+    if (!X || !Y) LZX_FAIL(LZX_ERR_ARG, "%s: null X / Y", fn);
+    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(build_tables(h));
+    // (the resident batch keeps its basis: only the work vectors may change width)
+    LZX_MULTI_DISPATCH(pad_width(b), spmm_run, h, b, X, Y);
+}
+
+extern "C" int lzx_multi_release(lzx_handle h)
+{
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "lzx_multi_release: null handle (h)");
+    lzx_multi_free(h, false);
+    return LZX_OK;
+}

@@ -12,7 +12,8 @@
 // scatter units of the shared launch instead of ahead of them), "start_vector_scan" (0: lzx_lanczos_prepare_f64 always uploads x0 and
 // sums its squares in one serial chain; default: one look at x0 first -- a constant vector is filled on the device, a sum that is
 // exact in any order is formed by several threads), "defer_finish" (0: the blocked SpMV always launches k_pb_finish; default: in the lazy loop
-// k_lazy_update adds the totals of multi-item gather bands where it reads v and the launch is left out).
+// k_lazy_update adds the totals of multi-item gather bands where it reads v and the launch is left out), "multi_row_chunk" (entries per
+// chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"

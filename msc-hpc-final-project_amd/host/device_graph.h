@@ -19,6 +19,9 @@ struct deviceGraph {
   // previous owner is told to bring its basis to the host.
   void *owner = nullptr;
   void (*evict)(void *owner) = nullptr;
+  // The resident batch basis (lzx_lanczos_multi_f64) is separate from it: which lanczosDecompMulti's batch (first column) it holds.
+  const void *multi_owner = nullptr;
+  unsigned multi_first = 0;
   deviceGraph() = default;
   deviceGraph(const deviceGraph &) = delete;
   deviceGraph &operator=(const deviceGraph &) = delete;

@@ -11,6 +11,7 @@
 #include "adjMatrix.h"
 #include "cu_lanczos.h"
 #include "eigen.h"
+#include "lanczos_multi.h"
 #include "multiplyOut.h"
 
 static std::string g_host_err;
@@ -182,6 +183,32 @@ long host_reference_order_check(const char *path, unsigned k, double *alpha_dev,
           return 0;
         }
     return 1;
+  } catch (const std::exception &e) {
+    g_host_err = e.what();
+    return -3;
+  }
+}
+
+// lanczosDecompMulti(A, k, X, b, cuda) + multOutMulti on a graph file: X[b][n] starting vectors; outputs ans[b][n], alpha[b][k],
+// beta[b][k], k_used[b], x_norm[b] (any may be NULL except ans).  Returns n or < 0.
+long host_expm_multi_file(const char *path, unsigned k, unsigned b, const double *X, int cuda, double *ans, unsigned ans_len,
+                          double *alpha, double *beta, unsigned *k_used, double *x_norm) {
+  try {
+    std::ifstream fs(path);
+    if (fs.fail()) { g_host_err = std::string("cannot open ") + path; return -1; }
+    unsigned n = 0, edges = 0;
+    fs >> n >> n >> edges;
+    adjMatrix A(n, edges, fs);
+    if (ans_len < static_cast<std::size_t>(n) * b) { g_host_err = "answer buffer too small"; return -2; }
+    lanczosDecompMulti L(A, k, X, b, cuda != 0);
+    multOutMulti(L, A);
+    const std::size_t bk = static_cast<std::size_t>(b) * k;
+    std::copy(L.answer(), L.answer() + static_cast<std::size_t>(n) * b, ans);
+    if (alpha) std::copy(L.get_alpha(), L.get_alpha() + bk, alpha);
+    if (beta) std::copy(L.get_beta(), L.get_beta() + bk, beta);
+    if (k_used) std::copy(L.k_used(), L.k_used() + b, k_used);
+    if (x_norm) std::copy(L.x_norms(), L.x_norms() + b, x_norm);
+    return static_cast<long>(n);
   } catch (const std::exception &e) {
     g_host_err = e.what();
     return -3;
