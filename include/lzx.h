@@ -261,8 +261,12 @@ int lzx_bench_spmv(lzx_handle h, uint32_t reps, double *avg_ms, double *min_ms);
  * bytes (rounded to 16; >= 256 MiB recommended), best of `reps`.  Results in GB/s (copy: bytes read + bytes written). */
 int lzx_bench_stream(lzx_handle h, uint64_t bytes, uint32_t reps, double *read_gbs, double *copy_gbs);
 
-/* Options, to be set before the graph is handed over (the last two: any time; setting one abandons a decomposition that
- * was being advanced in chunks):
+/* Values of the option "operator" (below). */
+#define LZX_OP_ADJACENCY 0
+#define LZX_OP_LAPLACIAN 1
+
+/* Options, to be set before the graph is handed over ("reorthogonalise", "basis_fp32", "reference_order" and "operator":
+ * any time; setting one abandons a decomposition that was being advanced in chunks):
  *   "hub_entries"           x values of the highest-degree vertices staged in LDS by the SpMV (0 = none)
  *   "propagation_blocking"  1 / 0 force the two-pass blocked treatment of non-staged columns on / off
  *                           (default: on for graphs whose x does not fit the L2s); with it off the sliced-ELL
@@ -334,7 +338,27 @@ int lzx_bench_stream(lzx_handle h, uint64_t bytes, uint32_t reps, double *read_g
  *                           twice); the rank keeps its own rows -- what parallel-two-cards does for its two halves
  *                           (parallel-two-cards/lib/cu_lanczos.cu:94-95,108-109).  Default 0.  C5, rank 0 of 8: 19 GB at the peak and 8.7 GB
  *                           resident instead of 102 / 17+ GB, 12.7 s instead of 5.8 s (profiles/r4_sharded_ingest.txt).
- * These twelve are all liblzx.so knows.  The experiment knobs and test hooks behind DESIGN.md's tuning log ("pb_*",
+ *   "operator"              the matrix M the Krylov space is built on.  LZX_OP_ADJACENCY (0, default): M = A, as above.
+ *                           LZX_OP_LAPLACIAN (1): the combinatorial Laplacian M = L = D - A, d_i = the number of stored
+ *                           entries of row i (rows without an edge: d_i = 0, (L x)_i = 0), for the heat kernel e^{-tL} x.
+ *                           (L x)_i := fma(d_i, x_i, -s_i), s_i = row i of A x summed exactly as the current mode sums it,
+ *                           one explicit fused multiply-add on the device and in the C++ class path alike, so that
+ *                           "reference_order" stays bit-identical to that path.  The per-row degree array (4 bytes per
+ *                           row) is built on the first use of L and kept as long as the graph; A allocates nothing new.
+ *                           Breakdown stop: L 1 = 0, so the start vector ones (and any vector in a small invariant
+ *                           subspace) exhausts the Krylov space.  Under L a beta_j <= 2^-40 * 2 d_max (2 d_max: the
+ *                           Gershgorin bound of ||L||) is returned as exactly 0 and so are every later alpha, beta and
+ *                           basis column; the caller trims T at the first zero beta.  Under A nothing changes.
+ *                           Where L runs: every loop form -- plain, lazy (one rank or several, every exchange and
+ *                           reduction), "reference_order", "reorthogonalise" -- applies v = fma(d, q, -v) after the SpMV,
+ *                           and lzx_spmv_f64 / _local return L x.  The batched path applies fma(d_i, X[i][c], -sum) after
+ *                           the chunk totals of split rows (lzx_spmm_f64 returns L X) and stops a column at the same
+ *                           threshold.  Refused with LZX_ERR_STATE (and a message): "basis_fp32" (it stores the
+ *                           unnormalised basis u_j = beta_{j-1} q_j, which a stop leaves with beta = 0 to divide by; under L
+ *                           the lazy loop keeps q_j), and a sharded hand-over of a CSR in host memory (no rank holds the row
+ *                           pointers the degrees come from).  Any other value: LZX_ERR_ARG.  May be changed between
+ *                           decompositions.
+ * These thirteen are all liblzx.so knows.  The experiment knobs and test hooks behind DESIGN.md's tuning log ("pb_*",
  * "phase_mask", "exchange_at_world_1", ...) exist only in liblzx_dbg.so, the same sources built with -DLZX_DEBUG_KNOBS
  * (`make debug`); tools/perf_probe.py and the tests that need them load that library.                               */
 int lzx_set_option(lzx_handle h, const char *name, int64_t value);

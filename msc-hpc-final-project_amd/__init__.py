@@ -18,7 +18,7 @@ DBG_LIB_PATH = os.path.join(_HERE, "liblzx_dbg.so")
 # what the product library's lzx_set_option knows (include/lzx.h); any other option name selects the debug library
 PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "sparse_exchange", "exchange_fp32",
                    "lazy_normalisation", "timing_marks_every", "reorthogonalise", "basis_fp32", "reference_order", "placement_trials",
-                   "sharded_ingest")
+                   "sharded_ingest", "operator")
 
 # test-only shapes the product library accepts through lzx_test_set_shape (csrc/lzx_test_hooks.h): they select among code
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
@@ -157,6 +157,28 @@ def _check(rc: int, what: str, L=None):
         raise LzxError(f"{what} failed ({rc}): {(L or lib()).lzx_last_error().decode(errors='replace')}")
 
 
+# values of the option "operator" (include/lzx.h)
+OP_ADJACENCY = 0
+OP_LAPLACIAN = 1
+
+
+def _expm_coefficients(alpha, beta, x_norm, s):
+    """t = V (e^{s theta} .* ||x|| V[0, :]) of the tridiagonal T (host/multiplyOut.cc: small_part), T trimmed at the first zero
+    beta (under L the breakdown stop returns every later coefficient and basis column as 0); zeros behind the trimmed block."""
+    k = len(alpha)
+    kb = k
+    zero = np.flatnonzero(np.asarray(beta[:k - 1]) == 0.0)
+    if zero.size:
+        kb = int(zero[0]) + 1
+    T = np.diag(np.asarray(alpha[:kb], dtype=np.float64))
+    if kb > 1:
+        T += np.diag(beta[:kb - 1], 1) + np.diag(beta[:kb - 1], -1)
+    lam, V = np.linalg.eigh(T)
+    t = np.zeros(k)
+    t[:kb] = V @ (np.exp(s * lam) * (x_norm * V[0, :]))
+    return t
+
+
 def rmat_thresholds(a=0.57, b=0.19, c=0.19):
     return int(round(a * 65536)), int(round((a + b) * 65536)), int(round((a + b + c) * 65536))
 
@@ -166,6 +188,7 @@ class Engine:
 
     def __init__(self, device: int = 0, **options):
         self.h = ctypes.c_void_p()
+        self.operator = OP_ADJACENCY
         self.debug = any(k not in PRODUCT_OPTIONS and k not in SHAPE_OPTIONS for k in options)   # experiment knobs: liblzx_dbg.so
         self.L = lib(debug=self.debug)
         _check(self.L.lzx_create(ctypes.byref(self.h), device), "lzx_create", self.L)
@@ -178,6 +201,8 @@ class Engine:
             _check(self.L.lzx_test_set_shape(self.h, name.encode(), int(value)), f"lzx_test_set_shape({name})", self.L)
             return
         _check(self.L.lzx_set_option(self.h, name.encode(), int(value)), f"lzx_set_option({name})", self.L)
+        if name == "operator":
+            self.operator = int(value)
 
     def shape(self, name: str) -> int:
         """what shape the blocked tables took (test hook lzx_test_get_shape): gather_items_dealt / _drawn, gather_workgroups"""
@@ -356,6 +381,13 @@ class Engine:
         _check(self.L.lzx_multout_f64(self.h, _p(t, _f64p), len(t), _p(ans, _f64p)), "lzx_multout_f64", self.L)
         return ans
 
+    def expm_multiply(self, x0, k: int, t: float = 1.0):
+        """e^{tA} x0 (operator adjacency) or the heat kernel e^{-tL} x0 (operator laplacian): k Lanczos iterations, the small
+        eigenproblem on the host, the answer formed from the resident basis (lzx_multout_f64)."""
+        alpha, beta, _, xn, _ = self.lanczos(x0, k, want_q=False)
+        s = -t if self.operator == OP_LAPLACIAN else t
+        return self.multout(_expm_coefficients(alpha, beta, xn, s))
+
     # ---- batched, independent Lanczos (include/lzx.h: up to 16 starting vectors, one SpMM per iteration) ----
     def _batch(self, X, what):
         X = np.ascontiguousarray(X, dtype=np.float64)
@@ -477,6 +509,12 @@ class LocalGroup:
         ans = np.empty(self.n)
         _check(self.L.lzx_multout_f64_local(self.arr, self.world, _p(t, _f64p), len(t), _p(ans, _f64p)), "lzx_multout_f64_local", self.L)
         return ans
+
+    def expm_multiply(self, x0, k: int, t: float = 1.0):
+        """Engine.expm_multiply over the group (the handles' operator)."""
+        alpha, beta, _, xn, _ = self.lanczos(x0, k, want_q=False)
+        s = -t if getattr(self.engines[0], "operator", OP_ADJACENCY) == OP_LAPLACIAN else t
+        return self.multout(_expm_coefficients(alpha, beta, xn, s))
 
     def lanczos_multi(self, X0, k: int, want_q: bool = False):
         """The batched path is one-GPU: the library refuses a handle of a communicator (LzxError naming the group's size)."""

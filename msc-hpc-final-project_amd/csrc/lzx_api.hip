@@ -100,8 +100,11 @@ extern "C" void lzx_destroy(lzx_handle c)
 extern "C" int lzx_set_option(lzx_handle c, const char *name, int64_t value)
 {
     if (!c || !name) LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: bad argument");
-    // the two options that shape the LOOP, not the graph, may change between decompositions
-    const bool loop_option = !strcmp(name, "reorthogonalise") || !strcmp(name, "basis_fp32") || !strcmp(name, "reference_order");
+    // the options that shape the LOOP, not the graph, may change between decompositions
+    const bool loop_option = !strcmp(name, "reorthogonalise") || !strcmp(name, "basis_fp32") || !strcmp(name, "reference_order") ||
+                             !strcmp(name, "operator");
+    if (!strcmp(name, "operator") && value != LZX_OP_ADJACENCY && value != LZX_OP_LAPLACIAN)
+        LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: operator must be LZX_OP_ADJACENCY (0) or LZX_OP_LAPLACIAN (1), got %lld", (long long)value);
     if (c->d_row_ptr && !loop_option) LZX_FAIL(LZX_ERR_STATE, "options must be set before the graph is handed over");
     if (loop_option) c->k_prep = 0;   // a decomposition that was being advanced in chunks is abandoned (what it has done stays usable)
     if (!strcmp(name, "hub_entries")) c->hub_opt = value;
@@ -114,6 +117,7 @@ extern "C" int lzx_set_option(lzx_handle c, const char *name, int64_t value)
     else if (!strcmp(name, "reorthogonalise")) c->reorth_opt = value;
     else if (!strcmp(name, "basis_fp32")) c->qf32_opt = value;
     else if (!strcmp(name, "reference_order")) c->ref_order_opt = value;
+    else if (!strcmp(name, "operator")) c->op_opt = value;
     else if (!strcmp(name, "placement_trials")) c->place_opt = value;
     else if (!strcmp(name, "sharded_ingest")) c->shard_opt = value < 0 ? 0 : value;
 #ifdef LZX_DEBUG_KNOBS
@@ -489,12 +493,16 @@ static int lanczos_prepare(std::vector<lzx_ctx *> &cs, const double *x0, u32 k, 
     };
     for (lzx_ctx *c : cs) {
         if (c->reorth_opt != c0->reorth_opt || c->qf32_opt != c0->qf32_opt) LZX_FAIL(LZX_ERR_STATE, "handles carry different loop options");
+        if (c->qf32_opt > 0 && c->op_opt == LZX_OP_LAPLACIAN)
+            LZX_FAIL(LZX_ERR_STATE, "basis_fp32 stores the unnormalised basis, which operator laplacian does not keep (its breakdown stop leaves beta = 0 to divide by)");
         if (c->qf32_opt > 0 && (!lazy || c->basis_u_opt == 0))
             LZX_FAIL(LZX_ERR_STATE, "basis_fp32 needs the lazy loop (not with lazy_normalisation = 0, not together with reorthogonalise)");
         if (c->ref_order_opt > 0 && (multi || cs.size() > 1))
             LZX_FAIL(LZX_ERR_STATE, "option reference_order runs on one rank");
         if (c->ref_order_opt > 0 && c->qf32_opt > 0)
             LZX_FAIL(LZX_ERR_STATE, "option reference_order keeps the fp64 basis (not together with basis_fp32)");
+        if (c->op_opt != c0->op_opt) LZX_FAIL(LZX_ERR_STATE, "handles carry different operators");
+        if (c->op_opt == LZX_OP_LAPLACIAN) LZX_TRY(lzx_ensure_degrees(c));   // operator L: the per-row degrees, once per graph
     }
     // From here on the resident basis of an earlier decomposition is gone (its buffers may be reallocated or change form):
     // nothing is resident and nothing prepared until this call has succeeded on every handle -- a failure part-way leaves
@@ -572,7 +580,8 @@ static int lanczos_prepare(std::vector<lzx_ctx *> &cs, const double *x0, u32 k, 
             c->iso_on = lazy && c->iso_opt != 0;
             c->iso_filled = false;
             c->iso_cols_filled = 1;
-            c->basis_u = lazy && c->basis_u_opt != 0;
+            // (operator L: the basis holds q_j, so that a breakdown stop -- beta = 0 -- leaves nothing to divide by it)
+            c->basis_u = lazy && c->basis_u_opt != 0 && c->op_opt != LZX_OP_LAPLACIAN;
             // columns 1.. are written by the loop up to rows_live only; with several ranks the exchanged prefix may reach
             // one slice further (into rows without an edge, which nobody reads): keep that slice clean
             if (!c->qf32 && c->basis_u && c->iso_on && k > 1 && c->rows_live < c->n_loc_pad)
@@ -628,10 +637,14 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
         std::vector<lzx_ctx *> &cs;
         Deferring(std::vector<lzx_ctx *> &h, bool on) : cs(h) { for (lzx_ctx *c : cs) c->pb_deferring = on && c->defer_opt != 0; }
         ~Deferring() { for (lzx_ctx *c : cs) c->pb_deferring = false; }
-    } deferring(cs, lazy);
+    } deferring(cs, lazy && c0->op_opt != LZX_OP_LAPLACIAN);   // operator L: v is complete before k_lap_apply reads it
     const bool mail_ok = multi && lzx_comm_mail_usable(cs);
     // timing marks on every 4th iteration (every one when k is small); the sums below are scaled to all iterations run
     const u32 every = c0->marks_every_opt > 0 ? (u32)c0->marks_every_opt : (k >= 8 ? 4u : 1u);
+    // operator L: after every SpMV, k_lap_apply turns A x into L x and the SpMV's alpha partials into those of L x; the vector
+    // kernels then stop at beta <= 2^-40 * 2 d_max (lzx_stop_threshold)
+    const bool lap = c0->op_opt == LZX_OP_LAPLACIAN;
+    const double stop = lzx_stop_threshold(c0);
     for (u32 j = j0; lazy && j < j1; ++j) {
         const bool first = j == 0, last = j == k - 1;
         LZX_TRY(mk.begin_iteration(j, every));
@@ -649,6 +662,8 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
             l.live_rows_only = true;   // k_lazy_update below takes (A u)_i = 0 for rows without an edge
             if (overlap && j > 0) l.chunk1_ready = c->ev_c1;
             LZX_TRY(lzx_launch_spmv(c, l));
+            // operator L: w = d .* u_j - w over the rows with an edge, and D = u_j . (L u_j) in the SpMV's partials
+            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, uj, c->d_partials, lzx_spmv_partials(c), c->rows_live));
         }
         LZX_TRY(mk.tick(CAT_SPMV));
         u32 np2 = 0;
@@ -756,12 +771,15 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
             const double *qj = c->d_Q + (size_t)j * c->ldq;
             if (ref) {
                 LZX_TRY(lzx_launch_ref_spmv(c, qj, c->d_v));
+                if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, nullptr, 0, c->n_loc_pad));   // (alpha: k_ref_dot below)
                 LZX_TRY(lzx_launch_ref_dot(c, c->d_v, qj, c->d_scal + 0));   // alpha_j = <v, q_j>, left to right
                 continue;
             }
             SpmvLaunch l{multi ? c->d_xbuf : qj, qj, c->d_v, c->d_partials};
             if (overlap && j > 0) l.chunk1_ready = c->ev_c1;
             LZX_TRY(lzx_launch_spmv(c, l));
+            // operator L: v = d .* q_j - v; the alpha_j partials are formed again, on L q_j
+            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, c->d_partials, lzx_spmv_partials(c), c->n_loc_pad));
         }
         LZX_TRY(mk.tick(CAT_SPMV));
 
@@ -836,7 +854,7 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
         for (lzx_ctx *c : cs) {
             LZX_HIP(hipSetDevice(c->device));
             LZX_TRY(lzx_launch_scale(c, c->d_v, c->d_Q + (size_t)(j + 1) * c->ldq,
-                                     scal ? c->d_scal + 1 : c->d_partials2, scal ? 1 : np2, c->d_beta + j));
+                                     scal ? c->d_scal + 1 : c->d_partials2, scal ? 1 : np2, c->d_beta + j, stop));
         }
         LZX_TRY(mk.tick(CAT_VEC));
 
@@ -1076,6 +1094,12 @@ static int spmv_run(std::vector<lzx_ctx *> &cs, const double *x, double *y)
     const bool multi = lzx_exchanges(c0);
     std::vector<const double *> src(cs.size());
     std::vector<double *> dst(cs.size());
+    // operator L (the handle's option): one rank, y = d .* x - A x with the loop's own kernel
+    const bool lap = c0->op_opt == LZX_OP_LAPLACIAN;
+    for (lzx_ctx *c : cs) {
+        if (c->op_opt != c0->op_opt) LZX_FAIL(LZX_ERR_STATE, "handles carry different operators");
+        if (lap) LZX_TRY(lzx_ensure_degrees(c));
+    }
     // this call overwrites the work vectors a prepared decomposition keeps its start vector in: the preparation is void
     for (lzx_ctx *c : cs) c->k_prep = 0;
     for (lzx_ctx *c : cs) {
@@ -1086,6 +1110,7 @@ static int spmv_run(std::vector<lzx_ctx *> &cs, const double *x, double *y)
         if (multi) LZX_TRY(lzx_launch_relayout(c, c->d_ybuf, c->d_xbuf));
         SpmvLaunch l{multi ? c->d_xbuf : c->d_ybuf, c->d_ybuf + (size_t)c->rank * c->n_loc_pad, c->d_v, c->d_partials};
         LZX_TRY(lzx_launch_spmv(c, l));
+        if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, l.q_loc, nullptr, 0, c->n_loc_pad));
     }
     if (multi) {
         for (size_t i = 0; i < cs.size(); ++i) { src[i] = cs[i]->d_v; dst[i] = cs[i]->d_ybuf; }

@@ -44,6 +44,7 @@ int lzx_graph_release(lzx_ctx *c)
 
     dev_free(c->d_row_ptr);
     dev_free(c->d_col_idx);
+    dev_free(c->d_deg);
     dev_free(c->d_shard_deg);
     c->shard = lzx_ctx::lzx_key_source();
     c->sharded = false;

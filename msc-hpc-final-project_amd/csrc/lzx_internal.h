@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -310,6 +311,11 @@ struct lzx_ctx {
     // norm one left-to-right accumulator in the caller's vertex order -- the reduction orders serial/ fixes (SPMV.cc:24-27,
     // lanczos.cc:155-171), so alpha / beta / Q meet the oracle's bit for bit at any k.  A parity instrument, not a fast path.
     int64_t ref_order_opt = -1;
+    // Option operator (include/lzx.h): LZX_OP_ADJACENCY (0) or LZX_OP_LAPLACIAN (1, L = D - A).  Under L every loop form
+    // applies v = fma(d, q, -v) after the SpMV (k_lap_apply) and stops at beta_j <= 2^-40 * 2 d_max.
+    int64_t op_opt = 0;
+    u32 *d_deg = nullptr;              // [ldq] stored entries of every local row in the rank's internal order (0 on padding): built on
+                                       // the first use of L, kept as long as the graph (lzx_graph_release)
     // Option placement_trials (blocked mode): at the end of a graph hand-over the value stream between the two passes is
     // allocated this many more times, the SpMV timed with each, the fastest kept -- where the driver puts that buffer
     // decides 15 % of the Erdos-Renyi SpMV and 1-2 % of the R-MAT one (lzx_pb.hip: lzx_pb_place_values).  -1: default (2), 0: off, at most 7.
@@ -412,8 +418,16 @@ int lzx_launch_axpy_norm(lzx_ctx *c, double *v, const double *qj, const double *
                          const double *partials_in, u32 np_in, double *alpha_out,
                          const double *beta_prev, double *partials_out, u32 *np_out);
 // q_next = v / sqrt(sum(partials_in)); writes beta_out.  in_is_sqrt: partials_in[0] already holds beta^2 summed.
+// stop >= 0 (operator L): a beta <= stop is written as 0 and q_next as zeros (the breakdown stop).
 int lzx_launch_scale(lzx_ctx *c, const double *v, double *q_next, const double *partials_in,
-                     u32 np_in, double *beta_out);
+                     u32 np_in, double *beta_out, double stop = -1.0);
+// operator L: the per-row degree array in the internal order (c->d_deg), built once per graph
+int lzx_ensure_degrees(lzx_ctx *c);
+// operator L: v = fma(d, q, -v) over rows [0, rows) (even); partials != nullptr: the np partials of v . q are replaced by
+// those of L q (same count, so whoever closed the SpMV's partials closes these)
+int lzx_launch_lap_apply(lzx_ctx *c, double *v, const double *q, double *partials, u32 np, u32 rows);
+// beta threshold of the breakdown stop under L: 2^-40 * 2 d_max (the Gershgorin bound of ||L||); -1 under A
+inline double lzx_stop_threshold(const lzx_ctx *c) { return c->op_opt == LZX_OP_LAPLACIAN ? ldexp(2.0 * (double)c->max_degree, -40) : -1.0; }
 int lzx_launch_permute_in(lzx_ctx *c, const double *io_old_order, double *full, double scale);
 int lzx_launch_fill(lzx_ctx *c, double *out, double value, u64 count);
 int lzx_launch_permute_out(lzx_ctx *c, const double *full, double *io_old_order, const double *div = nullptr);   // div: device scalar every entry is divided by

@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK)
 k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict__ u, const double *__restrict__ q_prev,
               const double *scal2, const double *pa, u32 na, const double *pb, u32 nb, int first, double *alpha_out,
               double *beta_out, double *q_out, double *u_next, double *partials_out, u32 n, double *iso, u32 iso_k, u32 iso_j,
-              const double *prev_div, float *f32_next, u32 mail_world, const LazyDeferred df)
+              const double *prev_div, float *f32_next, u32 mail_world, const LazyDeferred df, double stop)
 {
     __shared__ double sh[4];
     // df.limit > 0 (blocked SpMV whose k_pb_finish launch was skipped, round 5): row r of a multi-item band still lacks the
@@ -129,8 +129,11 @@ k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict
         B = first ? 1.0 : block_sum_fixed_256(pb, nb, sh);
     }
     if (first) B = 1.0;
-    const double beta = first ? 1.0 : sqrt(B);
-    const double alpha = first ? D : D / B;
+    // stop >= 0 (operator L): beta_{j-1} <= stop is the breakdown stop -- beta_{j-1}, alpha_j, q_j and u_{j+1} are 0, and so
+    // is everything after them (u = 0 multiplies to w = 0, and B = 0 stops again)
+    const bool zero = !first && sqrt(B) <= stop;
+    const double beta = first ? 1.0 : (zero ? 0.0 : sqrt(B));
+    const double alpha = zero ? 0.0 : (first ? D : D / B);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *alpha_out = alpha;
         if (beta_out) *beta_out = beta;
@@ -138,7 +141,7 @@ k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict
             // the rows without an edge (this launch covers [0, n) only): q_j = c_j q_0, u_j = d_j q_0 there, and the update
             // below with w = 0 is one scalar recurrence, rounded where the elementwise form rounds; their share of
             // ||u_{j+1}||^2 goes into one more partial
-            const double cj = first ? 1.0 : iso[iso_k + 1 + iso_j] / beta;
+            const double cj = first ? 1.0 : (zero ? 0.0 : iso[iso_k + 1 + iso_j] / beta);
             iso[iso_j] = cj;
             if (u_next) {
                 double t = 0.0;
@@ -159,6 +162,7 @@ k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict
             q.x /= beta;
             q.y /= beta;
         }
+        if (zero) q = make_double2(0.0, 0.0);
         if (q_out) *reinterpret_cast<double2 *>(q_out + i) = q;
         if (u_next) {
             // rows without an edge (the tail beyond w_rows) have (A u)_i = 0: not read, and the SpMV did not write them
@@ -171,6 +175,7 @@ k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict
                 t.x /= beta;
                 t.y /= beta;
             }
+            if (zero) t = make_double2(0.0, 0.0);
             t.x -= alpha * q.x;
             t.y -= alpha * q.y;
             if (q_prev) {
@@ -224,20 +229,63 @@ k_reduce2(const double *pa, u32 na, const double *pb, u32 nb, double *out2)
 }
 
 // serial/lib/lanczos.cc:39-44: beta_j = sqrt(sum v^2); q_{j+1} = v / beta_j (a true division).
+// stop >= 0 (operator L): beta <= stop is the breakdown stop -- beta_j = 0 and q_{j+1} = 0, after which every later alpha,
+// beta and column comes out 0 by itself (A 0 = 0, and the updates only subtract multiples of zeros).
 __global__ void __launch_bounds__(LZX_VEC_BLOCK)
 k_scale(const double *__restrict__ v, double *q_next, const double *partials_in, u32 np_in,
-        double *beta_out, u32 n)
+        double *beta_out, u32 n, double stop)
 {
     __shared__ double sh[4];
-    const double beta = sqrt(block_sum_fixed_256(partials_in, np_in, sh));
+    double beta = sqrt(block_sum_fixed_256(partials_in, np_in, sh));
+    const bool zero = beta <= stop;
+    if (zero) beta = 0.0;
     if (blockIdx.x == 0 && threadIdx.x == 0) *beta_out = beta;
     const u32 stride = gridDim.x * LZX_VEC_BLOCK * 2;
     for (u32 i = (blockIdx.x * LZX_VEC_BLOCK + threadIdx.x) * 2; i < n; i += stride) {
         double2 w = *reinterpret_cast<const double2 *>(v + i);
         w.x /= beta;
         w.y /= beta;
+        if (zero) w = make_double2(0.0, 0.0);
         *reinterpret_cast<double2 *>(q_next + i) = w;
     }
+}
+
+// Operator L = D - A after the SpMV: v = fma(d, q, -v) over rows [0, n) (the one rounding the CPU path's std::fma has too),
+// and the partials of v . q formed again on L q: block b writes partials[b], slots [gridDim.x, np) are set to 0, so every
+// consumer that closes the SpMV's np partials (the vector kernels, reduce / reduce2, the mailboxes, the peer-window reduce)
+// closes these instead.  partials == nullptr: v only.  n is even; d is 0 on rows without an edge and on the padding.
+__global__ void __launch_bounds__(LZX_VEC_BLOCK)
+k_lap_apply(double *v, const double *__restrict__ q, const u32 *__restrict__ deg, double *partials_out, u32 np, u32 n)
+{
+    if (partials_out)
+        for (u32 i = gridDim.x + blockIdx.x * LZX_VEC_BLOCK + threadIdx.x; i < np; i += gridDim.x * LZX_VEC_BLOCK) partials_out[i] = 0.0;
+    __shared__ double sh[4];
+    double dot = 0.0;
+    const u32 stride = gridDim.x * LZX_VEC_BLOCK * 2;
+    for (u32 i = (blockIdx.x * LZX_VEC_BLOCK + threadIdx.x) * 2; i < n; i += stride) {
+        double2 w = *reinterpret_cast<const double2 *>(v + i);
+        const double2 x = *reinterpret_cast<const double2 *>(q + i);
+        const uint2 d = *reinterpret_cast<const uint2 *>(deg + i);
+        w.x = fma((double)d.x, x.x, -w.x);
+        w.y = fma((double)d.y, x.y, -w.y);
+        *reinterpret_cast<double2 *>(v + i) = w;
+        dot += w.x * x.x;
+        dot += w.y * x.y;
+    }
+    dot = wave_sum(dot);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = dot;
+    __syncthreads();
+    if (threadIdx.x == 0 && partials_out) partials_out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// deg[l] = row_ptr[o + 1] - row_ptr[o] for the caller's vertices o this rank owns (gidx[o] = lo + l, l < n_loc_pad): the CSR
+// row lengths in the rank's internal row order
+__global__ void k_lap_degrees(const u64 *row_ptr, const u32 *gidx, u32 *deg, u64 n, u32 lo, u32 n_loc_pad)
+{
+    const u64 o = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= n) return;
+    const u32 g = gidx[o];
+    if (g >= lo && g - lo < n_loc_pad) deg[g - lo] = (u32)(row_ptr[o + 1] - row_ptr[o]);
 }
 
 // caller's order -> internal full-length layout (and back); div = ||x|| for the start vector.
@@ -697,7 +745,8 @@ int lzx_launch_lazy_update(lzx_ctx *c, const double *w, u32 w_rows, const double
     const u32 g = vec_grid(c);
     hipLaunchKernelGGL(k_lazy_update, dim3(g), dim3(LZX_VEC_BLOCK), 0, c->stream, w, w_rows, u, q_prev, scal2, nullptr, 0u, nullptr, 0u,
                        first, alpha_out, beta_out, q_out, u_next, partials_out, c->iso_on ? c->rows_live : c->n_loc_pad,
-                       c->iso_on ? c->d_iso : nullptr, c->iso_cap, (u32)(alpha_out - c->d_alpha), prev_div, f32_next, mail_world, lazy_deferred(c));
+                       c->iso_on ? c->d_iso : nullptr, c->iso_cap, (u32)(alpha_out - c->d_alpha), prev_div, f32_next, mail_world, lazy_deferred(c),
+                       lzx_stop_threshold(c));
     LZX_HIP(hipGetLastError());
     *np_out = g + (c->iso_on ? 1u : 0u);
     return LZX_OK;
@@ -710,7 +759,8 @@ int lzx_launch_lazy_update_local(lzx_ctx *c, const double *w, u32 w_rows, const 
     const u32 g = vec_grid(c);
     hipLaunchKernelGGL(k_lazy_update, dim3(g), dim3(LZX_VEC_BLOCK), 0, c->stream, w, w_rows, u, q_prev, nullptr, pa, na, pb, nb, first,
                        alpha_out, beta_out, q_out, u_next, partials_out, c->iso_on ? c->rows_live : c->n_loc_pad,
-                       c->iso_on ? c->d_iso : nullptr, c->iso_cap, (u32)(alpha_out - c->d_alpha), prev_div, f32_next, 0u, lazy_deferred(c));
+                       c->iso_on ? c->d_iso : nullptr, c->iso_cap, (u32)(alpha_out - c->d_alpha), prev_div, f32_next, 0u, lazy_deferred(c),
+                       lzx_stop_threshold(c));
     LZX_HIP(hipGetLastError());
     *np_out = g + (c->iso_on ? 1u : 0u);
     return LZX_OK;
@@ -758,10 +808,40 @@ int lzx_launch_axpy_norm(lzx_ctx *c, double *v, const double *qj, const double *
 }
 
 int lzx_launch_scale(lzx_ctx *c, const double *v, double *q_next, const double *partials_in,
-                     u32 np_in, double *beta_out)
+                     u32 np_in, double *beta_out, double stop)
 {
     hipLaunchKernelGGL(k_scale, dim3(vec_grid(c)), dim3(LZX_VEC_BLOCK), 0, c->stream, v, q_next,
-                       partials_in, np_in, beta_out, c->n_loc_pad);
+                       partials_in, np_in, beta_out, c->n_loc_pad, stop);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+int lzx_ensure_degrees(lzx_ctx *c)
+{
+    if (c->d_deg) return LZX_OK;
+    if (!c->d_row_ptr || !c->d_gidx_of_old)
+        LZX_FAIL(LZX_ERR_STATE, "operator laplacian needs the graph's row pointers on the handle (not with a sharded hand-over of a CSR in host memory)");
+    LZX_HIP(hipSetDevice(c->device));
+    u32 *d = nullptr;
+    LZX_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(u32) * c->ldq));
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(u32) * c->ldq, c->stream);
+    if (e == hipSuccess && c->n) {
+        hipLaunchKernelGGL(k_lap_degrees, dim3((u32)((c->n + 255) / 256)), dim3(256), 0, c->stream, c->d_row_ptr, c->d_gidx_of_old, d, c->n,
+                           (u32)c->rank * c->n_loc_pad, c->n_loc_pad);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        LZX_HIP(e);
+    }
+    c->d_deg = d;   // only once it is being filled
+    return LZX_OK;
+}
+
+int lzx_launch_lap_apply(lzx_ctx *c, double *v, const double *q, double *partials, u32 np, u32 rows)
+{
+    const u32 g = partials ? std::max(1u, std::min(vec_grid(c), np)) : vec_grid(c);
+    hipLaunchKernelGGL(k_lap_apply, dim3(g), dim3(LZX_VEC_BLOCK), 0, c->stream, v, q, c->d_deg, partials, np, rows);
     LZX_HIP(hipGetLastError());
     return LZX_OK;
 }

@@ -227,8 +227,11 @@ __device__ __forceinline__ void close_cols(const double *p, u32 np, double *shw 
 template <u32 B>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK)
 k_multi_alpha(double *V, const double *__restrict__ part, const u32 *__restrict__ split_row, const u32 *__restrict__ split_first,
-                const u32 *__restrict__ run_split, u32 n_split, const double *__restrict__ Q, double *pa, u64 n, u32 n_seg)
+                const u32 *__restrict__ run_split, u32 n_split, const double *__restrict__ Q, double *pa, u64 n, u32 n_seg,
+                const u64 *__restrict__ row_ptr, const double *__restrict__ X)
 {
+    // row_ptr != nullptr (operator L): V[r] = fma(d_r, X[r], -V[r]) once the row's total is complete -- the epilogue of the
+    // single-vector k_lap_apply, per column, so columns stay independent
     __shared__ double sh[LZX_MULTI_RUNS * B];
     for (u32 seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {
         for (u32 u = threadIdx.x; u < LZX_MULTI_RUNS * B; u += LZX_MULTI_BLOCK) {
@@ -239,7 +242,13 @@ k_multi_alpha(double *V, const double *__restrict__ part, const u32 *__restrict_
             u32 ks = r0 < n ? run_split[r0 / LZX_MULTI_RUN] : n_split;
             if (r0 < n && r1 == r0 + LZX_MULTI_RUN && (ks >= n_split || split_row[ks] >= r1)) {
                 // no split row in this run (nearly every run): eight rows' loads in flight, products added in row order
-                if (Q) {
+                if (row_ptr) {
+                    for (u64 r = r0; r < r1; ++r) {
+                        const double v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -V[r * B + c]);
+                        V[r * B + c] = v;
+                        if (Q) s += v * Q[r * B + c];
+                    }
+                } else if (Q) {
                     for (u64 r = r0; r < r1; r += 8) {
                         double v[8], q[8];
 #pragma unroll
@@ -254,10 +263,15 @@ k_multi_alpha(double *V, const double *__restrict__ part, const u32 *__restrict_
                     if (ks < n_split && split_row[ks] == r) {
                         v = 0.0;
                         for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) v += part[(u64)p * B + c];
+                        if (row_ptr) v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -v);
                         V[r * B + c] = v;
                         ++ks;
                     } else {
                         v = V[r * B + c];
+                        if (row_ptr) {
+                            v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -v);
+                            V[r * B + c] = v;
+                        }
                     }
                     if (Q) s += v * Q[r * B + c];
                 }
@@ -337,7 +351,7 @@ k_multi_update(double *V, const double *__restrict__ Qj, const double *__restric
 template <u32 B>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK)
 k_multi_scale(const double *__restrict__ V, const double *pn, u32 n_seg, const double *alpha, double *beta, double *mx, u32 k, u32 j,
-              double *Qn, u64 n)
+              double *Qn, u64 n, double lstop)
 {
     __shared__ double shw[4 * B], sq[B], sd[B];
     close_cols<B>(pn, n_seg, shw, sq);
@@ -346,7 +360,8 @@ k_multi_scale(const double *__restrict__ V, const double *pn, u32 n_seg, const d
         double bt = sqrt(sq[c]);
         const double bp = j > 0 ? beta[(u64)c * k + j - 1] : 0.0;
         const double m = fmax(j > 0 ? mx[(u64)(j - 1) * B + c] : 0.0, fabs(alpha[(u64)c * k + j]) + bp);
-        const bool stop = (j > 0 && bp == 0.0) || bt <= 0x1p-40 * m;
+        // lstop >= 0 (operator L): the single-vector rule, beta <= 2^-40 * 2 d_max
+        const bool stop = (j > 0 && bp == 0.0) || (lstop >= 0.0 ? bt <= lstop : bt <= 0x1p-40 * m);
         if (stop) bt = 0.0;
         sd[c] = bt;
         if (blockIdx.x == 0) {
@@ -524,9 +539,11 @@ static int launch_spmm(lzx_ctx *c, const double *X, double *Y, const double *Q)
     if (n_waves)
         hipLaunchKernelGGL(k_multi_spmm<B>, dim3((u32)((n_waves + 3) / 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_wl, n_waves,
                            c->d_col_idx, X, Y, m->d_part);
-    if (m->n_seg && (Q || m->n_split))
+    const bool lap = c->op_opt == LZX_OP_LAPLACIAN;
+    if (m->n_seg && (Q || m->n_split || lap))
         hipLaunchKernelGGL(k_multi_alpha<B>, dim3(std::min<u32>(m->n_seg, (u32)c->cu_count * 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, Y,
-                           m->d_part, m->d_split_row, m->d_split_first, m->d_run_split, m->n_split, Q, m->d_pa, c->n, m->n_seg);
+                           m->d_part, m->d_split_row, m->d_split_first, m->d_run_split, m->n_split, Q, m->d_pa, c->n, m->n_seg,
+                           lap ? c->d_row_ptr : nullptr, X);
     LZX_HIP(hipGetLastError());
     return LZX_OK;
 }
@@ -583,7 +600,7 @@ static int multi_loop(lzx_ctx *c, u32 b, const double *X0, u32 k, double *alpha,
                            j ? qj - nB : qj, m->d_pa, m->n_seg, m->d_alpha, m->d_beta, k, j, m->d_pn, n, last ? 1 : 0);
         if (!last)
             hipLaunchKernelGGL(k_multi_scale<B>, dim3(sgrid), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, m->d_pn, m->n_seg,
-                               m->d_alpha, m->d_beta, m->d_mx, k, j, qj + nB, n);
+                               m->d_alpha, m->d_beta, m->d_mx, k, j, qj + nB, n, lzx_stop_threshold(c));
         LZX_HIP(hipGetLastError());
         if (mark) LZX_HIP(hipEventRecord(e[2], c->stream));
     }

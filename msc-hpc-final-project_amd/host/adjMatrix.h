@@ -73,6 +73,7 @@ class adjMatrix {
   friend std::ostream &operator<<(std::ostream &, const adjMatrix &);
   template <typename T> friend void multOut(lanczosDecomp<T> &, eigenDecomp<T> &, adjMatrix &, bool);
   template <typename T> friend class lanczosDecomp;
+  friend class lanczosDecompMulti;   // the CPU path's row lengths under operator L
 
  private:
   unsigned *row_offset = nullptr;  // [n + 1]

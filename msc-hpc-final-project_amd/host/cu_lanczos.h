@@ -69,12 +69,20 @@ struct lanczosTimings {
 //                  norm one left-to-right accumulator: serial/lib/SPMV.cc:24-27, lanczos.cc:155-171), so that
 //                  lanczosDecomp(A, k, x, true, {reference_order}) and lanczosDecomp(A, k, x, false) hold the same alpha, beta
 //                  and Q BIT FOR BIT -- a parity instrument (slow), one GPU handle only.
+//   op             the operator M of f(M) x: the adjacency matrix A (default), or the combinatorial Laplacian L = D - A
+//                  (d_i = stored entries of row i), applied as (L x)_i = fma(d_i, x_i, -(A x)_i) on the CPU and the device
+//                  alike.  Under L a beta_j <= 2^-40 * 2 d_max stops the recurrence: beta_j and everything after it are 0
+//                  (include/lzx.h, option "operator").
+//   time           t of the answer: multOut and its kin form e^{tA} x, or e^{-tL} x (the heat kernel) under L.
+enum class graphOperator { adjacency = 0, laplacian = 1 };
 struct lanczosOptions {
   unsigned arnoldi_every = 0;
   unsigned adaptive_step = 0;
   double adaptive_tol = 1e-10;
   bool basis_fp32 = false;
   bool reference_order = false;
+  graphOperator op = graphOperator::adjacency;
+  double time = 1.0;
 };
 
 struct convergenceReport {
@@ -114,6 +122,10 @@ class lanczosDecomp {
   // adaptive_step > 0: what the chunked run evaluated; iterations (= SpMVs) it actually ran
   const convergenceReport &convergence() const { return adaptive; }
   unsigned iterations_run() const { return iters_run; }
+  // e^{s theta} is what the answer takes of a Ritz value theta: s = time under A, s = -time under L
+  double exponent_scale() const { return opts.op == graphOperator::laplacian ? -opts.time : opts.time; }
+  // the leading block of T the answer uses: up to the first zero beta under L (the breakdown stop), all of it under A
+  unsigned effective_krylov() const;
   // Post-hoc orthonormalisation of the stored basis, the role of serial/lib/lanczos.cc:202-207 (LAPACKE_dgeqrf + dorgqr):
   // Q <- the orthonormal factor of Q = Q'R, here by two modified Gram-Schmidt sweeps (R's diagonal positive; LAPACK's
   // Householder form may flip the sign of a column).  A device decomposition brings its basis to the host first.
@@ -138,6 +150,7 @@ class lanczosDecomp {
   lanczosOptions opts;
   convergenceReport adaptive;
   unsigned iters_run = 0;
+  double stop_thr = -1.0;              // under L: 2^-40 * 2 d_max, the breakdown threshold of beta_j (< 0: no stop)
   bool on_device_layout = false;       // Q (once on the host) holds k contiguous vectors rather than row-major n x k
   bool basis_lost = false;             // the resident basis was overwritten and could not be brought to the host
   std::shared_ptr<deviceGraph> graph;  // device path: the adjMatrix's graph on the GPU(s); the basis is resident there
@@ -149,5 +162,7 @@ class lanczosDecomp {
 
   void decompose();     // CPU:    serial/lib/lanczos.cc:9-56 == parallel-final/lib/lanczos.cu:17-60
   void decompose_with_arnoldi(unsigned every);   // CPU: serial/lib/lanczos.cc:58-132
+  void apply_operator(const T *q, T *v) const;   // v = L q given v = A q (no-op under A)
+  bool breakdown(T &beta_j) const;   // under L: beta_j <= 2^-40 * 2 d_max becomes exactly 0 (true: q_{j+1} = 0)
   void cu_decompose();  // MI355X: replaces parallel-final/lib/cu_lanczos.cu:20-142
 };

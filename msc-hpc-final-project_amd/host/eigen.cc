@@ -92,12 +92,18 @@ eigenDecomp<T>::~eigenDecomp() {
 template <typename T>
 void eigenDecomp<T>::decompose() {
   const int k = static_cast<int>(L.krylov_dim);
-  std::vector<double> d(eigenvalues, eigenvalues + k), e(k > 1 ? k - 1 : 1, 0.0), z(static_cast<std::size_t>(k) * k);
-  for (int i = 0; i + 1 < k; ++i) e[i] = L.beta[i];
-  if (symtridiag_ql(k, d.data(), e.data(), z.data()) != 0)
+  // under L, T is trimmed at the first zero beta (the breakdown stop): the leading kb x kb block is decomposed; the rows and
+  // columns behind it (alpha = beta = 0, basis columns 0) keep eigenvalue 0 and the unit eigenvector, which the answer
+  // weighs by V[0][j] = 0
+  const int kb = static_cast<int>(L.effective_krylov());
+  std::vector<double> d(eigenvalues, eigenvalues + kb), e(kb > 1 ? kb - 1 : 1, 0.0), z(static_cast<std::size_t>(kb) * kb);
+  for (int i = 0; i + 1 < kb; ++i) e[i] = L.beta[i];
+  if (symtridiag_ql(kb, d.data(), e.data(), z.data()) != 0)
     throw std::runtime_error("eigenDecomp: QL iteration did not converge");
-  for (int i = 0; i < k; ++i) eigenvalues[i] = static_cast<T>(d[i]);
-  for (std::size_t i = 0; i < z.size(); ++i) eigenvectors[i] = static_cast<T>(z[i]);
+  for (int i = 0; i < k; ++i) eigenvalues[i] = i < kb ? static_cast<T>(d[i]) : T(0);
+  for (int i = 0; i < k; ++i)
+    for (int j = 0; j < k; ++j)
+      eigenvectors[static_cast<std::size_t>(i) * k + j] = (i < kb && j < kb) ? static_cast<T>(z[static_cast<std::size_t>(i) * kb + j]) : T(i == j ? 1 : 0);
 }
 
 template class eigenDecomp<double>;

@@ -152,6 +152,45 @@ long host_expm_options_file(const char *path, unsigned k, int cuda, int device_m
   }
 }
 
+// The operator option of lanczosOptions on a graph file: op 0 = A (e^{tA} x), 1 = L = D - A (e^{-tL} x), x0 (NULL: ones),
+// cuda 0 = the CPU class path, 1 = the device path (reference_order != 0: with the CPU path's reduction orders).  Outputs:
+// ans[n], alpha[k], beta[k-1], Q[k][n] (vector after vector, either path; NULL: not wanted).  Returns n, or < 0.
+long host_expm_operator_file(const char *path, unsigned k, int cuda, int device_multout, int op, double time, unsigned arnoldi_every,
+                             int reference_order, const double *x0, double *ans, unsigned ans_len, double *alpha, double *beta, double *Q) {
+  try {
+    std::ifstream fs(path);
+    if (fs.fail()) { g_host_err = std::string("cannot open ") + path; return -1; }
+    unsigned n = 0, edges = 0;
+    fs >> n >> n >> edges;
+    adjMatrix A(n, edges, fs);
+    if (ans_len < n) { g_host_err = "answer buffer too small"; return -2; }
+    std::vector<double> x(n, 1.0);
+    if (x0) std::copy(x0, x0 + n, x.begin());
+    lanczosOptions o;
+    o.op = op ? graphOperator::laplacian : graphOperator::adjacency;
+    o.time = time;
+    o.arnoldi_every = arnoldi_every;
+    o.reference_order = reference_order != 0;
+    lanczosDecomp<double> L(A, k, x.data(), cuda != 0, o);
+    if (alpha) std::copy(L.get_alpha(), L.get_alpha() + k, alpha);
+    if (beta && k > 1) std::copy(L.get_beta(), L.get_beta() + (k - 1), beta);
+    if (Q) {
+      const double *B = L.basis();   // device path: k contiguous vectors; CPU path: row-major n x k
+      for (unsigned j = 0; j < k; ++j)
+        for (unsigned i = 0; i < n; ++i)
+          Q[static_cast<std::size_t>(j) * n + i] = cuda ? B[static_cast<std::size_t>(j) * n + i] : B[static_cast<std::size_t>(i) * k + j];
+    }
+    eigenDecomp<double> E(L);
+    if (cuda && device_multout) cu_multOut(L, E, A, true);
+    else multOut(L, E, A, cuda != 0);
+    std::copy(L.answer(), L.answer() + n, ans);
+    return static_cast<long>(n);
+  } catch (const std::exception &e) {
+    g_host_err = e.what();
+    return -3;
+  }
+}
+
 // Drop-in parity, literally: the same graph file through lanczosDecomp(A, k, x, /*cuda*/false) and through
 // lanczosDecomp(A, k, x, /*cuda*/true, {reference_order}); returns 1 when alpha, beta and every entry of Q are bit-identical,
 // 0 when they are not (first difference in diff[0..2]: 0 alpha / 1 beta / 2 Q, index, -), < 0 on error.
@@ -208,6 +247,30 @@ long host_expm_multi_file(const char *path, unsigned k, unsigned b, const double
     if (beta) std::copy(L.get_beta(), L.get_beta() + bk, beta);
     if (k_used) std::copy(L.k_used(), L.k_used() + b, k_used);
     if (x_norm) std::copy(L.x_norms(), L.x_norms() + b, x_norm);
+    return static_cast<long>(n);
+  } catch (const std::exception &e) {
+    g_host_err = e.what();
+    return -3;
+  }
+}
+
+// host_expm_multi_file with the operator: op 0 = A (e^{tA} x_c), 1 = L = D - A (e^{-tL} x_c).
+long host_expm_multi_operator_file(const char *path, unsigned k, unsigned b, const double *X, int cuda, int op, double time, double *ans,
+                                   unsigned ans_len, double *alpha, double *beta, unsigned *k_used) {
+  try {
+    std::ifstream fs(path);
+    if (fs.fail()) { g_host_err = std::string("cannot open ") + path; return -1; }
+    unsigned n = 0, edges = 0;
+    fs >> n >> n >> edges;
+    adjMatrix A(n, edges, fs);
+    if (ans_len < static_cast<std::size_t>(n) * b) { g_host_err = "answer buffer too small"; return -2; }
+    lanczosDecompMulti L(A, k, X, b, cuda != 0, op ? graphOperator::laplacian : graphOperator::adjacency, time);
+    multOutMulti(L, A);
+    const std::size_t bk = static_cast<std::size_t>(b) * k;
+    std::copy(L.answer(), L.answer() + static_cast<std::size_t>(n) * b, ans);
+    if (alpha) std::copy(L.get_alpha(), L.get_alpha() + bk, alpha);
+    if (beta) std::copy(L.get_beta(), L.get_beta() + bk, beta);
+    if (k_used) std::copy(L.k_used(), L.k_used() + b, k_used);
     return static_cast<long>(n);
   } catch (const std::exception &e) {
     g_host_err = e.what();

@@ -1,6 +1,7 @@
 // lanczos.cc -- CPU and device paths of lanczosDecomp<T> (see cu_lanczos.h).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <iomanip>
 #include <iostream>
 #include <stdexcept>
@@ -25,6 +26,11 @@ lanczosDecomp<T>::lanczosDecomp(adjMatrix &adj, const unsigned krylov, T *starti
   if (!cuda) Q = new T[n * krylov];   // the device path keeps the basis in HBM (ensure_host_basis)
   x = new T[n];
   ans = new T[n];
+  if (opts.op == graphOperator::laplacian) {
+    unsigned dmax = 0;
+    for (std::size_t r = 0; r < n; ++r) dmax = std::max(dmax, A.row_offset[r + 1] - A.row_offset[r]);
+    stop_thr = std::ldexp(2.0 * dmax, -40);
+  }
   x_norm = norm(starting_vec, A.get_n());
   std::copy(starting_vec, starting_vec + n, x);
   on_device_layout = cuda;
@@ -53,6 +59,29 @@ void lanczosDecomp<T>::free_mem() {
   }
 }
 
+// Under L: v = d .* q - v, one explicit fma per row (the device applies the same form, so reference_order stays bit-identical).
+template <typename T>
+void lanczosDecomp<T>::apply_operator(const T *q, T *v) const {
+  if (opts.op != graphOperator::laplacian) return;
+  const unsigned n = A.get_n();
+  for (unsigned r = 0; r < n; ++r) v[r] = std::fma(static_cast<T>(A.row_offset[r + 1] - A.row_offset[r]), q[r], -v[r]);
+}
+
+template <typename T>
+bool lanczosDecomp<T>::breakdown(T &beta_j) const {
+  if (!(stop_thr >= 0.0) || !(static_cast<double>(beta_j) <= stop_thr)) return false;
+  beta_j = 0;
+  return true;
+}
+
+template <typename T>
+unsigned lanczosDecomp<T>::effective_krylov() const {
+  if (opts.op != graphOperator::laplacian) return krylov_dim;
+  for (unsigned j = 0; j + 1 < krylov_dim; ++j)
+    if (beta[j] == 0) return j + 1;
+  return krylov_dim;
+}
+
 // The three-term recurrence with two ping-pong vectors; q_j is copied into column j of the row-major
 // basis at the end of step j.
 template <typename T>
@@ -64,6 +93,7 @@ void lanczosDecomp<T>::decompose() {
 
   for (unsigned j = 0; j < k; ++j) {
     spMV(A, cur.data(), v.data());
+    apply_operator(cur.data(), v.data());
     alpha[j] = inner_prod(v.data(), cur.data(), n);
     for (unsigned r = 0; r < n; ++r) v[r] -= alpha[j] * cur[r];
     if (j > 0)
@@ -71,7 +101,9 @@ void lanczosDecomp<T>::decompose() {
     for (unsigned r = 0; r < n; ++r) Q[j + static_cast<std::size_t>(r) * k] = cur[r];
     if (j + 1 < k) {
       beta[j] = norm(v.data(), n);
-      for (unsigned r = 0; r < n; ++r) prev[r] = v[r] / beta[j];
+      if (breakdown(beta[j])) std::fill(prev.begin(), prev.end(), T(0));   // the Krylov space is exhausted: q_{j+1} = 0
+      else
+        for (unsigned r = 0; r < n; ++r) prev[r] = v[r] / beta[j];
       cur.swap(prev);  // cur = q_{j+1}, prev = q_j
     }
   }
@@ -88,6 +120,7 @@ void lanczosDecomp<T>::decompose_with_arnoldi(unsigned every) {
 
   for (unsigned j = 0; j < k; ++j) {
     spMV(A, cur.data(), v.data());
+    apply_operator(cur.data(), v.data());
     if (j % every == 0 && j > 2) {
       for (unsigned m = 0; m + 1 < j; ++m) {
         const T *qm = kept.data() + static_cast<std::size_t>(m) * n;
@@ -103,7 +136,9 @@ void lanczosDecomp<T>::decompose_with_arnoldi(unsigned every) {
     std::copy(cur.begin(), cur.end(), kept.begin() + static_cast<std::size_t>(j) * n);
     if (j + 1 < k) {
       beta[j] = norm(v.data(), n);
-      for (unsigned r = 0; r < n; ++r) prev[r] = v[r] / beta[j];
+      if (breakdown(beta[j])) std::fill(prev.begin(), prev.end(), T(0));   // the Krylov space is exhausted: q_{j+1} = 0
+      else
+        for (unsigned r = 0; r < n; ++r) prev[r] = v[r] / beta[j];
       cur.swap(prev);
     }
   }
@@ -143,6 +178,8 @@ void lanczosDecomp<T>::cu_decompose() {
     lzx_or_throw(lzx_set_option(hs[p], "reorthogonalise", opts.arnoldi_every), "lzx_set_option(reorthogonalise)");
     lzx_or_throw(lzx_set_option(hs[p], "basis_fp32", opts.basis_fp32 ? 1 : 0), "lzx_set_option(basis_fp32)");
     lzx_or_throw(lzx_set_option(hs[p], "reference_order", opts.reference_order ? 1 : 0), "lzx_set_option(reference_order)");
+    lzx_or_throw(lzx_set_option(hs[p], "operator", opts.op == graphOperator::laplacian ? LZX_OP_LAPLACIAN : LZX_OP_ADJACENCY),
+                 "lzx_set_option(operator)");
   }
   lzx_stats st{};
   auto run = [&](const double *x0, double *a, double *b) {
@@ -169,17 +206,23 @@ void lanczosDecomp<T>::cu_decompose() {
       st.spmv_bytes = s1.spmv_bytes;
       if (world == 1) lzx_or_throw(lzx_lanczos_fetch_f64(hs[0], done, a, b, nullptr), "lzx_lanczos_fetch_f64");
       else lzx_or_throw(lzx_lanczos_fetch_f64_local(hs, world, done, a, b, nullptr), "lzx_lanczos_fetch_f64_local");
-      d.assign(a, a + done);
-      e.assign(done, 0.0);
-      for (unsigned i = 0; i + 1 < done; ++i) e[i] = b[i];
-      z.assign(static_cast<std::size_t>(done) * done, 0.0);
-      if (symtridiag_ql(static_cast<int>(done), d.data(), e.data(), z.data()) != 0)
+      // under L the block of T ends at the first zero beta (the breakdown stop); the columns behind it are 0
+      unsigned kb = done;
+      if (opts.op == graphOperator::laplacian)
+        for (unsigned i = 0; i + 1 < done; ++i)
+          if (b[i] == 0) { kb = i + 1; break; }
+      d.assign(a, a + kb);
+      e.assign(kb, 0.0);
+      for (unsigned i = 0; i + 1 < kb; ++i) e[i] = b[i];
+      z.assign(static_cast<std::size_t>(kb) * kb, 0.0);
+      if (symtridiag_ql(static_cast<int>(kb), d.data(), e.data(), z.data()) != 0)
         throw std::runtime_error("lanczosDecomp: QL iteration did not converge");
       t.assign(done, 0.0);
-      for (unsigned j = 0; j < done; ++j) d[j] = std::exp(d[j]) * (xn * z[j]);
-      for (unsigned i = 0; i < done; ++i) {
+      const double s = exponent_scale();
+      for (unsigned j = 0; j < kb; ++j) d[j] = std::exp(d[j] * s) * (xn * z[j]);
+      for (unsigned i = 0; i < kb; ++i) {
         double acc = 0;
-        for (unsigned j = 0; j < done; ++j) acc += z[static_cast<std::size_t>(i) * done + j] * d[j];
+        for (unsigned j = 0; j < kb; ++j) acc += z[static_cast<std::size_t>(i) * kb + j] * d[j];
         t[i] = acc;
       }
       double change = 1.0;

@@ -18,7 +18,11 @@ void lzx_or_throw(int rc, const char *what) {
 }  // namespace
 
 lanczosDecompMulti::lanczosDecompMulti(adjMatrix &adj, unsigned krylov, const double *Xin, unsigned nb, bool on_gpu)
-    : A{adj}, krylov_dim{krylov}, b{nb}, cuda{on_gpu} {
+    : lanczosDecompMulti(adj, krylov, Xin, nb, on_gpu, graphOperator::adjacency, 1.0) {}
+
+lanczosDecompMulti::lanczosDecompMulti(adjMatrix &adj, unsigned krylov, const double *Xin, unsigned nb, bool on_gpu, graphOperator o,
+                                       double t)
+    : A{adj}, krylov_dim{krylov}, b{nb}, cuda{on_gpu}, op{o}, time{t} {
   if (krylov == 0) throw std::invalid_argument("lanczosDecompMulti: krylov dimension must be positive");
   if (nb == 0) throw std::invalid_argument("lanczosDecompMulti: no starting vectors");
   const std::size_t n = A.get_n(), k = krylov;
@@ -62,8 +66,17 @@ void lanczosDecompMulti::decompose_column(unsigned c) {
   for (unsigned r = 0; r < n; ++r) cur[r] = x[r] / xnorm;
   double mx = 0.0;
   kused[c] = k;
+  const bool lap = op == graphOperator::laplacian;
+  double lstop = 0.0;   // under L: 2^-40 * 2 d_max (lanczos.cc: breakdown)
+  if (lap) {
+    unsigned dmax = 0;
+    for (unsigned r = 0; r < n; ++r) dmax = std::max(dmax, A.row_offset[r + 1] - A.row_offset[r]);
+    lstop = std::ldexp(2.0 * dmax, -40);
+  }
   for (unsigned j = 0; j < k; ++j) {
     spMV(A, cur.data(), v.data());
+    if (lap)
+      for (unsigned r = 0; r < n; ++r) v[r] = std::fma(static_cast<double>(A.row_offset[r + 1] - A.row_offset[r]), cur[r], -v[r]);
     a[j] = inner_prod(v.data(), cur.data(), n);
     for (unsigned r = 0; r < n; ++r) v[r] -= a[j] * cur[r];
     if (j > 0)
@@ -72,7 +85,7 @@ void lanczosDecompMulti::decompose_column(unsigned c) {
     if (j + 1 < k) {
       const double nb = norm(v.data(), n);
       mx = std::max(mx, std::abs(a[j]) + (j > 0 ? bt[j - 1] : 0.0));
-      if (nb <= 0x1p-40 * mx) {
+      if (lap ? nb <= lstop : nb <= 0x1p-40 * mx) {
         kused[c] = j + 1;
         return;
       }
@@ -87,6 +100,8 @@ void lanczosDecompMulti::run_batch(unsigned first) {
   const std::size_t n = A.get_n(), k = krylov_dim;
   const unsigned cnt = std::min(batch, b - first);
   lzx_stats st{};
+  lzx_or_throw(lzx_set_option(graph->ranks[0], "operator", op == graphOperator::laplacian ? LZX_OP_LAPLACIAN : LZX_OP_ADJACENCY),
+               "lzx_set_option(operator)");
   lzx_or_throw(lzx_lanczos_multi_f64(graph->ranks[0], cnt, X.data() + first * n, krylov_dim, alpha.data() + first * k,
                                      beta.data() + first * k, kused.data() + first, xn.data() + first, nullptr, &st),
                "lzx_lanczos_multi_f64");
@@ -101,14 +116,16 @@ void lanczosDecompMulti::answer_batch(unsigned first) {
   std::vector<double> T(cnt * k, 0.0), d, e, z;
   for (unsigned i = 0; i < cnt; ++i) {
     const unsigned c = first + i, ku = kused[c];
-    // t = V (e^lambda .* ||x|| V[0,:]) of the leading k_used x k_used block (multiplyOut.cc: small_part)
+    // t = V (e^{s lambda} .* ||x|| V[0,:]) of the leading k_used x k_used block (multiplyOut.cc: small_part); s = time under A
+    // (1: e^lambda bit for bit), -time under L
     d.assign(alpha.begin() + c * k, alpha.begin() + c * k + ku);
     e.assign(ku, 0.0);
     for (unsigned j = 0; j + 1 < ku; ++j) e[j] = beta[c * k + j];
     z.assign(static_cast<std::size_t>(ku) * ku, 0.0);
     if (symtridiag_ql(static_cast<int>(ku), d.data(), e.data(), z.data()) != 0)
       throw std::runtime_error("lanczosDecompMulti: QL iteration did not converge");
-    for (unsigned j = 0; j < ku; ++j) d[j] = std::exp(d[j]) * (xn[c] * z[j]);
+    const double es = op == graphOperator::laplacian ? -time : time;
+    for (unsigned j = 0; j < ku; ++j) d[j] = std::exp(d[j] * es) * (xn[c] * z[j]);
     double *t = T.data() + i * k;
     for (unsigned r = 0; r < ku; ++r) {
       double s = 0;

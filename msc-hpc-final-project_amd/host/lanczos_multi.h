@@ -21,11 +21,15 @@
 #include <vector>
 
 #include "adjMatrix.h"
+#include "cu_lanczos.h"
 #include "device_graph.h"
 
 class lanczosDecompMulti {
  public:
   lanczosDecompMulti(adjMatrix &A, unsigned krylov, const double *X, unsigned b, bool cuda);
+  // op / time as in lanczosOptions: the Krylov spaces of L = D - A (with its stop rule, beta <= 2^-40 * 2 d_max) and answers
+  // e^{-tL} x_c, or e^{tA} x_c
+  lanczosDecompMulti(adjMatrix &A, unsigned krylov, const double *X, unsigned b, bool cuda, graphOperator op, double time);
   lanczosDecompMulti(const lanczosDecompMulti &) = delete;
   lanczosDecompMulti &operator=(const lanczosDecompMulti &) = delete;
   ~lanczosDecompMulti();
@@ -46,6 +50,8 @@ class lanczosDecompMulti {
   adjMatrix &A;
   unsigned krylov_dim, b;
   bool cuda;
+  graphOperator op = graphOperator::adjacency;
+  double time = 1.0;
   std::vector<double> X, alpha, beta, xn, ans, Q;   // Q: CPU path, [b][k][n]
   std::vector<unsigned> kused;
   std::vector<char> answered;

@@ -12,6 +12,8 @@
 // Environment: FINAL_ADAPTIVE_STEP=S [FINAL_ADAPTIVE_TOL=t, default 1e-10]: the device run advances in chunks of S iterations and
 // stops once the answer moved by less than t (K is then the upper limit; k_used is printed); FINAL_ARNOLDI=E: both runs
 // re-orthogonalise every E iterations (serial/lib/lanczos.cc:58-132; the reference's constant is 2);
+// FINAL_OPERATOR=laplacian: both runs use L = D - A and print the heat kernel e^{-tL} x (default adjacency: e^{tA} x), with
+// FINAL_TIME=t (default 1);
 // FINAL_SKIP_SERIAL=1 skips the CPU run (large graphs), FINAL_DEVICE_MULTOUT=1 uses the
 // on-device back-projection (parallel-mult-on-card's cu_multOut) for the GPU column; LZX_DEVICES=all | N | a,b,c
 // spreads the device run over several GPUs from this one process (parallel-two-cards' model, any number of cards);
@@ -103,6 +105,15 @@ int main(int argc, char **argv) {
   if (const char *v = std::getenv("FINAL_ARNOLDI")) host_opt.arnoldi_every = dev_opt.arnoldi_every = static_cast<unsigned>(std::atoi(v));
   if (const char *v = std::getenv("FINAL_ADAPTIVE_STEP")) dev_opt.adaptive_step = static_cast<unsigned>(std::atoi(v));
   if (const char *v = std::getenv("FINAL_ADAPTIVE_TOL")) dev_opt.adaptive_tol = std::atof(v);
+  if (const char *v = std::getenv("FINAL_OPERATOR")) {
+    const std::string op(v);
+    if (op == "laplacian") host_opt.op = dev_opt.op = graphOperator::laplacian;
+    else if (op != "adjacency") {
+      std::cerr << "FINAL_OPERATOR must be adjacency or laplacian, got '" << op << "'\n";
+      return 1;
+    }
+  }
+  if (const char *v = std::getenv("FINAL_TIME")) host_opt.time = dev_opt.time = std::atof(v);
   dev_opt.reference_order = env_on("FINAL_REFERENCE_ORDER");   // the device run with the CPU run's reduction orders: identical alpha / beta / Q
 
   // ---- CPU ----

@@ -9,11 +9,12 @@
 #include "lzx.h"
 
 namespace {
-// t = V (e^lambda .* ||x|| V[0,:])  -- multiplyOut.cu:30-40 of the reference: exponentiate the Ritz
-// values in place, weight by the first eigenvector components, one k x k GEMV.
+// t = V (e^{s lambda} .* ||x|| V[0,:])  -- multiplyOut.cu:30-40 of the reference: exponentiate the Ritz
+// values in place, weight by the first eigenvector components, one k x k GEMV.  s = time under A (1: the reference's
+// e^lambda, bit for bit), -time under L.
 template <typename T>
-std::vector<T> small_part(T *lambda, const T *V, unsigned k, T x_norm) {
-  for (unsigned j = 0; j < k; ++j) lambda[j] = std::exp(lambda[j]);
+std::vector<T> small_part(T *lambda, const T *V, unsigned k, T x_norm, double s) {
+  for (unsigned j = 0; j < k; ++j) lambda[j] = std::exp(lambda[j] * static_cast<T>(s));
   for (unsigned j = 0; j < k; ++j) lambda[j] *= x_norm * V[j];
   std::vector<T> t(k);
   for (unsigned i = 0; i < k; ++i) {
@@ -29,7 +30,7 @@ template <typename T>
 void multOut(lanczosDecomp<T> &L, eigenDecomp<T> &E, adjMatrix &, bool Qtrans) {
   const std::size_t n = L.get_n();
   const unsigned k = L.get_krylov();
-  const std::vector<T> t = small_part(E.eigenvalues, E.eigenvectors, k, L.x_norm);
+  const std::vector<T> t = small_part(E.eigenvalues, E.eigenvectors, k, L.x_norm, L.exponent_scale());
   if (Qtrans) {
     L.ensure_host_basis();   // a device decomposition downloads its basis here, on first use
     // ans = sum_j t_j q_j over contiguous vectors: stream each vector once
@@ -54,7 +55,7 @@ template <typename T>
 void cu_multOut(lanczosDecomp<T> &L, eigenDecomp<T> &E, adjMatrix &, bool) {
   if (!L.on_device()) throw std::logic_error("cu_multOut: the decomposition has no device-resident basis");
   const unsigned k = L.get_krylov();
-  const std::vector<T> t = small_part(E.eigenvalues, E.eigenvectors, k, L.x_norm);
+  const std::vector<T> t = small_part(E.eigenvalues, E.eigenvectors, k, L.x_norm, L.exponent_scale());
   std::vector<double> td(t.begin(), t.end()), out(L.get_n());
   L.device_multout(td.data(), k, out.data());
   for (std::size_t i = 0; i < out.size(); ++i) L.ans[i] = static_cast<T>(out[i]);
@@ -67,19 +68,22 @@ convergenceReport multOutAdaptive(lanczosDecomp<T> &L, adjMatrix &, unsigned ste
   if (step == 0) step = 5;
   convergenceReport rep;
   std::vector<double> prev, cur(n), d, e, z, t;
+  const double es = L.exponent_scale();
+  const unsigned Kb = L.effective_krylov();   // under L: T ends at the first zero beta (the columns behind it are 0)
   for (unsigned k = std::min(step, K);; k = std::min(k + step, K)) {
-    // leading k x k block of T: eigen-decomposition, then t = V (e^lambda .* ||x|| V[0,:])
-    d.assign(L.alpha, L.alpha + k);
-    e.assign(k, 0.0);
-    for (unsigned i = 0; i + 1 < k; ++i) e[i] = L.beta[i];
-    z.assign(static_cast<std::size_t>(k) * k, 0.0);
-    if (symtridiag_ql(static_cast<int>(k), d.data(), e.data(), z.data()) != 0)
+    // leading k x k block of T: eigen-decomposition, then t = V (e^{s lambda} .* ||x|| V[0,:])
+    const unsigned kb = std::min(k, Kb);
+    d.assign(L.alpha, L.alpha + kb);
+    e.assign(kb, 0.0);
+    for (unsigned i = 0; i + 1 < kb; ++i) e[i] = L.beta[i];
+    z.assign(static_cast<std::size_t>(kb) * kb, 0.0);
+    if (symtridiag_ql(static_cast<int>(kb), d.data(), e.data(), z.data()) != 0)
       throw std::runtime_error("multOutAdaptive: QL iteration did not converge");
     t.assign(k, 0.0);
-    for (unsigned j = 0; j < k; ++j) d[j] = std::exp(d[j]) * (static_cast<double>(L.x_norm) * z[j]);
-    for (unsigned i = 0; i < k; ++i) {
+    for (unsigned j = 0; j < kb; ++j) d[j] = std::exp(d[j] * es) * (static_cast<double>(L.x_norm) * z[j]);
+    for (unsigned i = 0; i < kb; ++i) {
       double s = 0;
-      for (unsigned j = 0; j < k; ++j) s += z[static_cast<std::size_t>(i) * k + j] * d[j];
+      for (unsigned j = 0; j < kb; ++j) s += z[static_cast<std::size_t>(i) * kb + j] * d[j];
       t[i] = s;
     }
     // y_k = Q_k t
