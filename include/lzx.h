@@ -251,6 +251,40 @@ int lzx_spmm_f64(lzx_handle h, uint32_t b, const double *X, double *Y);
 /* Give back the batch basis and work vectors (they are also freed by a new graph and by lzx_destroy). */
 int lzx_multi_release(lzx_handle h);
 
+/* ---- stochastic Lanczos quadrature on the batched path (one GPU) ---------------------------------
+ * Random +-1 probe vectors z_p for estimates of tr f(M) and diag f(M) (M = A, or L under the option "operator"): the
+ * batched recurrence above started from probes generated on the device, optionally without a basis.
+ * Probe p (0 <= p < 2^32) at vertex i (caller order, 0 <= i < n), all arithmetic mod 2^64:
+ *     key = seed + 0x9E3779B97F4A7C15 * ((p << 32) + i + 1)
+ *     h = key; h ^= h >> 30; h *= 0xBF58476D1CE4E5B9; h ^= h >> 27; h *= 0x94D049BB133111EB; h ^= h >> 31
+ *     z_p[i] = (h >> 63) ? -1.0 : +1.0
+ * It depends on neither the internal vertex order nor how the probes are split into batches.
+ * Errors of all three, as for the batched entries: LZX_ERR_ARG for a null handle or pointer, b == 0, k == 0 or
+ * first + b > 2^32; LZX_ERR_LIMIT for b > 16; LZX_ERR_STATE for a handle with a communicator or without a graph.
+ *
+ * lzx_probes_f64: Z[b][n] = probes first .. first + b - 1.  Leaves the resident batch basis alone.
+ *
+ * lzx_lanczos_probes_f64: lzx_lanczos_multi_f64 with X0 = lzx_probes_f64(seed, first, b): alpha, beta, k_used ([b][k], [b])
+ * bit-identical to it, flags or not; the implied x_norm is sqrt(n) (the exact norm of a +-1 vector).  q_0 = z_p / sqrt(n)
+ * is written on the device (no host upload).
+ *   flags = 0: basis-free.  q_{j-1}, q_j, q_{j+1} rotate through three [n][B] slots, so the batch state is about
+ *     4 * n * B * 8 bytes (slots and one work vector) plus the work list, whatever k is; any resident batch basis is given
+ *     back first and none is resident afterwards (lzx_multout_multi_f64 / lzx_probe_diag_f64: LZX_ERR_STATE).
+ *   flags = LZX_PROBE_KEEP_BASIS: the [k][n][B] basis is kept as the resident batch basis, for lzx_multout_multi_f64
+ *     and lzx_probe_diag_f64.  LZX_ERR_NOMEM when it does not fit: the message states the bytes and no batch state is
+ *     left behind.
+ * stats as for lzx_lanczos_multi_f64 (spmv_bytes keeps its formula).  Any other flag bit: LZX_ERR_ARG.
+ *
+ * lzx_probe_diag_f64: out[n] = sum over the resident probe batch's columns c, ascending, of z_c .* (Q_c t_c), where
+ * Q_c t_c is exactly lzx_multout_multi_f64's answer for T ([b][k], b the batch's, k at most its k; entries >= k_used[c]
+ * ignored) and z_c is probe c (multiplied exactly: +-1).  Only the n-vector leaves the device.  LZX_ERR_STATE unless the
+ * resident basis is a kept probe basis (after a basis-free run, or a basis of lzx_lanczos_multi_f64's caller vectors). */
+#define LZX_PROBE_KEEP_BASIS 1
+int lzx_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t b, double *Z);
+int lzx_lanczos_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t b, uint32_t k, uint32_t flags,
+                           double *alpha, double *beta, uint32_t *k_used, lzx_stats *stats);
+int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, double *out);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -106,6 +106,10 @@ SYMBOLS = [
     ("lzx_multout_multi_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, _f64p]),
     ("lzx_spmm_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, _f64p]),
     ("lzx_multi_release", ctypes.c_int, [_h]),
+    ("lzx_probes_f64", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, _f64p]),
+    ("lzx_lanczos_probes_f64", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              _f64p, _f64p, _u32p, ctypes.POINTER(LzxStats)]),
+    ("lzx_probe_diag_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p]),
 ]
 
 _LIB = None
@@ -177,6 +181,66 @@ def _expm_coefficients(alpha, beta, x_norm, s):
     t = np.zeros(k)
     t[:kb] = V @ (np.exp(s * lam) * (x_norm * V[0, :]))
     return t
+
+
+# ---- stochastic Lanczos quadrature (include/lzx.h: lzx_lanczos_probes_f64) ----
+PROBE_KEEP_BASIS = 1   # LZX_PROBE_KEEP_BASIS
+PROBE_BATCH = 16       # probes per batched decomposition
+
+
+def _probe_ritz(alpha, beta, m):
+    """Eigenpairs (theta, V) of one probe's tridiagonal T trimmed to its m = k_used coefficients."""
+    T = np.diag(np.asarray(alpha[:m], dtype=np.float64))
+    if m > 1:
+        T += np.diag(beta[:m - 1], 1) + np.diag(beta[:m - 1], -1)
+    return np.linalg.eigh(T)
+
+
+def _logsumexp(x):
+    m = x.max()
+    return m + np.log(np.sum(np.exp(x - m)))
+
+
+def slq_log_quadratures(alpha, beta, k_used, n, s):
+    """ell[i, p] = log(z_p^T e^{s_i M} z_p) by the Gauss quadrature of probe p's T (alpha, beta: (P, k); k_used: (P,)):
+    log n + logsumexp_j(log w_j + s_i theta_j), w_j = V[0, j]^2 > 0 -- finite where e^{s theta} itself overflows.  Each
+    (s_i, p) is computed on its own, so a grid of s gives the bits of one s at a time."""
+    s = np.atleast_1d(np.asarray(s, dtype=np.float64))
+    alpha, beta = np.atleast_2d(alpha), np.atleast_2d(beta)
+    ell = np.empty((len(s), alpha.shape[0]))
+    for p in range(alpha.shape[0]):
+        theta, V = _probe_ritz(alpha[p], beta[p], int(k_used[p]))
+        w = V[0, :] ** 2
+        keep = w > 0.0
+        logw, theta = np.log(w[keep]), theta[keep]
+        for i, si in enumerate(s):
+            ell[i, p] = np.log(float(n)) + _logsumexp(logw + si * theta)
+    return ell
+
+
+def slq_trace(ell):
+    """From ell (S, N) of slq_log_quadratures: (log_trace[S], rel_stderr[S]) with log_trace = logsumexp_p ell_p - log N, the
+    log of the Hutchinson mean, and rel_stderr = std(e^{ell - max ell}, ddof=1) / (sqrt(N) mean(e^{ell - max ell}))."""
+    ell = np.atleast_2d(ell)
+    N = ell.shape[1]
+    log_trace, rel = np.empty(ell.shape[0]), np.empty(ell.shape[0])
+    for i, e in enumerate(ell):
+        log_trace[i] = _logsumexp(e) - np.log(float(N))
+        r = np.exp(e - e.max())
+        rel[i] = np.std(r, ddof=1) / (np.sqrt(N) * np.mean(r)) if N > 1 else np.nan
+    return log_trace, rel
+
+
+def slq_diag_coefficients(alpha, beta, k_used, n, s, shift):
+    """T[p] = V (e^{s (theta - shift)} .* sqrt(n) V[0, :]) of probe p's trimmed T, zeros behind k_used[p]: the weights with
+    which Q_p T[p] = e^{s (M - shift I)} z_p (||z_p|| = sqrt(n)), for lzx_probe_diag_f64."""
+    alpha, beta = np.atleast_2d(alpha), np.atleast_2d(beta)
+    T = np.zeros(alpha.shape)
+    for p in range(alpha.shape[0]):
+        m = int(k_used[p])
+        theta, V = _probe_ritz(alpha[p], beta[p], m)
+        T[p, :m] = V @ (np.exp(s * (theta - shift)) * (np.sqrt(float(n)) * V[0, :]))
+    return T
 
 
 def rmat_thresholds(a=0.57, b=0.19, c=0.19):
@@ -426,6 +490,77 @@ class Engine:
 
     def multi_release(self):
         _check(self.L.lzx_multi_release(self.h), "lzx_multi_release", self.L)
+
+    # ---- stochastic Lanczos quadrature: tr and diag of e^{tA} / e^{-tL} from +-1 probes made on the device ----
+    def probes(self, seed: int, first: int, b: int):
+        """Z[b, n]: probes first .. first + b - 1 of seed (the hash of include/lzx.h, caller's vertex order)."""
+        Z = np.empty((b, self.n))
+        _check(self.L.lzx_probes_f64(self.h, seed, first, b, _p(Z, _f64p)), "lzx_probes_f64", self.L)
+        return Z
+
+    def lanczos_probes(self, seed: int, first: int, b: int, k: int, keep_basis: bool = False):
+        """lanczos_multi(probes(seed, first, b), k) without the upload, basis-free unless keep_basis (then the basis is the
+        resident batch basis, for probe_diag and multout_multi).  Returns (alpha[b,k], beta[b,k], k_used[b], stats dict);
+        every x_norm is sqrt(n)."""
+        alpha, beta = np.zeros((b, k)), np.zeros((b, k))
+        k_used = np.zeros(b, dtype=np.uint32)
+        st = LzxStats()
+        _check(self.L.lzx_lanczos_probes_f64(self.h, seed, first, b, k, PROBE_KEEP_BASIS if keep_basis else 0, _p(alpha, _f64p),
+                                            _p(beta, _f64p), _p(k_used, _u32p), ctypes.byref(st)), "lzx_lanczos_probes_f64", self.L)
+        return alpha, beta, k_used, st.as_dict()
+
+    def probe_diag(self, T):
+        """out[n] = sum over the resident probe batch's columns c (ascending) of z_c .* (Q_c T[c]) (T: (b, k))."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 2:
+            raise ValueError(f"probe_diag: T must be a (b, k) array, got shape {T.shape}")
+        out = np.empty(self.n)
+        _check(self.L.lzx_probe_diag_f64(self.h, _p(T, _f64p), T.shape[1], _p(out, _f64p)), "lzx_probe_diag_f64", self.L)
+        return out
+
+    def _probe_scale(self, t):
+        return -t if self.operator == OP_LAPLACIAN else t
+
+    def trace_expm(self, t, n_probes: int = 64, k: int = 50, seed: int = 0):
+        """Stochastic Lanczos quadrature of tr e^{tA} (or the heat trace tr e^{-tL}) for a scalar t or a 1-D array of t, from
+        one basis-free pass over n_probes probes in batches of 16.  Returns (log_trace, rel_stderr, ell): the log of the
+        estimate, its relative standard error, and the per-probe log quadratures ell_p (shape (N,) for a scalar t, (len(t), N)
+        otherwise).  The Estrada index is exp(log_trace) at t = 1; natural connectivity is log_trace - log n."""
+        ts = np.asarray(t, dtype=np.float64)
+        if ts.ndim > 1:
+            raise ValueError(f"trace_expm: t must be a scalar or a 1-D array, got shape {ts.shape}")
+        if n_probes < 1:
+            raise ValueError("trace_expm: n_probes must be at least 1")
+        s = self._probe_scale(np.atleast_1d(ts))
+        ell = []
+        for first in range(0, n_probes, PROBE_BATCH):
+            b = min(PROBE_BATCH, n_probes - first)
+            alpha, beta, k_used, _ = self.lanczos_probes(seed, first, b, k)
+            ell.append(slq_log_quadratures(alpha, beta, k_used, self.n, s))
+        ell = np.concatenate(ell, axis=1)
+        log_trace, rel = slq_trace(ell)
+        if ts.ndim == 0:
+            return log_trace[0], rel[0], ell[0]
+        return log_trace, rel, ell
+
+    def diag_expm(self, t: float = 1.0, n_probes: int = 64, k: int = 50, seed: int = 0, shift=None):
+        """Estimate of diag e^{s (M - shift I)} (s = t under A, -t under L): (1/N) sum_p z_p .* (e^{s (M - shift I)} z_p), each
+        batch of 16 probes run with its basis kept and reduced on the device (probe_diag), the batch vectors added in batch
+        order.  shift defaults to the largest Ritz value of the first batch under A (subgraph centrality without overflow) and
+        to 0 under L.  Returns (estimate[n], shift); diag e^{sM} = estimate * e^{s shift}.  The last batch's basis stays resident."""
+        if n_probes < 1:
+            raise ValueError("diag_expm: n_probes must be at least 1")
+        s = self._probe_scale(float(t))
+        acc = None
+        for first in range(0, n_probes, PROBE_BATCH):
+            b = min(PROBE_BATCH, n_probes - first)
+            alpha, beta, k_used, _ = self.lanczos_probes(seed, first, b, k, keep_basis=True)
+            if shift is None:
+                shift = 0.0 if self.operator == OP_LAPLACIAN else \
+                    max(float(_probe_ritz(alpha[p], beta[p], int(k_used[p]))[0].max()) for p in range(b))
+            d = self.probe_diag(slq_diag_coefficients(alpha, beta, k_used, self.n, s, shift))
+            acc = d if acc is None else acc + d
+        return acc / n_probes, float(shift)
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

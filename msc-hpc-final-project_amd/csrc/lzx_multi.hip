@@ -1,5 +1,6 @@
 // lzx_multi.hip -- batched, independent Lanczos: b <= 16 separate three-term recurrences (one per column of X) that share
-// one SpMM per iteration (include/lzx.h: lzx_lanczos_multi_f64, lzx_multout_multi_f64, lzx_spmm_f64, lzx_multi_release).
+// one SpMM per iteration (include/lzx.h: lzx_lanczos_multi_f64, lzx_multout_multi_f64, lzx_spmm_f64, lzx_multi_release), and
+// the stochastic-trace entries built on it (lzx_probes_f64, lzx_lanczos_probes_f64, lzx_probe_diag_f64).
 //
 // Not block Lanczos: no QR of a block, no coupling between columns.  Each column runs serial/lib/lanczos.cc:9-56 (the
 // arithmetic of lzx_lanczos_f64) plus a breakdown stop of its own.
@@ -29,6 +30,11 @@
 //   beta_{c,j} <= 2^-40 * max_{i <= j} (|alpha_{c,i}| + beta_{c,i-1}),   beta_{c,-1} = 0.
 // Its beta_j is then stored as 0 and its later basis vectors are zero, so its later alpha / beta come out 0; "stopped before
 // iteration j" is read from beta_{c,j-1} == 0, which every workgroup of a later launch sees complete -- no flag round trip.
+//
+// Probes (lzx_lanczos_probes_f64).  q_0 is written on the device by k_multi_probe from a counter hash of (seed, probe, vertex)
+// -- no host upload.  Basis-free ("ring") runs keep q_{j-1}, q_j, q_{j+1} in three rotating [n][B] slots instead of the
+// [k][n][B] basis: the same four launches on other pointers, so alpha / beta / k_used are those of the kept-basis run.  On a
+// kept probe basis k_multi_diag forms sum_c z_c (Q_c t_c) per row, so one vector of n leaves the device per batch.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -64,7 +70,9 @@ struct lzx_multi_state {
     // batch basis
     u32 B = 0, b = 0, k = 0;
     bool resident = false;             // a decomposition's basis is there
-    double *d_Q = nullptr;             // [k][n][B]
+    bool ring = false;                 // d_Q is three rotating slots (basis-free run), not a basis
+    bool probe = false;                // the resident basis was started from probes (lzx_probe_diag_f64 works on it)
+    double *d_Q = nullptr;             // [k][n][B], or [3][n][B] when ring
     double *d_alpha = nullptr, *d_beta = nullptr, *d_T = nullptr;   // [B][k]
     double *d_mx = nullptr;            // [k][B] running max of |alpha_i| + beta_{i-1}
     u32 *d_kused = nullptr;            // [B]
@@ -104,7 +112,7 @@ static void free_basis(lzx_multi_state *m)
 {
     mfree(m->d_Q); mfree(m->d_alpha); mfree(m->d_beta); mfree(m->d_T); mfree(m->d_mx); mfree(m->d_kused);
     m->B = m->b = m->k = 0;
-    m->resident = false;
+    m->resident = m->ring = m->probe = false;
     m->h_kused.clear();
 }
 
@@ -144,6 +152,29 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_unpack(const double *
     if (i >= n * B) return;
     const u32 c = (u32)(i % B);
     if (c < b) out[(u64)c * n + i / B] = in[i];
+}
+
+// Probe p's value at vertex i (caller order): the sign bit of the splitmix64 finaliser of
+// seed + golden * ((p << 32) + i + 1), all mod 2^64 (include/lzx.h, lzx_probes_f64).
+__host__ __device__ __forceinline__ double probe_value(u64 seed, u64 p, u64 i)
+{
+    u64 h = seed + 0x9E3779B97F4A7C15ull * ((p << 32) + i + 1);
+    h ^= h >> 30;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 27;
+    h *= 0x94D049BB133111EBull;
+    h ^= h >> 31;
+    return (h >> 63) ? -1.0 : 1.0;
+}
+
+// out [n][B]: column c < b is probe first + c divided by div (sqrt(n) for a start vector, 1 for lzx_probes_f64); padded columns 0
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_probe(u64 seed, u64 first, u32 b, u64 n, double div, double *out)
+{
+    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (i >= n * B) return;
+    const u32 c = (u32)(i % B);
+    out[i] = c < b ? probe_value(seed, first + c, i / B) / div : 0.0;
 }
 
 template <u32 B>
@@ -377,18 +408,53 @@ k_multi_scale(const double *__restrict__ V, const double *pn, u32 n_seg, const d
     }
 }
 
-// out[r][c] = sum over j < min(k, k_used[c]) of T[c][j] q_{j,c}[r], j ascending
+// (Q_c t_c)[r] at i = r * B + c: sum over j < min(k, k_used[c]) of T[c][j] q_{j,c}[r], j ascending.  The one expression
+// k_multi_multout and k_multi_diag share, so the diagonal's y_c is the answer's bit for bit.
+template <u32 B>
+__device__ __forceinline__ double multout_entry(const double *__restrict__ Q, u32 k, u64 n, const double *__restrict__ T,
+                                                const u32 *__restrict__ kused, u64 i)
+{
+    const u32 c = (u32)(i % B);
+    const u32 kc = std::min(k, kused[c]);
+    double acc = 0.0;
+    for (u32 j = 0; j < kc; ++j) acc += T[(u64)c * k + j] * Q[(u64)j * n * B + i];
+    return acc;
+}
+
+// out[r][c] = (Q_c t_c)[r]
 template <u32 B>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK)
 k_multi_multout(const double *__restrict__ Q, u32 k, u64 n, const double *__restrict__ T, const u32 *__restrict__ kused, double *out)
 {
     const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
     if (i >= n * B) return;
-    const u32 c = (u32)(i % B);
-    const u32 kc = std::min(k, kused[c]);
-    double acc = 0.0;
-    for (u32 j = 0; j < kc; ++j) acc += T[(u64)c * k + j] * Q[(u64)j * n * B + i];
-    out[i] = acc;
+    out[i] = multout_entry<B>(Q, k, n, T, kused, i);
+}
+
+// out[r] = sum over c < b, ascending, of z_c[r] (Q_c t_c)[r] on a probe basis.  z_c[r] = the sign of q_{0,c}[r] (= z / sqrt(n),
+// never 0), so the product is exact.  A workgroup holds 256 / B whole rows: the (row, column) products are staged in LDS and
+// the row's column-0 thread adds them in column order.
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_multi_diag(const double *__restrict__ Q, u32 k, u64 n, u32 b, const double *__restrict__ T, const u32 *__restrict__ kused, double *out)
+{
+    static_assert(LZX_MULTI_BLOCK % B == 0, "rows do not straddle workgroups");
+    __shared__ double sh[LZX_MULTI_BLOCK];
+    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    const u32 c = threadIdx.x % B;
+    const bool in = i < n * B;
+    double p = 0.0;
+    if (in && c < b) {
+        const double y = multout_entry<B>(Q, k, n, T, kused, i);
+        p = Q[i] > 0.0 ? y : -y;
+    }
+    sh[threadIdx.x] = p;
+    __syncthreads();
+    if (in && c == 0) {
+        double s = 0.0;
+        for (u32 cc = 0; cc < b; ++cc) s += sh[threadIdx.x + cc];
+        out[i / B] = s;
+    }
 }
 
 // ==================================================================================================== host side
@@ -483,50 +549,58 @@ static int build_tables(lzx_ctx *c)
     return LZX_OK;
 }
 
-static int ensure_work(lzx_ctx *c, u32 B)
+// the work vectors of width B; need_x: the second one too (packing, unpacking -- a probe run starts on the device without it)
+static int ensure_work(lzx_ctx *c, u32 B, bool need_x = true)
 {
     lzx_multi_state *m = c->multi;
-    if (m->wB == B && m->d_V) return LZX_OK;
-    free_work(m);
     const u64 n = c->n;
     int rc;
-    if ((rc = malloc_n(&m->d_V, n * B, "work vector")) || (rc = malloc_n(&m->d_X, n * B, "work vector")) ||
-        (rc = malloc_n(&m->d_part, (u64)m->n_parts * B, "chunk totals")) || (rc = malloc_n(&m->d_pa, (u64)m->n_seg * B, "partials")) ||
-        (rc = malloc_n(&m->d_pn, (u64)m->n_seg * B, "partials"))) {
+    if (m->wB != B || !m->d_V) {
+        free_work(m);
+        if ((rc = malloc_n(&m->d_V, n * B, "work vector")) || (rc = malloc_n(&m->d_part, (u64)m->n_parts * B, "chunk totals")) ||
+            (rc = malloc_n(&m->d_pa, (u64)m->n_seg * B, "partials")) || (rc = malloc_n(&m->d_pn, (u64)m->n_seg * B, "partials"))) {
+            free_work(m);
+            return rc;
+        }
+        m->wB = B;
+    }
+    if (need_x && !m->d_X && (rc = malloc_n(&m->d_X, n * B, "work vector"))) {
         free_work(m);
         return rc;
     }
-    m->wB = B;
     return LZX_OK;
 }
 
-static int ensure_basis(lzx_ctx *c, u32 k, u32 B)
+// The batch basis of k vectors, or (ring) three rotating slots; any other basis is given back first.
+static int ensure_basis(lzx_ctx *c, u32 k, u32 B, bool ring, const char *fn)
 {
     lzx_multi_state *m = c->multi;
-    m->resident = false;
-    if (m->d_Q && m->k == k && m->B == B) return LZX_OK;
+    m->resident = m->probe = false;
+    if (m->d_Q && m->k == k && m->B == B && m->ring == ring) return LZX_OK;
     free_basis(m);
-    const u64 bytes = (u64)k * c->n * B * sizeof(double);
+    const u32 slots = ring ? 3 : k;
+    const u64 bytes = (u64)slots * c->n * B * sizeof(double);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > (u64)total_b) {
         free_work(m);
-        LZX_FAIL(LZX_ERR_NOMEM, "lzx_lanczos_multi_f64: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8), the device has %llu",
-                 (unsigned long long)bytes, k, (unsigned long long)c->n, B, (unsigned long long)total_b);
+        LZX_FAIL(LZX_ERR_NOMEM, "%s: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8), the device has %llu", fn,
+                 (unsigned long long)bytes, slots, (unsigned long long)c->n, B, (unsigned long long)total_b);
     }
     (void)hipGetLastError();
     int rc;
-    if ((rc = malloc_n(&m->d_Q, (u64)k * c->n * B, "batch basis")) || (rc = malloc_n(&m->d_alpha, (u64)B * k, "coefficients")) ||
+    if ((rc = malloc_n(&m->d_Q, (u64)slots * c->n * B, "batch basis")) || (rc = malloc_n(&m->d_alpha, (u64)B * k, "coefficients")) ||
         (rc = malloc_n(&m->d_beta, (u64)B * k, "coefficients")) || (rc = malloc_n(&m->d_T, (u64)B * k, "coefficients")) ||
         (rc = malloc_n(&m->d_mx, (u64)k * B, "coefficients")) || (rc = malloc_n(&m->d_kused, B, "coefficients"))) {
         free_basis(m);
         free_work(m);
         if (rc == LZX_ERR_NOMEM)
-            lzx_set_error("lzx_lanczos_multi_f64: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8) and does not fit",
-                          (unsigned long long)bytes, k, (unsigned long long)c->n, B);
+            lzx_set_error("%s: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8) and does not fit", fn,
+                          (unsigned long long)bytes, slots, (unsigned long long)c->n, B);
         return rc;
     }
     m->k = k;
     m->B = B;
+    m->ring = ring;
     return LZX_OK;
 }
 
@@ -548,33 +622,49 @@ static int launch_spmm(lzx_ctx *c, const double *X, double *Y, const double *Q)
     return LZX_OK;
 }
 
+// where the start vectors come from: the caller's X0, or probes first .. first + b - 1 of seed
+struct MultiStart {
+    const double *X0;
+    u64 seed, first;
+};
+
 template <u32 B>
-static int multi_loop(lzx_ctx *c, u32 b, const double *X0, u32 k, double *alpha, double *beta, uint32_t *k_used, double *x_norm,
-                      double *Q, lzx_stats *stats)
+static int multi_loop(lzx_ctx *c, u32 b, MultiStart start, bool ring, u32 k, double *alpha, double *beta, uint32_t *k_used,
+                      double *x_norm, double *Q, lzx_stats *stats, const char *fn)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n, nB = n * B;
+    const double *X0 = start.X0;
     // ||x_c||: left-to-right sum of squares, then sqrt (serial/lib/lanczos.cc:155-161), as lzx_lanczos_prepare_f64 forms it
     MultiDiv div{};
     for (u32 col = 0; col < 16; ++col) div.v[col] = 1.0;
-    for (u32 col = 0; col < b; ++col) {
+    for (u32 col = 0; X0 && col < b; ++col) {
         double s = 0.0;
         const double *x = X0 + (u64)col * n;
         for (u64 i = 0; i < n; ++i) s += x[i] * x[i];
         div.v[col] = std::sqrt(s);
         x_norm[col] = div.v[col];
     }
-    int rc = ensure_basis(c, k, B);
-    if (rc == LZX_OK) rc = ensure_work(c, B);
+    int rc = ensure_basis(c, k, B, ring, fn);
+    if (rc == LZX_OK) rc = ensure_work(c, B, X0 != nullptr);
     if (rc != LZX_OK) {   // nothing half-built is left behind
         free_basis(m);
         free_work(m);
         return rc;
     }
-    // x0 staged in the work vector as [b][n], packed into column 0 of the basis
-    LZX_HIP(hipMemcpyAsync(m->d_V, X0, sizeof(double) * b * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_multi_pack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, div, m->d_Q);
+    if (ring) mfree(m->d_X);   // the state is the three slots and V
+    if (X0) {
+        // x0 staged in the work vector as [b][n], packed into column 0 of the basis
+        LZX_HIP(hipMemcpyAsync(m->d_V, X0, sizeof(double) * b * n, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_multi_pack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, div, m->d_Q);
+    } else {
+        // a +-1 probe has the norm sqrt(n) exactly: the left-to-right sum of n ones
+        hipLaunchKernelGGL(k_multi_probe<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, start.seed, start.first, b, n,
+                           std::sqrt((double)n), m->d_Q);
+    }
     LZX_HIP(hipGetLastError());
+    // q_j: basis vector j, or slot j mod 3 of the ring (q_{j+1} overwrites q_{j-2}, which no launch of iteration j reads)
+    auto slot = [&](u32 j) { return m->d_Q + (u64)(ring ? j % 3 : j) * nB; };
 
     // timing marks: every 4th iteration (every one when k < 8); each mark is a barrier packet
     const u32 every = k < 8 ? 1 : 4;
@@ -591,16 +681,16 @@ static int multi_loop(lzx_ctx *c, u32 b, const double *X0, u32 k, double *alpha,
     for (u32 j = 0; j < k; ++j) {
         const bool mark = j % every == 0;
         hipEvent_t *e = m->ev.data() + 3 * (j / every);
-        double *qj = m->d_Q + (u64)j * nB;
+        double *qj = slot(j);
         if (mark) LZX_HIP(hipEventRecord(e[0], c->stream));
         LZX_TRY(launch_spmm<B>(c, qj, m->d_V, qj));
         if (mark) LZX_HIP(hipEventRecord(e[1], c->stream));
         const bool last = j + 1 == k;
         hipLaunchKernelGGL(k_multi_update<B>, dim3(last ? 1 : vgrid), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, qj,
-                           j ? qj - nB : qj, m->d_pa, m->n_seg, m->d_alpha, m->d_beta, k, j, m->d_pn, n, last ? 1 : 0);
+                           j ? slot(j - 1) : qj, m->d_pa, m->n_seg, m->d_alpha, m->d_beta, k, j, m->d_pn, n, last ? 1 : 0);
         if (!last)
             hipLaunchKernelGGL(k_multi_scale<B>, dim3(sgrid), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, m->d_pn, m->n_seg,
-                               m->d_alpha, m->d_beta, m->d_mx, k, j, qj + nB, n, lzx_stop_threshold(c));
+                               m->d_alpha, m->d_beta, m->d_mx, k, j, slot(j + 1), n, lzx_stop_threshold(c));
         LZX_HIP(hipGetLastError());
         if (mark) LZX_HIP(hipEventRecord(e[2], c->stream));
     }
@@ -634,7 +724,8 @@ static int multi_loop(lzx_ctx *c, u32 b, const double *X0, u32 k, double *alpha,
         LZX_HIP(hipStreamSynchronize(c->stream));
     }
     m->b = b;
-    m->resident = true;
+    m->resident = !ring;
+    m->probe = !ring && !X0;
     if (stats) {
         double spmm = 0, vec = 0, mn = 1e300;
         for (u32 q = 0; q < marked; ++q) {
@@ -678,20 +769,57 @@ static int spmm_run(lzx_ctx *c, u32 b, const double *X, double *Y)
     return LZX_OK;
 }
 
+// T [b][k] -> d_T [B][k], entries at or behind k_used[c] and padded columns 0
+static int upload_T(lzx_ctx *c, u32 B, u32 b, const double *T, u32 k)
+{
+    lzx_multi_state *m = c->multi;
+    std::vector<double> t((u64)B * k, 0.0);
+    for (u32 col = 0; col < b; ++col)
+        for (u32 j = 0; j < std::min(k, m->h_kused[col]); ++j) t[(u64)col * k + j] = T[(u64)col * k + j];
+    LZX_HIP(hipMemcpyAsync(m->d_T, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));   // t is freed on return
+    return LZX_OK;
+}
+
 template <u32 B>
 static int multout_run(lzx_ctx *c, u32 b, const double *T, u32 k, double *ans)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n, nB = n * B;
     LZX_TRY(ensure_work(c, B));
-    std::vector<double> t((u64)B * k, 0.0);
-    for (u32 col = 0; col < b; ++col)
-        for (u32 j = 0; j < std::min(k, m->h_kused[col]); ++j) t[(u64)col * k + j] = T[(u64)col * k + j];
-    LZX_HIP(hipMemcpyAsync(m->d_T, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
+    LZX_TRY(upload_T(c, B, b, T, k));
     hipLaunchKernelGGL(k_multi_multout<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q, k, n, m->d_T, m->d_kused, m->d_V);
     hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
     LZX_HIP(hipGetLastError());
     LZX_HIP(hipMemcpyAsync(ans, m->d_X, sizeof(double) * b * n, hipMemcpyDeviceToHost, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    return LZX_OK;
+}
+
+template <u32 B>
+static int diag_run(lzx_ctx *c, u32 b, const double *T, u32 k, double *out)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n = c->n;
+    LZX_TRY(ensure_work(c, B, false));
+    LZX_TRY(upload_T(c, B, b, T, k));
+    hipLaunchKernelGGL(k_multi_diag<B>, dim3(grid_of(n * B)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q, k, n, b, m->d_T, m->d_kused, m->d_V);
+    LZX_HIP(hipGetLastError());
+    LZX_HIP(hipMemcpyAsync(out, m->d_V, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    return LZX_OK;
+}
+
+template <u32 B>
+static int probes_run(lzx_ctx *c, u64 seed, u64 first, u32 b, double *Z)
+{
+    lzx_multi_state *m = c->multi;
+    const u64 n = c->n, nB = n * B;
+    LZX_TRY(ensure_work(c, B));
+    hipLaunchKernelGGL(k_multi_probe<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, seed, first, b, n, 1.0, m->d_V);
+    hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
+    LZX_HIP(hipGetLastError());
+    LZX_HIP(hipMemcpyAsync(Z, m->d_X, sizeof(double) * b * n, hipMemcpyDeviceToHost, c->stream));
     LZX_HIP(hipStreamSynchronize(c->stream));
     return LZX_OK;
 }
@@ -725,7 +853,7 @@ extern "C" int lzx_lanczos_multi_f64(lzx_handle h, uint32_t b, const double *X0,
     int rc = build_tables(h);
     if (rc) return rc;
     const u32 B = pad_width(b);
-    LZX_MULTI_DISPATCH(B, multi_loop, h, b, X0, k, alpha, beta, k_used, x_norm, Q, stats);
+    LZX_MULTI_DISPATCH(B, multi_loop, h, b, MultiStart{X0, 0, 0}, false, k, alpha, beta, k_used, x_norm, Q, stats, fn);
 }
 
 extern "C" int lzx_multout_multi_f64(lzx_handle h, uint32_t b, const double *T, uint32_t k, double *ans)
@@ -762,4 +890,53 @@ extern "C" int lzx_multi_release(lzx_handle h)
     if (!h) LZX_FAIL(LZX_ERR_ARG, "lzx_multi_release: null handle (h)");
     lzx_multi_free(h, false);
     return LZX_OK;
+}
+
+// ---- stochastic Lanczos quadrature: probes generated on the device
+static int check_probes(lzx_handle h, const char *fn, uint64_t first, uint32_t b)
+{
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    if (b == 0) LZX_FAIL(LZX_ERR_ARG, "%s: b == 0", fn);
+    if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
+    if (first > (1ull << 32) - b) LZX_FAIL(LZX_ERR_ARG, "%s: probes %llu + %u pass 2^32", fn, (unsigned long long)first, b);
+    return LZX_OK;
+}
+
+extern "C" int lzx_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t b, double *Z)
+{
+    static const char *fn = "lzx_probes_f64";
+    LZX_TRY(check_probes(h, fn, first, b));
+    if (!Z) LZX_FAIL(LZX_ERR_ARG, "%s: null Z", fn);
+    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(build_tables(h));
+    LZX_MULTI_DISPATCH(pad_width(b), probes_run, h, seed, first, b, Z);
+}
+
+extern "C" int lzx_lanczos_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t b, uint32_t k, uint32_t flags,
+                                      double *alpha, double *beta, uint32_t *k_used, lzx_stats *stats)
+{
+    static const char *fn = "lzx_lanczos_probes_f64";
+    LZX_TRY(check_probes(h, fn, first, b));
+    if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
+    if (!alpha || !beta || !k_used) LZX_FAIL(LZX_ERR_ARG, "%s: null alpha / beta / k_used", fn);
+    if (flags & ~(uint32_t)LZX_PROBE_KEEP_BASIS) LZX_FAIL(LZX_ERR_ARG, "%s: unknown flags 0x%x", fn, flags);
+    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(build_tables(h));
+    const bool ring = !(flags & LZX_PROBE_KEEP_BASIS);
+    LZX_MULTI_DISPATCH(pad_width(b), multi_loop, h, b, MultiStart{nullptr, seed, first}, ring, k, alpha, beta, k_used, nullptr, nullptr,
+                       stats, fn);
+}
+
+extern "C" int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, double *out)
+{
+    static const char *fn = "lzx_probe_diag_f64";
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    if (!T || !out) LZX_FAIL(LZX_ERR_ARG, "%s: null T / out", fn);
+    if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
+    LZX_TRY(check_handle(h, fn));
+    lzx_multi_state *m = h->multi;
+    if (!m->resident || !m->probe)
+        LZX_FAIL(LZX_ERR_STATE, "%s: no probe basis is resident (run lzx_lanczos_probes_f64 with LZX_PROBE_KEEP_BASIS)", fn);
+    if (k > m->k) LZX_FAIL(LZX_ERR_ARG, "%s: the resident probe basis has k = %u vectors (asked k = %u)", fn, m->k, k);
+    LZX_MULTI_DISPATCH(m->B, diag_run, h, m->b, T, k, out);
 }
