@@ -285,6 +285,48 @@ int lzx_lanczos_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t
                            double *alpha, double *beta, uint32_t *k_used, lzx_stats *stats);
 int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, double *out);
 
+/* ---- extreme eigenpairs: thick-restart Lanczos --------------------------------
+ * lzx_eigsh_f64: the nev algebraically largest (LZX_EIG_LARGEST) or smallest (LZX_EIG_SMALLEST) eigenpairs of the handle's
+ * operator M -- A, or L = D - A under option "operator" = LZX_OP_LAPLACIAN -- by thick-restart Lanczos (Wu-Simon, the
+ * symmetric Krylov-Schur) with full re-orthogonalisation (classical Gram-Schmidt twice) on the device.  One GPU handle only.
+ *   start     x0 [n] in caller order; NULL: probe 0 of `seed` as lzx_probes_f64 defines it, generated on the device.  The
+ *             start vector is orthogonalised against W.
+ *   deflation W [nw][n] (nw <= 8, caller order): every basis vector is kept orthogonal to span(W).  The library
+ *             orthonormalises W itself (on the device); a rank-deficient W is LZX_ERR_ARG.  Example: W = 1/sqrt(n) under L on
+ *             a connected graph makes lambda_2 the smallest wanted eigenvalue.
+ *   outputs   evals [nev]: descending for LARGEST, ascending for SMALLEST.  evecs [nev][n] (or NULL): unit vectors in caller
+ *             order, each signed so that its entry of largest magnitude (the first such on a tie) is positive.  resid [nev] (or
+ *             NULL): the true residual ||M v_i - theta_i v_i||_2, formed on the device with one more SpMV per pair.
+ *   converged pair i converges when |beta_m y_{m,i}| <= tol * norm_est, norm_est = the largest |Ritz value| seen (under L at
+ *             most 2 d_max).  If max_restarts runs out first, the best nev Ritz pairs are still written, info->converged <
+ *             nev, and the call returns LZX_ERR_LIMIT with a message stating the pairs converged and the largest residual
+ *             estimate.
+ *   limits    1 <= nev, nev + 2 <= m <= 128, m + nw <= n; m = 0 picks max(2 nev + 1, 20) clipped to those limits.
+ *             LZX_ERR_ARG: null handle, nev = 0, unknown `which`, tol <= 0, a size rule above.  LZX_ERR_LIMIT: m > 128, nw > 8.
+ *             LZX_ERR_STATE: a handle with a communicator, or no graph.  LZX_ERR_NOMEM: the basis, (nw + m + 1) * n_loc_pad * 8
+ *             bytes, does not fit (the message states the bytes; nothing of the eigensolver is left behind).
+ *   state     like lzx_spmv_f64 the call voids a prepared (chunked) single-vector decomposition: the next
+ *             lzx_lanczos_run_steps gets LZX_ERR_STATE.  The resident single-vector basis (lzx_multout_f64 on it) and the batch
+ *             state are left alone; the eigensolver's basis is freed before the call returns.
+ *   breakdown beta_j <= 2^-40 * g (g = d_max under A, 2 d_max under L) ends a cycle early: its Ritz pairs are exact, and the
+ *             next cycle starts from a fresh probe (seed, index 1 + earlier breakdowns) orthogonalised against the basis.
+ *   repeated  a single-vector Krylov method finds one vector per eigenspace from one start vector: further copies of a
+ *             repeated eigenvalue appear only through rounding or a breakdown restart.  W is the tool for getting them.
+ *   determinism: the same graph, options and arguments give bit-identical evals, evecs, resid and counts.
+ * info (or NULL): converged pairs, restarts, Lanczos matvecs (the residual SpMVs not counted), m used; loop_ms (host clock,
+ * whole call), spmv_ms and orth_ms (device event time of the SpMVs / of Gram-Schmidt + normalise + rotation launches),
+ * host_ms (dense eigenproblems and restart set-up), norm_est. */
+#define LZX_EIG_LARGEST  0   /* algebraically largest */
+#define LZX_EIG_SMALLEST 1   /* algebraically smallest */
+typedef struct lzx_eig_info {
+    uint32_t converged, restarts, matvecs, m;   /* m: the subspace size used */
+    double   loop_ms, spmv_ms, orth_ms, host_ms;
+    double   norm_est;                           /* the ||M|| estimate the tolerance is relative to */
+} lzx_eig_info;
+int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, double tol, uint32_t max_restarts,
+                  const double *x0, uint64_t seed, const double *W, uint32_t nw,
+                  double *evals, double *evecs, double *resid, lzx_eig_info *info);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -24,7 +24,7 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk")
+                 "multi_row_chunk", "eig_basis_bytes")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -58,6 +58,15 @@ class LzxGraphInfo(ctypes.Structure):
         d = {f: getattr(self, f) for f, _ in self._fields_}
         d["placement_us"] = list(d["placement_us"])[:d["placement_tried"]]
         return d
+
+
+class LzxEigInfo(ctypes.Structure):
+    _fields_ = [("converged", ctypes.c_uint32), ("restarts", ctypes.c_uint32), ("matvecs", ctypes.c_uint32), ("m", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("orth_ms", ctypes.c_double), ("host_ms", ctypes.c_double),
+                ("norm_est", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 # every symbol include/lzx.h declares: (name, restype, argtypes)
@@ -110,6 +119,8 @@ SYMBOLS = [
     ("lzx_lanczos_probes_f64", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                               _f64p, _f64p, _u32p, ctypes.POINTER(LzxStats)]),
     ("lzx_probe_diag_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p]),
+    ("lzx_eigsh_f64", ctypes.c_int, [_h, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, _f64p,
+                                     ctypes.c_uint64, _f64p, ctypes.c_uint32, _f64p, _f64p, _f64p, ctypes.POINTER(LzxEigInfo)]),
 ]
 
 _LIB = None
@@ -136,6 +147,8 @@ def _load(path: str, mode: int) -> ctypes.CDLL:
     L.lzx_test_allreduce_latency.argtypes = [_h, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
     L.lzx_test_rank_row_sums.restype = ctypes.c_int
     L.lzx_test_rank_row_sums.argtypes = [_h, _f64p, _u32p, _u64p]
+    L.lzx_test_sym_eig.restype = ctypes.c_int          # the eigensolver's dense solver (csrc/lzx_test_hooks.h)
+    L.lzx_test_sym_eig.argtypes = [ctypes.c_uint32, _f64p, _f64p, _f64p]
     return L
 
 
@@ -185,6 +198,9 @@ def _expm_coefficients(alpha, beta, x_norm, s):
 
 # ---- stochastic Lanczos quadrature (include/lzx.h: lzx_lanczos_probes_f64) ----
 PROBE_KEEP_BASIS = 1   # LZX_PROBE_KEEP_BASIS
+EIG_LARGEST = 0        # LZX_EIG_LARGEST
+EIG_SMALLEST = 1       # LZX_EIG_SMALLEST
+ERR_LIMIT = -6         # LZX_ERR_LIMIT
 PROBE_BATCH = 16       # probes per batched decomposition
 
 
@@ -561,6 +577,41 @@ class Engine:
             d = self.probe_diag(slq_diag_coefficients(alpha, beta, k_used, self.n, s, shift))
             acc = d if acc is None else acc + d
         return acc / n_probes, float(shift)
+
+    def eigsh(self, nev: int = 6, which: str = "LA", m: int = 0, tol: float = 1e-10, max_restarts: int = 300, x0=None, seed: int = 0,
+              deflate=None, want_vectors: bool = True):
+        """The nev algebraically largest ("LA") or smallest ("SA") eigenpairs of the handle's operator (A, or L under option
+        operator = OP_LAPLACIAN) by thick-restart Lanczos on the device (lzx_eigsh_f64), in the shape scipy.sparse.linalg.eigsh
+        returns: (w ascending, V (n, nev) with column i belonging to w[i], or None, info).  info: the lzx_eig_info fields plus
+        "resid" (the true residuals ||M v - w v||, ordered like w).  deflate: vectors (nw, n) or (n,) every basis vector is kept
+        orthogonal to.  Non-convergence within max_restarts raises LzxError with the partial (w, V, info) as `.partial`."""
+        if which not in ("LA", "SA"):
+            raise ValueError(f"which must be 'LA' or 'SA', not {which!r}")
+        n = self.n
+        x = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
+        if x is not None:
+            assert x.shape == (n,)
+        W = None if deflate is None else np.ascontiguousarray(np.atleast_2d(deflate), dtype=np.float64)
+        if W is not None:
+            assert W.shape[1] == n
+        nw = 0 if W is None else W.shape[0]
+        evals = np.zeros(nev)
+        evecs = np.zeros((nev, n)) if want_vectors else None
+        resid = np.zeros(nev)
+        info = LzxEigInfo()
+        rc = self.L.lzx_eigsh_f64(self.h, nev, EIG_LARGEST if which == "LA" else EIG_SMALLEST, m, tol, max_restarts,
+                                  None if x is None else _p(x, _f64p), seed, None if W is None else _p(W, _f64p), nw,
+                                  _p(evals, _f64p), None if evecs is None else _p(evecs, _f64p), _p(resid, _f64p), ctypes.byref(info))
+        o = slice(None, None, -1) if which == "LA" else slice(None)   # the library sorts wanted-most first; scipy ascending
+        d = info.as_dict()
+        d["resid"] = resid[o].copy()
+        result = (evals[o].copy(), None if evecs is None else evecs[o].T.copy(), d)
+        if rc == ERR_LIMIT and info.m > 0:   # (info is written only by a run that got as far as the restarts)
+            err = LzxError(f"lzx_eigsh_f64 failed ({rc}): {self.L.lzx_last_error().decode(errors='replace')}")
+            err.partial = result
+            raise err
+        _check(rc, "lzx_eigsh_f64", self.L)
+        return result
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

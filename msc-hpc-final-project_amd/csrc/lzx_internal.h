@@ -355,6 +355,7 @@ struct lzx_ctx {
     // batched independent Lanczos (lzx_multi.hip): its own work list, basis and work vectors, apart from everything above
     struct lzx_multi_state *multi = nullptr;
     int64_t multi_chunk_opt = -1;      // test shape multi_row_chunk: entries per chunk of a split row in the batched SpMM (-1: LZX_MULTI_CHUNK)
+    int64_t eig_basis_cap_opt = -1;    // test shape eig_basis_bytes: lzx_eigsh_f64 treats a basis larger than this as out of device memory
 };
 
 // ---- lzx_graph.hip ----
@@ -446,6 +447,19 @@ int lzx_launch_ref_spmv(lzx_ctx *c, const double *x, double *y);
 int lzx_launch_ref_dot(lzx_ctx *c, const double *a, const double *b, double *out);
 // column `col` of the fp32 basis, widened to fp64 into out[0..n_loc_pad)
 int lzx_launch_widen_col(lzx_ctx *c, u32 col, double *out);
+
+// Probe p's value at vertex i (caller order): the sign bit of the splitmix64 finaliser of seed + golden * ((p << 32) + i + 1),
+// all mod 2^64 (include/lzx.h, lzx_probes_f64); shared by the batched probes (lzx_multi.hip) and the eigensolver's start vectors
+__host__ __device__ __forceinline__ double lzx_probe_value(u64 seed, u64 p, u64 i)
+{
+    u64 h = seed + 0x9E3779B97F4A7C15ull * ((p << 32) + i + 1);
+    h ^= h >> 30;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 27;
+    h *= 0x94D049BB133111EBull;
+    h ^= h >> 31;
+    return (h >> 63) ? -1.0 : 1.0;
+}
 
 // ---- lzx_comm.hip ----
 // does the Lanczos loop exchange vectors / reduce scalars through the communicator?

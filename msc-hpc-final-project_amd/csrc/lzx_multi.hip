@@ -154,18 +154,6 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_unpack(const double *
     if (c < b) out[(u64)c * n + i / B] = in[i];
 }
 
-// Probe p's value at vertex i (caller order): the sign bit of the splitmix64 finaliser of
-// seed + golden * ((p << 32) + i + 1), all mod 2^64 (include/lzx.h, lzx_probes_f64).
-__host__ __device__ __forceinline__ double probe_value(u64 seed, u64 p, u64 i)
-{
-    u64 h = seed + 0x9E3779B97F4A7C15ull * ((p << 32) + i + 1);
-    h ^= h >> 30;
-    h *= 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 27;
-    h *= 0x94D049BB133111EBull;
-    h ^= h >> 31;
-    return (h >> 63) ? -1.0 : 1.0;
-}
 
 // out [n][B]: column c < b is probe first + c divided by div (sqrt(n) for a start vector, 1 for lzx_probes_f64); padded columns 0
 template <u32 B>
@@ -174,7 +162,7 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_probe(u64 seed, u64 f
     const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
     if (i >= n * B) return;
     const u32 c = (u32)(i % B);
-    out[i] = c < b ? probe_value(seed, first + c, i / B) / div : 0.0;
+    out[i] = c < b ? lzx_probe_value(seed, first + c, i / B) / div : 0.0;
 }
 
 template <u32 B>

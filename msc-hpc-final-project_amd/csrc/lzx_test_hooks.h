@@ -13,7 +13,8 @@
 // sums its squares in one serial chain; default: one look at x0 first -- a constant vector is filled on the device, a sum that is
 // exact in any order is formed by several threads), "defer_finish" (0: the blocked SpMV always launches k_pb_finish; default: in the lazy loop
 // k_lazy_update adds the totals of multi-item gather bands where it reads v and the launch is left out), "multi_row_chunk" (entries per
-// chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048).
+// chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048), "eig_basis_bytes" (lzx_eigsh_f64 takes a basis larger than this
+// many bytes as out of device memory).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
@@ -45,3 +46,9 @@ int lzx_test_rank_row_sums(lzx_handle h, double *v_local, uint32_t *layout_pos, 
 extern "C"
 #endif
 int lzx_test_allreduce_latency(lzx_handle h, uint32_t reps, double *us_each);
+// The eigensolver's dense symmetric solver (lzx_eig.hip, cyclic Jacobi), no GPU needed: A is n x n row-major (n <= 1024),
+// w the eigenvalues ascending, V[i * n + j] component i of the unit eigenvector of w[j].
+#ifdef __cplusplus
+extern "C"
+#endif
+int lzx_test_sym_eig(uint32_t n, const double *A, double *w, double *V);
