@@ -327,6 +327,52 @@ int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, double tol,
                   const double *x0, uint64_t seed, const double *W, uint32_t nw,
                   double *evals, double *evecs, double *resid, lzx_eig_info *info);
 
+/* ---- shifted linear systems: multi-shift conjugate gradients ------------------------------------------
+ * S(sigma_s) x_s = b for s = 1 .. ns (ns <= 16) from ONE Krylov sequence, on the device, with the handle's operator:
+ * S(sigma) = sigma I - A (option "operator" = LZX_OP_ADJACENCY, the default; Katz centrality x = (beta / alpha) S(1 / alpha)^(-1) 1)
+ * or S(sigma) = sigma I + L (LZX_OP_LAPLACIAN; the regularised Laplacian kernel (I + t L)^(-1) = (1/t) S(1/t)^(-1), and with
+ * sigma = 0 and deflation the pseudo-inverse L+ b).  S(sigma) is symmetric positive definite exactly when sigma > lambda_max(A)
+ * under A, sigma > 0 under L.  No reference counterpart.
+ *   method    plain CG on the seed system, the smallest shift sigma_0 (r_0 = p_0 = b, x = 0); every other shift follows it by the
+ *             multi-shift recurrences (Frommer 2003; Jegerlehner): zeta_{j+1} = zeta_j zeta_{j-1} alpha_{j-1} / (alpha_j beta_{j-1}
+ *             (zeta_{j-1} - zeta_j) + zeta_{j-1} alpha_{j-1} (1 + (sigma_s - sigma_0) alpha_j)), alpha^s_j = alpha_j zeta_{j+1} / zeta_j,
+ *             beta^s_j = (zeta_{j+1} / zeta_j)^2 beta_j.  Shift s's residual is zeta_{s,j} r_j.  One SpMV and two streaming
+ *             kernels per iteration; the state is (2 + 2 ns' + nw) vectors of n_loc_pad + 64 doubles (ns' = distinct shifts).
+ *   stop      shift s is frozen (its x_s and p_s are no longer written) once |zeta_{s,j}| ||r_j|| <= tol ||b||; the seed's r and p
+ *             run on until every shift is frozen or maxiter iterations have run.  The rule is evaluated on the device; the host
+ *             reads a small status every 16 iterations (the results do not depend on that period).
+ *   W         nw <= 8 deflation vectors (nw x n, caller order; NULL when nw = 0), orthonormalised in order on the device: b is
+ *             projected onto span(W)^perp before the solve and every x_s after it.  Under L, sigma_0 = 0 is allowed only with
+ *             nw >= 1 (L+ b: W = 1/sqrt(n) on a connected graph, the component indicators otherwise; b must be orthogonal to the
+ *             rest of the null space).  ||b|| below is the norm after the projection.
+ *   output    X[s * n + i]: x_s in the caller's shift and vertex order (a duplicate shift gets the same vector); iters[s]: the
+ *             iteration at which shift s froze (maxiter if it did not); resid[s]: the true relative residual ||b - S(sigma_s) x_s||
+ *             / ||b||, formed on the device with one SpMV per distinct shift.
+ *   errors    LZX_ERR_ARG: null handle, b or X (or shifts); ns = 0; tol <= 0 or NaN; maxiter = 0; a shift that is not finite or
+ *             < 0; sigma_0 <= 0 under A; sigma_0 = 0 under L without W; nw > 0 with W null; W rank-deficient; b zero or in
+ *             span(W); and, during the solve, p . S(sigma_0) p <= 0 or not finite (S(sigma_0) is not positive definite: the
+ *             message names sigma_0, the iteration and the curvature; nothing is written).  LZX_ERR_LIMIT: ns > 16, nw > 8, or
+ *             maxiter reached before every shift converged (X, iters and resid are still written).  LZX_ERR_STATE: a handle
+ *             with a communicator (one GPU only), no graph.  LZX_ERR_NOMEM: the state does not fit (the message states the
+ *             bytes).  Nothing of the solver is left allocated after any return.
+ *   state     like lzx_spmv_f64 the call voids a prepared (chunked) single-vector decomposition; the resident basis, its
+ *             alpha / beta and the batch state are left alone.
+ *   determinism: identical arguments give identical bits; each x_s does not depend on the order of `shifts` or on
+ *             duplicates, and the seed's x has the bits of a call with sigma_0 alone.
+ * info (or NULL): iterations (the last freeze; the iterations whose results were used), launched (>= iterations: the status
+ * period), converged (caller's shifts that met tol), ns; loop_ms (host clock, whole call), spmv_ms / vec_ms (device event time
+ * of the loop's SpMVs / of its vector kernels), bnorm (||b|| after deflation). */
+typedef struct lzx_solve_info {
+    uint32_t iterations;   /* seed iterations whose results were used (the last freeze) */
+    uint32_t launched;     /* iterations launched, >= iterations (poll granularity)     */
+    uint32_t converged;    /* shifts that met tol                                       */
+    uint32_t ns;
+    double   loop_ms, spmv_ms, vec_ms;   /* host clock of the call; device event time of SpMVs / vector kernels */
+    double   bnorm;        /* ||b|| after deflation */
+} lzx_solve_info;
+int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns, const double *shifts, double tol, uint32_t maxiter,
+                          const double *W, uint32_t nw, double *X, uint32_t *iters, double *resid, lzx_solve_info *info);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -24,7 +24,7 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk", "eig_basis_bytes")
+                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -64,6 +64,14 @@ class LzxEigInfo(ctypes.Structure):
     _fields_ = [("converged", ctypes.c_uint32), ("restarts", ctypes.c_uint32), ("matvecs", ctypes.c_uint32), ("m", ctypes.c_uint32),
                 ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("orth_ms", ctypes.c_double), ("host_ms", ctypes.c_double),
                 ("norm_est", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LzxSolveInfo(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("launched", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("ns", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("vec_ms", ctypes.c_double), ("bnorm", ctypes.c_double)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -121,6 +129,8 @@ SYMBOLS = [
     ("lzx_probe_diag_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p]),
     ("lzx_eigsh_f64", ctypes.c_int, [_h, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, _f64p,
                                      ctypes.c_uint64, _f64p, ctypes.c_uint32, _f64p, _f64p, _f64p, ctypes.POINTER(LzxEigInfo)]),
+    ("lzx_solve_shifted_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, ctypes.c_uint32,
+                                             _f64p, _u32p, _f64p, ctypes.POINTER(LzxSolveInfo)]),
 ]
 
 _LIB = None
@@ -612,6 +622,61 @@ class Engine:
             raise err
         _check(rc, "lzx_eigsh_f64", self.L)
         return result
+
+    def solve_shifted(self, b, shifts, tol: float = 1e-10, maxiter: int = 1000, W=None):
+        """x_s = S(sigma_s)^(-1) b for every shift by multi-shift CG on the device (lzx_solve_shifted_f64): S(sigma) = sigma I - A,
+        or sigma I + L under option operator = OP_LAPLACIAN.  Returns (X, info): X of shape (n,) for a scalar shift, (ns, n)
+        otherwise; info: the lzx_solve_info fields plus "iters" and "resid" (true relative residuals), one per shift.  W: (nw, n)
+        or (n,) deflation vectors (b and every x_s are projected onto their complement).  If maxiter runs out first, LzxError
+        carries the partial (X, info) as `.partial`."""
+        n = self.n
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (n,):
+            raise ValueError(f"solve_shifted: b must have shape ({n},), got {b.shape}")
+        sh = np.asarray(shifts, dtype=np.float64)
+        if sh.ndim > 1:
+            raise ValueError(f"solve_shifted: shifts must be a scalar or a 1-D array, got shape {sh.shape}")
+        s1 = np.ascontiguousarray(np.atleast_1d(sh))
+        ns = len(s1)
+        Wc = None if W is None else np.ascontiguousarray(np.atleast_2d(W), dtype=np.float64)
+        if Wc is not None and Wc.shape[1] != n:
+            raise ValueError(f"solve_shifted: W must have n = {n} columns, got shape {Wc.shape}")
+        nw = 0 if Wc is None else Wc.shape[0]
+        X = np.zeros((max(ns, 1), n))
+        iters = np.zeros(max(ns, 1), dtype=np.uint32)
+        resid = np.zeros(max(ns, 1))
+        info = LzxSolveInfo()
+        rc = self.L.lzx_solve_shifted_f64(self.h, _p(b, _f64p), ns, _p(s1, _f64p) if ns else None, tol, maxiter,
+                                          None if Wc is None else _p(Wc, _f64p), nw, _p(X, _f64p), _p(iters, _u32p), _p(resid, _f64p),
+                                          ctypes.byref(info))
+        d = info.as_dict()
+        d["iters"], d["resid"] = iters[:ns].copy(), resid[:ns].copy()
+        result = (X[0].copy() if sh.ndim == 0 else X[:ns].copy(), d)
+        if rc == ERR_LIMIT and info.launched > 0:   # (info is written only by a run that got through its iterations)
+            err = LzxError(f"lzx_solve_shifted_f64 failed ({rc}): {self.L.lzx_last_error().decode(errors='replace')}")
+            err.partial = result
+            raise err
+        _check(rc, "lzx_solve_shifted_f64", self.L)
+        return result
+
+    def katz(self, alpha=None, beta: float = 1.0, normalized: bool = True, factor: float = 0.85, tol: float = 1e-10, maxiter: int = 1000):
+        """Katz centrality x = beta (I - alpha A)^(-1) 1 as networkx.katz_centrality_numpy defines it (normalised by
+        sign(sum x) ||x||_2), by one multi-shift solve with sigma = 1 / alpha: x = (beta / alpha) S(sigma)^(-1) 1.  alpha=None:
+        factor / lambda_max, lambda_max from eigsh(nev=1).  A list of alpha gives one row per alpha.  Adjacency operator only."""
+        if self.operator != OP_ADJACENCY:
+            raise ValueError("katz: Katz centrality is defined on the adjacency matrix; this engine's operator is the Laplacian")
+        if alpha is None:
+            lam = float(self.eigsh(nev=1, which="LA", want_vectors=False)[0][0])
+            alpha = factor / lam
+        al = np.asarray(alpha, dtype=np.float64)
+        if al.ndim > 1 or np.any(~(al > 0)):
+            raise ValueError("katz: alpha must be a positive scalar or a 1-D array of positive values")
+        a1 = np.atleast_1d(al)
+        X, _ = self.solve_shifted(np.ones(self.n), 1.0 / a1, tol=tol, maxiter=maxiter)
+        X = X * (beta / a1)[:, None]
+        if normalized:
+            X = X / (np.sign(X.sum(axis=1)) * np.linalg.norm(X, axis=1))[:, None]
+        return X[0] if al.ndim == 0 else X
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

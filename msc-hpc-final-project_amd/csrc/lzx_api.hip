@@ -201,6 +201,9 @@ extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
     else if (!strcmp(name, "multi_row_chunk")) c->multi_chunk_opt = value;
     // lzx_eigsh_f64 takes a basis of more than this many bytes as out of device memory (its LZX_ERR_NOMEM path on a small graph)
     else if (!strcmp(name, "eig_basis_bytes")) c->eig_basis_cap_opt = value;
+    // lzx_solve_shifted_f64: a state of more than this many bytes is out of device memory; iterations between its status polls
+    else if (!strcmp(name, "solve_state_bytes")) c->solve_cap_opt = value;
+    else if (!strcmp(name, "solve_poll")) c->solve_poll_opt = value;
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: unknown shape '%s'", name);
     return LZX_OK;
 }

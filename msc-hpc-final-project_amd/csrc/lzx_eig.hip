@@ -269,6 +269,54 @@ extern "C" int lzx_test_sym_eig(uint32_t n, const double *A, double *w, double *
     return LZX_OK;
 }
 
+// ==================================================================================================== host: shared CGS2
+// (include/lzx_internal.h: the solver of lzx_solve.hip deflates with the same launches)
+static int launch_proj(lzx_ctx *c, const double *Q, u32 J, const double *w, u32 G, double *part)
+{
+    hipLaunchKernelGGL(k_eig_proj, dim3(G, (J + LZX_EIG_CT - 1) / LZX_EIG_CT), dim3(LZX_VEC_BLOCK), 0, c->stream, Q, c->ldq, J, w, c->n_loc_pad, part);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+static int launch_update(lzx_ctx *c, const double *Q, u32 J, const double *h, double *w, u32 G, double *npart)
+{
+    hipLaunchKernelGGL(k_eig_update, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, Q, c->ldq, J, h, w, c->n_loc_pad, npart);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+u32 lzx_cgs_grid(const lzx_ctx *c)
+{
+    return std::max<u32>(1u, std::min<u32>((u32)c->cu_count * 4u, (c->n_loc_pad + 2 * LZX_VEC_BLOCK - 1) / (2 * LZX_VEC_BLOCK)));
+}
+
+int lzx_cgs2(lzx_ctx *c, const double *Q, u32 J, double *w, const LzxCgsScratch &s, double *hsum, u32 nw)
+{
+    if (J == 0) return launch_update(c, Q, 0, s.h1, w, s.G, s.npart);
+    LZX_TRY(launch_proj(c, Q, J, w, s.G, s.part));
+    hipLaunchKernelGGL(k_eig_close, dim3(J), dim3(LZX_VEC_BLOCK), 0, c->stream, s.part, s.G, s.h1, nullptr, nullptr, 0u);
+    LZX_TRY(launch_update(c, Q, J, s.h1, w, s.G, nullptr));
+    LZX_TRY(launch_proj(c, Q, J, w, s.G, s.part));
+    hipLaunchKernelGGL(k_eig_close, dim3(J), dim3(LZX_VEC_BLOCK), 0, c->stream, s.part, s.G, s.h2, s.h1, hsum, nw);
+    return launch_update(c, Q, J, s.h2, w, s.G, s.npart);
+}
+
+int lzx_cgs_normalise(lzx_ctx *c, const double *w, double *q, const LzxCgsScratch &s, double *beta_out, double stop)
+{
+    hipLaunchKernelGGL(k_eig_scale, dim3(s.G), dim3(LZX_VEC_BLOCK), 0, c->stream, w, q, s.npart, s.G, beta_out, c->n_loc_pad, stop);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+int lzx_cgs_orthonormalise(lzx_ctx *c, double *Q, u32 i, const LzxCgsScratch &s, double *beta_out)
+{
+    double *q = Q + (size_t)i * c->ldq;
+    LZX_TRY(launch_update(c, Q, 0, s.h1, q, s.G, s.npart));
+    LZX_TRY(lzx_cgs_normalise(c, q, q, s, nullptr, -1.0));
+    LZX_TRY(lzx_cgs2(c, Q, i, q, s));
+    return lzx_cgs_normalise(c, q, q, s, beta_out, 1e-10);
+}
+
 // ==================================================================================================== host: driver
 namespace {
 struct EigRun {
@@ -305,36 +353,10 @@ struct EigRun {
         if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, x, nullptr, 0, c->n_loc_pad));
         return LZX_OK;
     }
-    int proj(const double *w, u32 J)
-    {
-        hipLaunchKernelGGL(k_eig_proj, dim3(G, (J + LZX_EIG_CT - 1) / LZX_EIG_CT), dim3(LZX_VEC_BLOCK), 0, c->stream, d_B, c->ldq, J, w,
-                           c->n_loc_pad, part);
-        LZX_HIP(hipGetLastError());
-        return LZX_OK;
-    }
-    int update(double *w, u32 J, const double *h, bool norm)
-    {
-        hipLaunchKernelGGL(k_eig_update, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, d_B, c->ldq, J, h, w, c->n_loc_pad, norm ? npart : nullptr);
-        LZX_HIP(hipGetLastError());
-        return LZX_OK;
-    }
+    LzxCgsScratch scratch() const { return LzxCgsScratch{G, part, h1, h2, npart}; }
     // w orthogonalised against columns [0, J) by CGS2, the norm partials of the result in npart; hsum: column of H
-    int orth(double *w, u32 J, double *hsum)
-    {
-        if (J == 0) return update(w, 0, h1, true);
-        LZX_TRY(proj(w, J));
-        hipLaunchKernelGGL(k_eig_close, dim3(J), dim3(LZX_VEC_BLOCK), 0, c->stream, part, G, h1, nullptr, nullptr, 0u);
-        LZX_TRY(update(w, J, h1, false));
-        LZX_TRY(proj(w, J));
-        hipLaunchKernelGGL(k_eig_close, dim3(J), dim3(LZX_VEC_BLOCK), 0, c->stream, part, G, h2, h1, hsum, nw);
-        return update(w, J, h2, true);
-    }
-    int scale(const double *w, double *q, double *beta_out, double stop)
-    {
-        hipLaunchKernelGGL(k_eig_scale, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, w, q, npart, G, beta_out, c->n_loc_pad, stop);
-        LZX_HIP(hipGetLastError());
-        return LZX_OK;
-    }
+    int orth(double *w, u32 J, double *hsum) { return lzx_cgs2(c, d_B, J, w, scratch(), hsum, nw); }
+    int scale(const double *w, double *q, double *beta_out, double stop) { return lzx_cgs_normalise(c, w, q, scratch(), beta_out, stop); }
     int rotate(u32 first, u32 min_, const std::vector<double> &Yh, u32 ldy, u32 p)
     {
         LZX_HIP(hipMemcpyAsync(Y, Yh.data(), sizeof(double) * min_ * ldy, hipMemcpyHostToDevice, c->stream));
@@ -346,13 +368,7 @@ struct EigRun {
     }
     // column i (which already holds a vector) made unit, orthogonalised against columns [0, i), made unit again; the
     // final beta goes to tmp[slot] (0: the vector lay in their span)
-    int orthonormalise(u32 i, u32 slot)
-    {
-        LZX_TRY(update(col(i), 0, h1, true));
-        LZX_TRY(scale(col(i), col(i), nullptr, -1.0));
-        LZX_TRY(orth(col(i), i, nullptr));
-        return scale(col(i), col(i), tmp + slot, 1e-10);
-    }
+    int orthonormalise(u32 i, u32 slot) { return lzx_cgs_orthonormalise(c, d_B, i, scratch(), tmp + slot); }
     // fresh start in column i: probe p of seed (x0 == nullptr) or x0, orthonormalised against [0, i); returns its beta
     int start(u32 i, const double *x0, u64 seed, u64 p, double *beta_host)
     {
@@ -441,7 +457,7 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
         LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the basis of (nw + m + 1) = %u columns needs %llu bytes of device memory: %s",
                  fn, nw + m + 1, (unsigned long long)basis_bytes, hipGetErrorString(e));
     }
-    r.G = std::max<u32>(1u, std::min<u32>((u32)c->cu_count * 4u, (c->n_loc_pad + 2 * LZX_VEC_BLOCK - 1) / (2 * LZX_VEC_BLOCK)));
+    r.G = lzx_cgs_grid(c);
     const u32 Jmax = nw + m + 1, ldy = (m + LZX_EIG_CT - 1) / LZX_EIG_CT * LZX_EIG_CT;
     const u64 scratch = (u64)Jmax * r.G + 2ull * Jmax + (u64)m * m + m + r.G + (u64)m * ldy + 16;
     LZX_HIP(hipMalloc(reinterpret_cast<void **>(&r.d_s), sizeof(double) * scratch));

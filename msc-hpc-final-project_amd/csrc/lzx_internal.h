@@ -356,6 +356,8 @@ struct lzx_ctx {
     struct lzx_multi_state *multi = nullptr;
     int64_t multi_chunk_opt = -1;      // test shape multi_row_chunk: entries per chunk of a split row in the batched SpMM (-1: LZX_MULTI_CHUNK)
     int64_t eig_basis_cap_opt = -1;    // test shape eig_basis_bytes: lzx_eigsh_f64 treats a basis larger than this as out of device memory
+    int64_t solve_cap_opt = -1;        // test shape solve_state_bytes: lzx_solve_shifted_f64 treats a state larger than this as out of device memory
+    int64_t solve_poll_opt = -1;       // test shape solve_poll: iterations between the shifted solver's status polls (default 16)
 };
 
 // ---- lzx_graph.hip ----
@@ -365,6 +367,24 @@ int lzx_graph_prepare(lzx_ctx *c);   // builds this rank's share from d_row_ptr/
 // ---- lzx_multi.hip ----
 // with_tables: the per-graph work list goes too (a new graph, lzx_destroy); otherwise only the batch basis and work vectors
 void lzx_multi_free(lzx_ctx *c, bool with_tables);
+
+// ---- lzx_eig.hip: classical Gram-Schmidt twice against the columns of a block Q (stride ldq, zero tails), shared by the
+// eigensolver and the shifted solver (lzx_solve.hip) ----
+struct LzxCgsScratch {
+    u32 G;                  // workgroups of the launches (lzx_cgs_grid)
+    double *part;           // [J][G] projection partials
+    double *h1, *h2;        // [J] the two passes' coefficients
+    double *npart;          // [G] partials of ||w||^2 after the last pass
+};
+u32 lzx_cgs_grid(const lzx_ctx *c);
+// w -= Q Q^T w twice over columns [0, J) (J = 0: nothing), the norm partials of the result in s.npart; hsum != nullptr:
+// hsum[c - nw] = h1[c] + h2[c] for the columns c >= nw (the eigensolver's column of H)
+int lzx_cgs2(lzx_ctx *c, const double *Q, u32 J, double *w, const LzxCgsScratch &s, double *hsum = nullptr, u32 nw = 0);
+// q = w / beta, beta = sqrt(sum of s.npart) (-> *beta_out); beta <= stop: beta = 0 and q = 0
+int lzx_cgs_normalise(lzx_ctx *c, const double *w, double *q, const LzxCgsScratch &s, double *beta_out, double stop);
+// column i of Q made unit, orthogonalised against columns [0, i), made unit again; its final norm (0: it lay in their span,
+// relative 1e-10) -> *beta_out (device)
+int lzx_cgs_orthonormalise(lzx_ctx *c, double *Q, u32 i, const LzxCgsScratch &s, double *beta_out);
 
 // ---- lzx_pb.hip ----
 // Builds the propagation-blocked structure for this rank's non-hub entries. d_nh_off: exclusive prefix of the
