@@ -92,9 +92,11 @@ def test_production_forms_match_cpu(pkg, host, tmp_path, path, pb):
     t = 5.0 / (2.0 * d.max())
     x0 = np.random.default_rng(2).standard_normal(n)
     y_c, a_c, b_c, _ = host_run(host, mtx, n, 30, t, x0)
-    eng = pkg.Engine(0, propagation_blocking=pb, operator=LAP)
+    # (hub_entries=64: propagation_blocking=1 alone stages min(16384, n) columns and leaves nothing to block on graphs this small)
+    eng = pkg.Engine(0, propagation_blocking=pb, operator=LAP, **(dict(hub_entries=64) if pb else {}))
     try:
         eng.set_graph_csr(rp, ci)
+        assert (eng.info()["pb_entries"] > 0) == (pb == 1)
         assert rel_inf(eng.expm_multiply(x0, 30, t), y_c) <= 1e-10
         a, b, Q, xn, _ = eng.lanczos(x0, 30)
         assert abs(a[0] - a_c[0]) <= 1e-12 * abs(a_c[0]) and abs(b[0] - b_c[0]) <= 1e-12 * abs(b_c[0])
@@ -120,9 +122,10 @@ def test_spmv_is_exact_laplacian(pkg, oracle, pb):
     n = len(rp) - 1
     x = np.random.default_rng(3).integers(-50, 50, n).astype(np.float64)   # integer-valued: every sum exact
     ref = d * x - A @ x
-    eng = pkg.Engine(0, propagation_blocking=pb)
+    eng = pkg.Engine(0, propagation_blocking=pb, **(dict(hub_entries=64) if pb else {}))   # (n = 12000 < 16384: see above)
     try:
         eng.set_graph_csr(rp, ci)
+        assert (eng.info()["pb_entries"] > 0) == (pb == 1)
         y_a = eng.spmv(x)
         assert np.array_equal(y_a, A @ x)
         eng.set_option("operator", LAP)
@@ -189,9 +192,10 @@ def test_default_operator_is_unchanged(pkg):
     x0 = np.random.default_rng(5).standard_normal(n)
     out = []
     for opts, flip in (({}, False), ({"operator": 0}, False), ({}, True)):
-        eng = pkg.Engine(0, propagation_blocking=1, **opts)
+        eng = pkg.Engine(0, propagation_blocking=1, hub_entries=64, **opts)
         try:
             eng.set_graph_csr(rp, ci)
+            assert eng.info()["pb_entries"] > 0
             if flip:   # L, then back to A on the same graph
                 eng.lanczos(x0, 20, want_q=False)
                 eng.set_option("operator", LAP)
