@@ -373,6 +373,53 @@ typedef struct lzx_solve_info {
 int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns, const double *shifts, double tol, uint32_t maxiter,
                           const double *W, uint32_t nw, double *X, uint32_t *iters, double *resid, lzx_solve_info *info);
 
+/* ---- connected components and induced subgraphs --------------------------------------------------------
+ * Everything above treats the graph as one piece; R-MAT graphs are not (tests/golden/rmat_n4096: 1 204 components, 1 200 of them
+ * single vertices), and under L every component adds a copy of the eigenvalue 0.  These two calls name the pieces and hand a
+ * handle one of them, on the device, from the caller-order CSR the handle keeps.  One GPU handle only.  No reference counterpart.
+ *
+ * lzx_components: labels[i] (or NULL: counts only, no n-vector crosses PCIe) = the smallest vertex id of i's component, in the
+ * caller's order -- canonical: any correct algorithm gives these bits.  A self loop changes nothing; a vertex without an edge
+ * labels itself and counts as a component of size 1.
+ *   method    min-label hooking with pointer jumping (FastSV's two hookings): parents f (f[v] = v at the start), grandparents
+ *             gf = f[f].  A round is one pull sweep over the CSR -- row u takes m = min(gf[u], gf of its neighbours), then u and
+ *             its parent f[u] are lowered to m in the next parent array (32-bit vector atomicMin, at most two per row and only
+ *             where they lower something) -- followed by f = next, gf = f[f].  A sweep reads f and gf only and writes by
+ *             minimum, so the labels AND the number of rounds are the same in every run.  The host reads one word per round;
+ *             the round that lowers nothing is the last (and is counted).  More than n + 1 rounds: LZX_ERR_LIMIT (cannot
+ *             happen on a symmetric matrix).
+ *   info      (or NULL) n_components, largest_size and largest_label are formed on the device: roots (label == id) counted with
+ *             the fixed-shape block reduction, sizes in a u32 histogram on the roots, the largest by size then smallest label.
+ *   state     the call touches none: it neither voids a prepared or chunked decomposition nor touches the resident bases or the
+ *             batch state, and what it allocates (16 n bytes and a few KiB) is freed before it returns.
+ *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded hand-over
+ *             over several ranks (where lzx_get_graph_csr refuses too).  LZX_ERR_NOMEM: the message states the bytes.
+ *
+ * lzx_set_graph_induced: dst receives the subgraph of src's graph induced by the vertices with keep[i] != 0 (keep: [n of src]),
+ * renumbered in ascending old id; old_of_new[j] (or NULL; [n_new]) = the old id of new vertex j, *n_new (or NULL) their number.
+ * dst == src replaces the graph in place; two different handles must be on the same GPU.  Only the mask crosses PCIe: the new
+ * ids are a scan of the mask, the kept neighbours of every kept row are counted, the counts scanned into row pointers and the
+ * columns written under their new ids -- the map is monotone, so they stay ascending -- and the result is handed to the same
+ * reshaping every hand-over ends in, under dst's options.  Afterwards dst is in exactly the state lzx_set_graph_csr of that CSR
+ * would have left it in: same status (degenerate subgraphs included), same lzx_get_graph_csr and lzx_get_graph_info, same bits
+ * out of every later call.  (With dst's option "sharded_ingest" set the subgraph IS handed to lzx_set_graph_csr through host
+ * memory, which that option streams from.)
+ *   errors    LZX_ERR_ARG: null dst, src or keep; nothing kept; handles on different GPUs (the message names both devices).
+ *             LZX_ERR_STATE: either handle with a communicator, src without a graph or without a whole caller-order CSR.
+ *             After any of these, and after a failed allocation while the subgraph is built, dst keeps the graph it had; a
+ *             failure of the reshaping itself leaves dst as the same failure of lzx_set_graph_csr would. */
+typedef struct lzx_components_info {
+    uint64_t n_components;     /* isolated vertices count as components of size 1 */
+    uint64_t largest_size;     /* vertices of the largest component */
+    uint32_t largest_label;    /* its label; ties: the smallest label */
+    uint32_t rounds;           /* sweeps over the edges until nothing changed */
+    double   loop_ms;          /* host clock, whole call */
+    double   sweep_ms;         /* device event time of the edge sweeps alone */
+} lzx_components_info;
+int lzx_components(lzx_handle h, uint32_t *labels /* [n], caller order */, lzx_components_info *info /* or NULL */);
+int lzx_set_graph_induced(lzx_handle dst, lzx_handle src, const uint8_t *keep /* [n of src], non-zero = keep */,
+                          uint32_t *old_of_new /* [n_new] or NULL */, uint64_t *n_new /* or NULL */);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -77,6 +77,14 @@ class LzxSolveInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxComponentsInfo(ctypes.Structure):
+    _fields_ = [("n_components", ctypes.c_uint64), ("largest_size", ctypes.c_uint64), ("largest_label", ctypes.c_uint32),
+                ("rounds", ctypes.c_uint32), ("loop_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -131,6 +139,8 @@ SYMBOLS = [
                                      ctypes.c_uint64, _f64p, ctypes.c_uint32, _f64p, _f64p, _f64p, ctypes.POINTER(LzxEigInfo)]),
     ("lzx_solve_shifted_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, ctypes.c_uint32,
                                              _f64p, _u32p, _f64p, ctypes.POINTER(LzxSolveInfo)]),
+    ("lzx_components", ctypes.c_int, [_h, _u32p, ctypes.POINTER(LzxComponentsInfo)]),
+    ("lzx_set_graph_induced", ctypes.c_int, [_h, _h, _u8p, _u32p, _u64p]),
 ]
 
 _LIB = None
@@ -278,6 +288,7 @@ class Engine:
 
     def __init__(self, device: int = 0, **options):
         self.h = ctypes.c_void_p()
+        self.device = device
         self.operator = OP_ADJACENCY
         self.debug = any(k not in PRODUCT_OPTIONS and k not in SHAPE_OPTIONS for k in options)   # experiment knobs: liblzx_dbg.so
         self.L = lib(debug=self.debug)
@@ -678,6 +689,67 @@ class Engine:
             X = X / (np.sign(X.sum(axis=1)) * np.linalg.norm(X, axis=1))[:, None]
         return X[0] if al.ndim == 0 else X
 
+    # ---- connected components and induced subgraphs (include/lzx.h: lzx_components, lzx_set_graph_induced) ----
+    def components(self, want_labels: bool = True):
+        """Connected components on the device.  Returns (labels, info): labels[i] = the smallest vertex id of i's component (uint32,
+        caller's order; None with want_labels=False, and then no n-vector leaves the device), info = the lzx_components_info
+        fields (n_components, largest_size, largest_label, rounds, loop_ms, sweep_ms)."""
+        labels = np.empty(self.n, dtype=np.uint32) if want_labels else None
+        info = LzxComponentsInfo()
+        _check(self.L.lzx_components(self.h, _p(labels, _u32p) if want_labels else None, ctypes.byref(info)), "lzx_components", self.L)
+        return labels, info.as_dict()
+
+    def _keep_mask(self, keep, what):
+        keep = np.asarray(keep)
+        if keep.shape != (self.n,):
+            raise ValueError(f"{what}: keep must have shape ({self.n},), one entry per vertex, got {keep.shape}")
+        return np.ascontiguousarray(keep != 0, dtype=np.uint8)
+
+    def _induce_into(self, dst, keep, what):
+        old = np.empty(max(int(np.count_nonzero(keep)), 1), dtype=np.uint32)
+        n_new = ctypes.c_uint64()
+        _check(self.L.lzx_set_graph_induced(dst.h, self.h, _p(keep, _u8p), _p(old, _u32p), ctypes.byref(n_new)), what, self.L)
+        dst.n = int(n_new.value)
+        return old[:dst.n]
+
+    def induced(self, keep, device=None, **options):
+        """A new Engine (this one's GPU; `options` as for Engine()) holding the subgraph induced by the vertices with keep[i] != 0,
+        built on the device and renumbered in ascending old id.  Returns (engine, old_of_new)."""
+        keep = self._keep_mask(keep, "induced")
+        sub = Engine(self.device if device is None else device, **options)
+        try:
+            if sub.debug != self.debug:   # two libraries, two handle layouts: both handles must come from the same one
+                raise ValueError("induced: the options select the other build of the library (product / debug knobs) than this Engine's")
+            old = self._induce_into(sub, keep, "lzx_set_graph_induced")
+        except Exception:
+            sub.close()
+            raise
+        return sub, old
+
+    def restrict(self, keep):
+        """Replace this Engine's graph by its subgraph on the vertices with keep[i] != 0 (lzx_set_graph_induced with dst == src).
+        Returns old_of_new.  If the call fails the Engine keeps its graph."""
+        return self._induce_into(self, self._keep_mask(keep, "restrict"), "lzx_set_graph_induced(in place)")
+
+    def largest_component(self, **options):
+        """components() followed by induced(labels == largest_label): (engine on the largest component, old_of_new)."""
+        labels, info = self.components()
+        return self.induced(labels == info["largest_label"], **options)
+
+    @staticmethod
+    def component_indicators(labels, which):
+        """W[nw][n]: the unit indicator vectors of the components whose labels are listed in `which` (host numpy) -- the null
+        space of L on those components, ready to be the deflation vectors of solve_shifted and eigsh."""
+        labels = np.asarray(labels)
+        which = np.atleast_1d(np.asarray(which))
+        W = np.zeros((len(which), len(labels)))
+        for i, r in enumerate(which):
+            members = labels == r
+            if not members.any() or labels[int(r)] != r:
+                raise ValueError(f"component_indicators: {int(r)} is not the label of a component")
+            W[i, members] = 1.0 / np.sqrt(np.count_nonzero(members))
+        return W
+
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()
         _check(self.L.lzx_bench_stream(self.h, nbytes, reps, ctypes.byref(rd), ctypes.byref(cp)), "lzx_bench_stream", self.L)
@@ -713,6 +785,7 @@ class LocalGroup:
         for h in self.arr:
             e = Engine.__new__(Engine)
             e.h, e.debug, e.L, e.n = ctypes.c_void_p(h), False, self.L, 0
+            e.device = devices[len(self.engines)]
             self.engines.append(e)
         self.n = 0
         return self
