@@ -82,129 +82,137 @@ extern "C" void lzx_destroy(lzx_handle c)
     for (double *&r : c->d_ring) { if (r) (void)hipFree(r); r = nullptr; }
     for (double *&r : c->d_ymon) { if (r) (void)hipFree(r); r = nullptr; }
     for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-    if (c->ev_a) (void)hipEventDestroy(c->ev_a);
-    if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-    if (c->ev_phase) (void)hipEventDestroy(c->ev_phase);
-    if (c->ev_phase2) (void)hipEventDestroy(c->ev_phase2);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_q) (void)hipEventDestroy(c->ev_q);
-    if (c->ev_c0) (void)hipEventDestroy(c->ev_c0);
-    if (c->ev_c1) (void)hipEventDestroy(c->ev_c1);
+    for (hipEvent_t ev : {c->ev_a, c->ev_b, c->ev_phase, c->ev_phase2, c->ev_fork, c->ev_join, c->ev_q, c->ev_c0, c->ev_c1})
+        if (ev) (void)hipEventDestroy(ev);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
     if (c->stream3) { (void)hipStreamSynchronize(c->stream3); (void)hipStreamDestroy(c->stream3); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
+// Every option name, once.  Who accepts a row:
+//   OPT_PRODUCT  lzx_set_option of both libraries (the documented options of include/lzx.h)
+//   OPT_KNOB     lzx_set_option of liblzx_dbg.so only (make debug, -DLZX_DEBUG_KNOBS): experiment knobs and test hooks, which
+//                tests/ and tools/perf_probe.py load when they ask for one; rows that are knobs and nothing else are compiled
+//                out of the product library, which does not know their names
+//   OPT_SHAPE    lzx_test_set_shape (csrc/lzx_test_hooks.h): selects among code paths the product build contains
+//   OPT_LOOP     shapes the LOOP, not the graph: may change between decompositions, i.e. after the hand-over, and abandons a
+//                decomposition that was being advanced in chunks (what it has done stays usable)
+enum : unsigned { OPT_PRODUCT = 1, OPT_KNOB = 2, OPT_SHAPE = 4, OPT_LOOP = 8 };
+struct Option {
+    const char *name;
+    int64_t lzx_ctx::*field;   // null: not a plain store (set_named_option)
+    unsigned flags;
+};
+static const Option g_options[] = {
+    {"hub_entries", &lzx_ctx::hub_opt, OPT_PRODUCT},
+    {"propagation_blocking", &lzx_ctx::pb_opt, OPT_PRODUCT},
+    {"overlap_exchange", &lzx_ctx::overlap_opt, OPT_PRODUCT},
+    {"lazy_normalisation", &lzx_ctx::lazy_opt, OPT_PRODUCT},
+    {"sparse_exchange", &lzx_ctx::sparse_opt, OPT_PRODUCT},
+    {"exchange_fp32", &lzx_ctx::xfp32_opt, OPT_PRODUCT},
+    {"timing_marks_every", &lzx_ctx::marks_every_opt, OPT_PRODUCT},
+    {"reorthogonalise", &lzx_ctx::reorth_opt, OPT_PRODUCT | OPT_LOOP},
+    {"basis_fp32", &lzx_ctx::qf32_opt, OPT_PRODUCT | OPT_LOOP},
+    {"reference_order", &lzx_ctx::ref_order_opt, OPT_PRODUCT | OPT_LOOP},
+    {"operator", &lzx_ctx::op_opt, OPT_PRODUCT | OPT_LOOP},   // range-checked
+    {"placement_trials", &lzx_ctx::place_opt, OPT_PRODUCT},
+    {"sharded_ingest", &lzx_ctx::shard_opt, OPT_PRODUCT},   // negative values count as 0
+    // the table shapes large graphs get by themselves, forced on small test graphs: run formats, band / item / unit sizes,
+    // slice classes, gather groups, tie-break
+    {"pb_reduce", &lzx_ctx::pb_reduce_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_target", &lzx_ctx::pb_target_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_unit", &lzx_ctx::pb_unit_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_column_band", &lzx_ctx::pb_cb_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_run_align", &lzx_ctx::pb_align_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_taper", &lzx_ctx::pb_taper_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_dyn_share", &lzx_ctx::pb_dyn_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_carry_scan", &lzx_ctx::pb_scan_opt, OPT_SHAPE},
+    {"pb_scatter_nt", &lzx_ctx::pb_scatter_nt_opt, OPT_SHAPE},
+    {"pb_gather_grid", &lzx_ctx::pb_grid_cap_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_gather_nt", &lzx_ctx::pb_gather_nt_opt, OPT_SHAPE | OPT_KNOB},
+    {"spmv_wgs", &lzx_ctx::spmv_wgs_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_group", &lzx_ctx::pb_group_opt, OPT_SHAPE | OPT_KNOB},
+    {"pb_group_force", &lzx_ctx::pb_group_force_opt, OPT_SHAPE | OPT_KNOB},
+    {"narrow_slices", &lzx_ctx::narrow_opt, OPT_SHAPE | OPT_KNOB},
+    {"tie_sort", &lzx_ctx::tie_sort_opt, OPT_SHAPE | OPT_KNOB},
+    {"long_row", &lzx_ctx::long_row_opt, OPT_SHAPE | OPT_KNOB},
+    {"item_len", &lzx_ctx::item_opt, OPT_SHAPE | OPT_KNOB},
+    // the several-rank loop on a 1-rank RCCL communicator, so that the parity tests exercise the same machine code the bench
+    // runs; writes the bool force_multi
+    {"exchange_at_world_1", nullptr, OPT_SHAPE | OPT_KNOB},
+    // the lazy loop's two other forms (rows without an edge elementwise instead of one scalar recurrence; q_j stored instead of
+    // the unnormalised u_j) and the staged-columns workgroups' place in the shared launch: all compiled into the product
+    {"isolated_rows", &lzx_ctx::iso_opt, OPT_SHAPE | OPT_KNOB},
+    {"unnormalised_basis", &lzx_ctx::basis_u_opt, OPT_SHAPE | OPT_KNOB},
+    {"fuse_staged", &lzx_ctx::fuse_opt, OPT_SHAPE | OPT_KNOB},
+    // 0: the start vector always crosses PCIe and its norm is always the serial chain (what round 5's look at x0 is compared with)
+    {"start_vector_scan", &lzx_ctx::x0_scan_opt, OPT_SHAPE | OPT_KNOB},
+    // 0: the blocked SpMV always launches k_pb_finish (default: the lazy loop's vector kernel stands in for it)
+    {"defer_finish", &lzx_ctx::defer_opt, OPT_SHAPE | OPT_KNOB},
+    // entries per chunk of a split row in the batched SpMM (lzx_multi.hip; default LZX_MULTI_CHUNK)
+    {"multi_row_chunk", &lzx_ctx::multi_chunk_opt, OPT_SHAPE},
+    // lzx_eigsh_f64 takes a basis of more than this many bytes as out of device memory (its LZX_ERR_NOMEM path on a small graph)
+    {"eig_basis_bytes", &lzx_ctx::eig_basis_cap_opt, OPT_SHAPE},
+    // lzx_solve_shifted_f64: a state of more than this many bytes is out of device memory; iterations between its status polls
+    {"solve_state_bytes", &lzx_ctx::solve_cap_opt, OPT_SHAPE},
+    {"solve_poll", &lzx_ctx::solve_poll_opt, OPT_SHAPE},
+#ifdef LZX_DEBUG_KNOBS
+    {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
+    {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},
+    {"side_stream", &lzx_ctx::side_opt, OPT_KNOB},
+    {"pb_stamps", &lzx_ctx::pb_stamps_opt, OPT_KNOB},
+    {"pb_order", &lzx_ctx::pb_order_opt, OPT_KNOB},
+    {"spmv_deep", &lzx_ctx::deep_opt, OPT_KNOB},
+    {"stage_burst", &lzx_ctx::burst_opt, OPT_KNOB},
+    {"vec_blocks_per_cu", &lzx_ctx::vec_per_cu_opt, OPT_KNOB},
+    {"pb_gather_waves", &lzx_ctx::pb_gwaves_opt, OPT_KNOB},
+    {"phase_mask", &lzx_ctx::phase_mask_opt, OPT_KNOB},
+#endif
+};
+
+// the row of `name` if one of `accepted` is among its flags
+static const Option *find_option(const char *name, unsigned accepted)
+{
+    for (const Option &o : g_options)
+        if ((o.flags & accepted) && !strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
+static void store_option(lzx_ctx *c, const Option &o, int64_t value)
+{
+    if (!o.field) c->force_multi = value > 0;   // exchange_at_world_1, the one row without a field
+    else if (o.field == &lzx_ctx::shard_opt) c->shard_opt = value < 0 ? 0 : value;
+    else c->*o.field = value;
+}
+
 extern "C" int lzx_set_option(lzx_handle c, const char *name, int64_t value)
 {
     if (!c || !name) LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: bad argument");
-    // the options that shape the LOOP, not the graph, may change between decompositions
-    const bool loop_option = !strcmp(name, "reorthogonalise") || !strcmp(name, "basis_fp32") || !strcmp(name, "reference_order") ||
-                             !strcmp(name, "operator");
-    if (!strcmp(name, "operator") && value != LZX_OP_ADJACENCY && value != LZX_OP_LAPLACIAN)
+#ifdef LZX_DEBUG_KNOBS
+    const Option *o = find_option(name, OPT_PRODUCT | OPT_KNOB);
+#else
+    const Option *o = find_option(name, OPT_PRODUCT);
+#endif
+    const bool loop_option = o && (o->flags & OPT_LOOP);
+    if (o && o->field == &lzx_ctx::op_opt && value != LZX_OP_ADJACENCY && value != LZX_OP_LAPLACIAN)
         LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: operator must be LZX_OP_ADJACENCY (0) or LZX_OP_LAPLACIAN (1), got %lld", (long long)value);
     if (c->d_row_ptr && !loop_option) LZX_FAIL(LZX_ERR_STATE, "options must be set before the graph is handed over");
-    if (loop_option) c->k_prep = 0;   // a decomposition that was being advanced in chunks is abandoned (what it has done stays usable)
-    if (!strcmp(name, "hub_entries")) c->hub_opt = value;
-    else if (!strcmp(name, "propagation_blocking")) c->pb_opt = value;
-    else if (!strcmp(name, "overlap_exchange")) c->overlap_opt = value;
-    else if (!strcmp(name, "lazy_normalisation")) c->lazy_opt = value;
-    else if (!strcmp(name, "sparse_exchange")) c->sparse_opt = value;
-    else if (!strcmp(name, "exchange_fp32")) c->xfp32_opt = value;
-    else if (!strcmp(name, "timing_marks_every")) c->marks_every_opt = value;
-    else if (!strcmp(name, "reorthogonalise")) c->reorth_opt = value;
-    else if (!strcmp(name, "basis_fp32")) c->qf32_opt = value;
-    else if (!strcmp(name, "reference_order")) c->ref_order_opt = value;
-    else if (!strcmp(name, "operator")) c->op_opt = value;
-    else if (!strcmp(name, "placement_trials")) c->place_opt = value;
-    else if (!strcmp(name, "sharded_ingest")) c->shard_opt = value < 0 ? 0 : value;
-#ifdef LZX_DEBUG_KNOBS
-    // experiment knobs and test hooks: only in liblzx_dbg.so (make debug), which tests/ and tools/perf_probe.py load
-    // when they ask for one of these; the product library does not know the names
-    else if (!strcmp(name, "wgs_per_cu")) c->wgs_per_cu_opt = value;
-    else if (!strcmp(name, "nt_index_loads")) c->nt_opt = value;
-    else if (!strcmp(name, "long_row")) c->long_row_opt = value;
-    else if (!strcmp(name, "pb_target")) c->pb_target_opt = value;
-    else if (!strcmp(name, "pb_run_align")) c->pb_align_opt = value;
-    else if (!strcmp(name, "pb_reduce")) c->pb_reduce_opt = value;
-    else if (!strcmp(name, "pb_unit")) c->pb_unit_opt = value;
-    else if (!strcmp(name, "pb_taper")) c->pb_taper_opt = value;
-    else if (!strcmp(name, "pb_dyn_share")) c->pb_dyn_opt = value;
-    else if (!strcmp(name, "pb_gather_grid")) c->pb_grid_cap_opt = value;
-    else if (!strcmp(name, "pb_gather_nt")) c->pb_gather_nt_opt = value;
-    else if (!strcmp(name, "spmv_wgs")) c->spmv_wgs_opt = value;
-    else if (!strcmp(name, "pb_column_band")) c->pb_cb_opt = value;
-    else if (!strcmp(name, "side_stream")) c->side_opt = value;
-    else if (!strcmp(name, "pb_stamps")) c->pb_stamps_opt = value;
-    else if (!strcmp(name, "pb_order")) c->pb_order_opt = value;
-    else if (!strcmp(name, "spmv_deep")) c->deep_opt = value;
-    else if (!strcmp(name, "tie_sort")) c->tie_sort_opt = value;
-    else if (!strcmp(name, "pb_group")) c->pb_group_opt = value;
-    else if (!strcmp(name, "pb_group_force")) c->pb_group_force_opt = value;
-    else if (!strcmp(name, "item_len")) c->item_opt = value;
-    else if (!strcmp(name, "stage_burst")) c->burst_opt = value;
-    else if (!strcmp(name, "vec_blocks_per_cu")) c->vec_per_cu_opt = value;
-    else if (!strcmp(name, "narrow_slices")) c->narrow_opt = value;
-    else if (!strcmp(name, "fuse_staged")) c->fuse_opt = value;
-    else if (!strcmp(name, "isolated_rows")) c->iso_opt = value;
-    else if (!strcmp(name, "unnormalised_basis")) c->basis_u_opt = value;
-    else if (!strcmp(name, "pb_gather_waves")) c->pb_gwaves_opt = value;
-    else if (!strcmp(name, "exchange_at_world_1")) c->force_multi = value > 0;
-    else if (!strcmp(name, "phase_mask")) c->phase_mask_opt = value;
-    else if (!strcmp(name, "start_vector_scan")) c->x0_scan_opt = value;
-    else if (!strcmp(name, "defer_finish")) c->defer_opt = value;
-#endif
-    else LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: unknown option '%s'", name);
+    if (!o) LZX_FAIL(LZX_ERR_ARG, "lzx_set_option: unknown option '%s'", name);
+    if (loop_option) c->k_prep = 0;
+    store_option(c, *o, value);
     return LZX_OK;
 }
 
-// Test-only entry of the PRODUCT library (declared in csrc/lzx_test_hooks.h, not in include/lzx.h): forces, on small test
-// graphs, the table shapes large graphs get by themselves -- run formats, band / item / unit sizes, slice classes, gather
-// groups, tie-break -- and the hook that runs the several-rank loop on a 1-rank RCCL communicator, so that the parity
-// tests exercise the same machine code the bench runs.  Every name below only selects among
-// code paths the product build contains; the experiment knobs stay in liblzx_dbg.so.
+// Test-only entry of the PRODUCT library (declared in csrc/lzx_test_hooks.h, not in include/lzx.h): the OPT_SHAPE rows.  Every
+// one of them only selects among code paths the product build contains; the experiment knobs stay in liblzx_dbg.so.
 extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
 {
     if (!c || !name) LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: bad argument");
     if (c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "shapes must be set before the graph is handed over");
-    if (!strcmp(name, "pb_reduce")) c->pb_reduce_opt = value;
-    else if (!strcmp(name, "pb_target")) c->pb_target_opt = value;
-    else if (!strcmp(name, "pb_unit")) c->pb_unit_opt = value;
-    else if (!strcmp(name, "pb_column_band")) c->pb_cb_opt = value;
-    else if (!strcmp(name, "pb_run_align")) c->pb_align_opt = value;
-    else if (!strcmp(name, "pb_taper")) c->pb_taper_opt = value;
-    else if (!strcmp(name, "pb_dyn_share")) c->pb_dyn_opt = value;
-    else if (!strcmp(name, "pb_carry_scan")) c->pb_scan_opt = value;
-    else if (!strcmp(name, "pb_scatter_nt")) c->pb_scatter_nt_opt = value;
-    else if (!strcmp(name, "pb_gather_grid")) c->pb_grid_cap_opt = value;
-    else if (!strcmp(name, "pb_gather_nt")) c->pb_gather_nt_opt = value;
-    else if (!strcmp(name, "spmv_wgs")) c->spmv_wgs_opt = value;
-    else if (!strcmp(name, "pb_group")) c->pb_group_opt = value;
-    else if (!strcmp(name, "pb_group_force")) c->pb_group_force_opt = value;
-    else if (!strcmp(name, "narrow_slices")) c->narrow_opt = value;
-    else if (!strcmp(name, "tie_sort")) c->tie_sort_opt = value;
-    else if (!strcmp(name, "long_row")) c->long_row_opt = value;
-    else if (!strcmp(name, "item_len")) c->item_opt = value;
-    else if (!strcmp(name, "exchange_at_world_1")) c->force_multi = value > 0;
-    // the lazy loop's two other forms (rows without an edge elementwise instead of one scalar recurrence; q_j stored instead of
-    // the unnormalised u_j) and the staged-columns workgroups' place in the shared launch: all compiled into this library
-    else if (!strcmp(name, "isolated_rows")) c->iso_opt = value;
-    else if (!strcmp(name, "unnormalised_basis")) c->basis_u_opt = value;
-    else if (!strcmp(name, "fuse_staged")) c->fuse_opt = value;
-    // 0: the start vector always crosses PCIe and its norm is always the serial chain (what round 5's look at x0 is compared with)
-    else if (!strcmp(name, "start_vector_scan")) c->x0_scan_opt = value;
-    // 0: the blocked SpMV always launches k_pb_finish (default: the lazy loop's vector kernel stands in for it)
-    else if (!strcmp(name, "defer_finish")) c->defer_opt = value;
-    // entries per chunk of a split row in the batched SpMM (lzx_multi.hip; default LZX_MULTI_CHUNK)
-    else if (!strcmp(name, "multi_row_chunk")) c->multi_chunk_opt = value;
-    // lzx_eigsh_f64 takes a basis of more than this many bytes as out of device memory (its LZX_ERR_NOMEM path on a small graph)
-    else if (!strcmp(name, "eig_basis_bytes")) c->eig_basis_cap_opt = value;
-    // lzx_solve_shifted_f64: a state of more than this many bytes is out of device memory; iterations between its status polls
-    else if (!strcmp(name, "solve_state_bytes")) c->solve_cap_opt = value;
-    else if (!strcmp(name, "solve_poll")) c->solve_poll_opt = value;
-    else LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: unknown shape '%s'", name);
+    const Option *o = find_option(name, OPT_SHAPE);
+    if (!o) LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: unknown shape '%s'", name);
+    store_option(c, *o, value);
     return LZX_OK;
 }
 
@@ -306,14 +314,21 @@ static int sync_all(std::vector<lzx_ctx *> &cs)
     return LZX_OK;
 }
 
+// frees a device buffer and zeroes the count that says how much of it there is
+template <class T>
+static void drop(T *&buf, u32 &count)
+{
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    count = 0;
+}
+
 static int ensure_capacity(lzx_ctx *c, u32 k, bool qf32)
 {
     LZX_HIP(hipSetDevice(c->device));
     if (k > c->k_cap) {
-        if (c->d_alpha) (void)hipFree(c->d_alpha);
-        if (c->d_beta) (void)hipFree(c->d_beta);
-        c->d_alpha = c->d_beta = nullptr;
-        c->k_cap = 0;
+        drop(c->d_alpha, c->k_cap);
+        drop(c->d_beta, c->k_cap);
         LZX_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_alpha), sizeof(double) * k));
         LZX_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_beta), sizeof(double) * k));
         c->k_cap = k;
@@ -321,13 +336,9 @@ static int ensure_capacity(lzx_ctx *c, u32 k, bool qf32)
     if (qf32) {
         // N4: the basis is stored as fp32; the recurrence's three live vectors stay fp64 (d_ring).  The fp64 basis of an
         // earlier decomposition on this handle goes first: the mode's point is half the HBM
-        if (c->d_Q) (void)hipFree(c->d_Q);
-        c->d_Q = nullptr;
-        c->q_cols = 0;
+        drop(c->d_Q, c->q_cols);
         if (k > c->qf_cols) {
-            if (c->d_Qf) (void)hipFree(c->d_Qf);
-            c->d_Qf = nullptr;
-            c->qf_cols = 0;
+            drop(c->d_Qf, c->qf_cols);
             LZX_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_Qf), sizeof(float) * (size_t)k * c->ldq));
             c->qf_cols = k;
         }
@@ -336,17 +347,10 @@ static int ensure_capacity(lzx_ctx *c, u32 k, bool qf32)
         return LZX_OK;
     }
     // ... and the fp32 form's buffers when the handle goes back to the fp64 basis
-    if (c->d_Qf) (void)hipFree(c->d_Qf);
-    c->d_Qf = nullptr;
-    c->qf_cols = 0;
-    for (double *&r : c->d_ring) {
-        if (r) (void)hipFree(r);
-        r = nullptr;
-    }
+    drop(c->d_Qf, c->qf_cols);
+    for (double *&r : c->d_ring) { if (r) (void)hipFree(r); r = nullptr; }
     if (k > c->q_cols) {
-        if (c->d_Q) (void)hipFree(c->d_Q);
-        c->d_Q = nullptr;
-        c->q_cols = 0;
+        drop(c->d_Q, c->q_cols);
         LZX_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_Q), sizeof(double) * (size_t)k * c->ldq));
         c->q_cols = k;
     }
@@ -601,6 +605,301 @@ static int lanczos_prepare(std::vector<lzx_ctx *> &cs, const double *x0, u32 k, 
     return LZX_OK;
 }
 
+// ---- the Lanczos loop: what a call of lanczos_loop fixes once for all its iterations, one step function per form ----
+struct LoopRun {
+    std::vector<lzx_ctx *> &cs;
+    lzx_ctx *c0;
+    u32 k;          // iterations of the prepared decomposition (k_prep)
+    bool multi;     // the vector is exchanged between ranks
+    bool overlap;   // ... in two chunks on the exchange streams, chunk 1 under the SpMV of chunk 0
+    // operator L: after every SpMV, k_lap_apply turns A x into L x and the SpMV's alpha partials into those of L x; the vector
+    // kernels then stop at beta <= 2^-40 * 2 d_max (lzx_stop_threshold)
+    bool lap;
+    double stop;
+    bool mail_ok;   // in-process group: the lazy loop's pair of sums goes through the peers' mailboxes
+    u32 reorth;     // plain loop, R1: every reorth iterations the Arnoldi pass (0: never)
+    // plain loop, option reference_order: the three reductions in serial/'s order (lzx_kernels.hip: k_ref_*).  The scalars then
+    // arrive in d_scal[0 / 1] the way the several-rank loop's all-reduced ones do, and the vector kernels are the same.
+    bool ref;
+    bool scal;      // plain loop: alpha_j / ||v||^2 come as ONE device scalar each instead of block partials
+    u32 np;         // block partials of one SpMV
+    u32 every;      // timing marks on every 4th iteration (every one when k is small); loop_stats scales the sums to all iterations run
+    Marks mk;
+    std::vector<const double *> src;   // exchange_next's per-handle pointers, allocated once per call
+    std::vector<double *> dst;
+
+    LoopRun(std::vector<lzx_ctx *> &h, bool lazy)
+        : cs(h), c0(h[0]), k(c0->k_prep), multi(lzx_exchanges(c0)), overlap(multi && c0->overlap), lap(c0->op_opt == LZX_OP_LAPLACIAN),
+          stop(lzx_stop_threshold(c0)), mail_ok(multi && lzx_comm_mail_usable(h)), reorth((!lazy && c0->reorth_opt > 0) ? (u32)c0->reorth_opt : 0u),
+          ref(!lazy && !multi && c0->ref_order_opt > 0), scal(multi || ref), np(lzx_spmv_partials(c0)),
+          every(c0->marks_every_opt > 0 ? (u32)c0->marks_every_opt : (k >= 8 ? 4u : 1u)), mk{c0}, src(h.size()), dst(h.size()) {}
+};
+
+// the lazy loop's u_j (u_0 = q_0) and where it writes u_{j+1}: a basis column when the resident basis holds u (basis_u),
+// else one of the two alternating work vectors
+static inline double *current_u(const lzx_ctx *c, u32 j) { return j == 0 ? basis_col(c, 0) : (c->basis_u ? basis_col(c, j) : c->d_u[j & 1]); }
+static inline double *next_u(const lzx_ctx *c, u32 j) { return c->basis_u ? basis_col(c, j + 1) : c->d_u[(j + 1) & 1]; }
+
+// Overlapped exchange: chunk 0 of this iteration's vector (the high-degree end of every slice, where the staged hub entries
+// and nearly all gathers are) has to be here; chunk 1 may still be on the wire while the SpMV works on chunk 0.
+static int wait_chunk0(LoopRun &r)
+{
+    for (lzx_ctx *c : r.cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        LZX_HIP(hipStreamWaitEvent(c->stream, c->ev_c0, 0));
+    }
+    return r.mk.tick(CAT_COMM);
+}
+
+// The exchange of the next iteration's vector, r.src[i] on handle i, into every handle's d_xbuf: only the prefix of every
+// slice that has edges (xs).
+static int exchange_next(LoopRun &r)
+{
+    std::vector<lzx_ctx *> &cs = r.cs;
+    lzx_ctx *c0 = r.c0;
+    for (size_t i = 0; i < cs.size(); ++i) r.dst[i] = cs[i]->d_xbuf;
+    if (!r.overlap) {
+        if (c0->xfp32) LZX_TRY(lzx_comm_allgather_fp32(cs, r.src.data(), true));   // N4: the same prefix, rounded to fp32 on the wire
+        else LZX_TRY(lzx_comm_allgather(cs, r.src.data(), r.dst.data(), c0->xs, false, true));
+        LZX_HIP(hipSetDevice(c0->device));
+        return r.mk.tick(CAT_COMM);
+    }
+    // exchange streams: both chunks back to back, an event after each.  They start once every handle's vector kernel is
+    // done (which also means every SpMV that read the previous x is done).
+    LZX_TRY(lzx_comm_order(cs, /*from main*/ false, /*to exchange*/ true));
+    LZX_TRY(lzx_comm_allgather(cs, r.src.data(), r.dst.data(), c0->xs0, true, true));
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        LZX_HIP(hipEventRecord(c->ev_c0, c->stream2));
+    }
+    if (c0->sparse) {   // every peer gets only what its rows reference
+        LZX_TRY(lzx_comm_sparse_chunk1(cs, r.src.data(), true));
+    } else {
+        for (size_t i = 0; i < cs.size(); ++i) {
+            r.src[i] += cs[i]->xs0;
+            r.dst[i] += (size_t)cs[i]->world * cs[i]->xs0;
+        }
+        LZX_TRY(lzx_comm_allgather(cs, r.src.data(), r.dst.data(), c0->xs - c0->xs0, true, true));
+    }
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        LZX_HIP(hipEventRecord(c->ev_c1, c->stream2));
+    }
+    return LZX_OK;
+}
+
+// One iteration of the lazy loop.  Several ranks: exchange and multiply the UNNORMALISED vector u_j = beta_{j-1} q_j, so that
+// beta_{j-1}^2 = ||u_j||^2 travels in the same all-reduce as u_j . (A u_j) (k_lazy_update): one 2-double all-reduce per
+// iteration instead of two dependent 1-double ones, and the exchange of u_{j+1} starts straight after the vector kernel
+// instead of after a second reduction.  Same recurrence, operands rounded at slightly different places (w / beta instead of
+// A (u / beta)).  One rank in blocked mode (whose sums are already ordered differently from the reference's) takes the same
+// form: it saves k_scale's pass over v and a launch; in plain mode one rank keeps the reference's order bit for bit (plain_step).
+static int lazy_step(LoopRun &r, u32 j)
+{
+    std::vector<lzx_ctx *> &cs = r.cs;
+    lzx_ctx *c0 = r.c0;
+    const bool multi = r.multi, first = j == 0, last = j == r.k - 1;
+    LZX_TRY(r.mk.begin_iteration(j, r.every));
+    if (r.overlap && j > 0) LZX_TRY(wait_chunk0(r));
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        const double *uj = current_u(c, j);
+        SpmvLaunch l{multi ? c->d_xbuf : uj, uj, c->d_v, c->d_partials};
+        l.live_rows_only = true;   // k_lazy_update below takes (A u)_i = 0 for rows without an edge
+        if (r.overlap && j > 0) l.chunk1_ready = c->ev_c1;
+        LZX_TRY(lzx_launch_spmv(c, l));
+        // operator L: w = d .* u_j - w over the rows with an edge, and D = u_j . (L u_j) in the SpMV's partials
+        if (r.lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, uj, c->d_partials, lzx_spmv_partials(c), c->rows_live));
+    }
+    LZX_TRY(r.mk.tick(CAT_SPMV));
+    u32 np2 = 0;
+    const bool mail = r.mail_ok;
+    if (mail) {
+        // in-process group: each rank's pair goes straight into every peer's mailbox (one barrier, no copies)
+        LZX_TRY(lzx_comm_mail_reduce2(cs, j & 1u, first));
+    } else if (multi && lzx_comm_fused_reduce2(c0)) {
+        // peer windows: the rank's two sums are closed and all-reduced by one single-workgroup launch
+        LZX_TRY(lzx_comm_reduce2_allreduce(c0, c0->d_partials, lzx_spmv_partials(c0), c0->d_partials2, first ? 0 : c0->np2_last));
+    } else if (multi) {
+        for (lzx_ctx *c : cs) {
+            LZX_HIP(hipSetDevice(c->device));
+            // [u_j . w, ||u_j||^2] of this rank (the second from the previous iteration's k_lazy_update)
+            LZX_TRY(lzx_launch_reduce2(c, c->d_partials, lzx_spmv_partials(c), c->d_partials2, first ? 0 : c->np2_last, c->d_scal + 0));
+        }
+        LZX_TRY(lzx_comm_allreduce_sum(cs, 0, 2));
+    }
+    // (no timing mark here: every mark is a barrier packet, ~5 us of drained pipeline between dependent kernels;
+    //  the reduction and its all-reduce are billed to the vector work, the exposed part of the all-gather to comm)
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        const double *uj = current_u(c, j);
+        // the resident basis holds u_j (basis_u): nothing normalised is stored, the previous column is divided by
+        // beta_{j-2} on the way in, the next one written in place
+        double *q_store = (first || c->basis_u) ? nullptr : basis_col(c, j);
+        double *u_store = last ? nullptr : next_u(c, j);
+        float *f_store = (c->qf32 && u_store) ? c->d_Qf + (size_t)(j + 1) * c->ldq : nullptr;   // N4: the column as it is stored
+        const double *pdiv = (c->basis_u && j >= 2) ? c->d_beta + (j - 2) : nullptr;
+        // one rank: both sums are closed in the kernel's prologue from the partials themselves (no reduce launch);
+        // the norm partials alternate between two arrays, the kernel reads one while writing the other
+        double *p_out = multi ? c->d_partials2 : ((j & 1) ? c->d_partials3 : c->d_partials2);
+        const double *p_in = multi ? nullptr : ((j & 1) ? c->d_partials2 : c->d_partials3);
+        if (!multi)
+            LZX_TRY(lzx_launch_lazy_update_local(c, c->d_v, c->rows_live, uj, first ? nullptr : basis_col(c, j - 1), c->d_partials,
+                                                 lzx_spmv_partials(c), p_in, first ? 0 : c->np2_last, first ? 1 : 0, c->d_alpha + j,
+                                                 first ? nullptr : c->d_beta + (j - 1), q_store, u_store, p_out, &np2, pdiv, f_store));
+        else
+            LZX_TRY(lzx_launch_lazy_update(c, c->d_v, c->rows_live, uj, first ? nullptr : basis_col(c, j - 1),
+                                           mail ? c->d_mail + (size_t)(j & 1u) * 64 * 2 : c->d_scal + 0, first ? 1 : 0,
+                                           c->d_alpha + j, first ? nullptr : c->d_beta + (j - 1), q_store, u_store, c->d_partials2, &np2, pdiv, f_store,
+                                           mail ? (u32)cs.size() : 0u));
+        c->np2_last = np2;
+    }
+    LZX_TRY(r.mk.tick(CAT_VEC));
+    if (last || !multi) return LZX_OK;
+    for (size_t i = 0; i < cs.size(); ++i) r.src[i] = next_u(cs[i], j);
+    return exchange_next(r);
+}
+
+// R1: the Arnoldi pass of serial/lib/lanczos.cc:85-90 -- A q_j against q_0 .. q_{j-2}, modified Gram-Schmidt in the
+// reference's order (every inner product over the v the previous update left), as a chain of j launches: the
+// first forms <v, q_0>, launch t applies vector t - 1 and forms the next inner product, the last one's is
+// <v, q_j>: the alpha_j partials, which replace those the SpMV formed before the pass.  The partial buffers
+// alternate so that the last launch writes d_partials3 (k_axpy_norm writes d_partials2 while reading them).
+// *np_re: how many partials that last launch wrote.
+static int arnoldi_pass(LoopRun &r, u32 j, u32 *np_re)
+{
+    std::vector<lzx_ctx *> &cs = r.cs;
+    const bool multi = r.multi, ref = r.ref, scal = r.scal;
+    for (u32 t = 0; t < j; ++t) {
+        for (lzx_ctx *c : cs) {
+            LZX_HIP(hipSetDevice(c->device));
+            double *out = ((j - 1 - t) & 1) ? c->d_partials2 : c->d_partials3;
+            const double *in = ((j - 1 - t) & 1) ? c->d_partials3 : c->d_partials2;
+            const double *qm = t == 0 ? nullptr : c->d_Q + (size_t)(t - 1) * c->ldq;
+            const double *qn = c->d_Q + (size_t)(t + 1 < j ? t : j) * c->ldq;
+            u32 npo = 0;
+            LZX_TRY(lzx_launch_mgs_step(c, c->d_v, qm, scal ? nullptr : in, scal ? 0u : *np_re, scal ? c->d_scal + 2 : nullptr, qn, out, &npo));
+            if (multi) LZX_TRY(lzx_launch_reduce(c, out, npo, c->d_scal + (t + 1 < j ? 2 : 0), 0));
+            // reference_order: the inner product over the updated v, left to right (serial/lib/lanczos.cc:86-90, 163-171)
+            if (ref) LZX_TRY(lzx_launch_ref_dot(c, c->d_v, qn, c->d_scal + (t + 1 < j ? 2 : 0)));
+            if (c == cs.back()) *np_re = npo;
+        }
+        if (multi) LZX_TRY(lzx_comm_allreduce_sum(cs, t + 1 < j ? 2 : 0));
+    }
+    return r.mk.tick(CAT_VEC);
+}
+
+// One iteration of the plain loop: the reference's operation order on the normalised basis (one rank in plain mode: bit for bit).
+static int plain_step(LoopRun &r, u32 j)
+{
+    std::vector<lzx_ctx *> &cs = r.cs;
+    const bool multi = r.multi, ref = r.ref, scal = r.scal, lap = r.lap;
+    LZX_TRY(r.mk.begin_iteration(j, r.every));
+    // v = A q_j ; partials of alpha_j
+    if (r.overlap && j > 0) LZX_TRY(wait_chunk0(r));
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        const double *qj = c->d_Q + (size_t)j * c->ldq;
+        if (ref) {
+            LZX_TRY(lzx_launch_ref_spmv(c, qj, c->d_v));
+            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, nullptr, 0, c->n_loc_pad));   // (alpha: k_ref_dot below)
+            LZX_TRY(lzx_launch_ref_dot(c, c->d_v, qj, c->d_scal + 0));   // alpha_j = <v, q_j>, left to right
+            continue;
+        }
+        SpmvLaunch l{multi ? c->d_xbuf : qj, qj, c->d_v, c->d_partials};
+        if (r.overlap && j > 0) l.chunk1_ready = c->ev_c1;
+        LZX_TRY(lzx_launch_spmv(c, l));
+        // operator L: v = d .* q_j - v; the alpha_j partials are formed again, on L q_j
+        if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, c->d_partials, lzx_spmv_partials(c), c->n_loc_pad));
+    }
+    LZX_TRY(r.mk.tick(CAT_SPMV));
+
+    const bool re = r.reorth && j % r.reorth == 0 && j > 2;
+    u32 np_re = 0;
+    if (re) LZX_TRY(arnoldi_pass(r, j, &np_re));
+
+    if (multi && !re) {
+        for (lzx_ctx *c : cs) {
+            LZX_HIP(hipSetDevice(c->device));
+            LZX_TRY(lzx_launch_reduce(c, c->d_partials, lzx_spmv_partials(c), c->d_scal + 0, 0));
+        }
+        LZX_TRY(lzx_comm_allreduce_sum(cs, 0));
+        LZX_TRY(r.mk.tick(CAT_COMM));
+    }
+
+    if (j == r.k - 1) {
+        // last step: only alpha_{k-1} is an output (the reference also updates v, then drops it)
+        for (lzx_ctx *c : cs) {
+            LZX_HIP(hipSetDevice(c->device));
+            if (scal) LZX_HIP(hipMemcpyAsync(c->d_alpha + j, c->d_scal + 0, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            else LZX_TRY(lzx_launch_reduce(c, re ? c->d_partials3 : c->d_partials, re ? np_re : r.np, c->d_alpha + j, 0));
+        }
+        return r.mk.tick(CAT_VEC);
+    }
+
+    u32 np2 = 0;
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        const double *qj = c->d_Q + (size_t)j * c->ldq;
+        const double *qjm1 = j > 0 ? c->d_Q + (size_t)(j - 1) * c->ldq : nullptr;
+        LZX_TRY(lzx_launch_axpy_norm(c, c->d_v, qj, qjm1, scal ? c->d_scal + 0 : (re ? c->d_partials3 : c->d_partials),
+                                     scal ? 1 : (re ? np_re : lzx_spmv_partials(c)), c->d_alpha + j,
+                                     j > 0 ? c->d_beta + (j - 1) : nullptr, c->d_partials2, &np2));
+        if (ref) LZX_TRY(lzx_launch_ref_dot(c, c->d_v, c->d_v, c->d_scal + 1));   // ||v||^2, left to right (k_scale takes the root)
+    }
+    if (multi) LZX_TRY(r.mk.tick(CAT_VEC));   // one rank: a single mark after k_scale covers both vector kernels
+
+    if (multi) {
+        for (lzx_ctx *c : cs) {
+            LZX_HIP(hipSetDevice(c->device));
+            LZX_TRY(lzx_launch_reduce(c, c->d_partials2, np2, c->d_scal + 1, 0));
+        }
+        LZX_TRY(lzx_comm_allreduce_sum(cs, 1));
+        LZX_TRY(r.mk.tick(CAT_COMM));
+    }
+
+    for (lzx_ctx *c : cs) {
+        LZX_HIP(hipSetDevice(c->device));
+        LZX_TRY(lzx_launch_scale(c, c->d_v, c->d_Q + (size_t)(j + 1) * c->ldq,
+                                 scal ? c->d_scal + 1 : c->d_partials2, scal ? 1 : np2, c->d_beta + j, r.stop));
+    }
+    LZX_TRY(r.mk.tick(CAT_VEC));
+    if (!multi) return LZX_OK;
+    for (size_t i = 0; i < cs.size(); ++i) r.src[i] = cs[i]->d_Q + (size_t)(j + 1) * cs[i]->ldq;
+    return exchange_next(r);
+}
+
+// What a call's `ran` iterations cost: wall time, and the intervals between the timing marks by category.
+static int loop_stats(const LoopRun &r, u32 ran, double loop_ms, lzx_stats *stats)
+{
+    const lzx_ctx *c0 = r.c0;
+    const Marks &mk = r.mk;
+    memset(stats, 0, sizeof *stats);
+    stats->loop_ms = loop_ms;
+    stats->iters = ran;
+    stats->spmv_kernels = c0->pb ? 3 + (c0->pb_finish_grid && !(c0->pb_deferring && c0->pb_defer_ok) ? 1 : 0) : 1 + (c0->fin_grid > 0 ? 1 : 0);
+    stats->spmv_bytes = spmv_algorithmic_bytes(c0);
+    stats->spmv_ms_min = 1e300;
+    for (size_t i = 1; i < mk.used; ++i) {
+        float ms = 0.f;
+        LZX_HIP(hipEventElapsedTime(&ms, c0->ev_pool[i - 1], c0->ev_pool[i]));
+        switch (mk.cat[i]) {
+            case CAT_SPMV: stats->spmv_ms += ms; if (ms < stats->spmv_ms_min) stats->spmv_ms_min = ms; break;
+            case CAT_VEC: stats->vec_ms += ms; break;
+            case CAT_COMM: stats->comm_ms += ms; break;
+            default: break;
+        }
+    }
+    if (stats->spmv_ms_min == 1e300) stats->spmv_ms_min = 0.0;
+    if (mk.sampled > 0 && mk.sampled < ran) {   // marks were carried by `sampled` of the iterations: scale the sums
+        const double f = (double)ran / (double)mk.sampled;
+        stats->spmv_ms *= f;
+        stats->vec_ms *= f;
+        stats->comm_ms *= f;
+    }
+    return LZX_OK;
+}
+
 // Iterations [k_done, min(k_prep, k_done + steps)) of the prepared decomposition, on the vectors lanczos_prepare (or the
 // previous call) left in HBM.  Everything an iteration needs from its predecessor lives on the device -- basis columns,
 // alpha / beta, the norm partials, the exchanged vector and its events -- so a decomposition can be advanced in chunks
@@ -615,27 +914,13 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
             LZX_FAIL(LZX_ERR_STATE, "lzx_lanczos_run: no prepared start vector (prepare, then run, with no SpMV / benchmark call on the handle between them)");
     const u32 j0 = c0->k_done;
     const u32 j1 = (u32)std::min<u64>(k, (u64)j0 + steps);
-    const bool multi = lzx_exchanges(c0);
     LZX_TRY(sync_all(cs));
 
-    Marks mk{c0};
+    const bool lazy = loop_is_lazy(c0);
+    LoopRun run(cs, lazy);
     LZX_HIP(hipSetDevice(c0->device));
     const auto t0 = std::chrono::steady_clock::now();
-    LZX_TRY(mk.tick(CAT_NONE));
-
-    std::vector<const double *> src(cs.size());
-    std::vector<double *> dst(cs.size());
-    const u32 np = lzx_spmv_partials(c0);
-
-    const bool overlap = multi && c0->overlap;
-    // Several ranks: exchange and multiply the UNNORMALISED vector u_j = beta_{j-1} q_j, so that beta_{j-1}^2 =
-    // ||u_j||^2 travels in the same all-reduce as u_j . (A u_j) (k_lazy_update): one 2-double all-reduce per
-    // iteration instead of two dependent 1-double ones, and the exchange of u_{j+1} starts straight after the vector
-    // kernel instead of after a second reduction.  Same recurrence, operands rounded at slightly different places
-    // (w / beta instead of A (u / beta)); one rank keeps the reference's exact operation order below.
-    // One rank in blocked mode (whose sums are already ordered differently from the reference's) takes the same form:
-    // it saves k_scale's pass over v and a launch; in plain mode one rank keeps the reference's order bit for bit.
-    const bool lazy = loop_is_lazy(c0);
+    LZX_TRY(run.mk.tick(CAT_NONE));
     // the lazy loop's vector kernel completes v for the rows of multi-item gather bands itself, so the blocked SpMV leaves its
     // k_pb_finish launch out (lzx_ctx::pb_deferring; test shape defer_finish = 0 keeps the launch); every other consumer of v gets it
     struct Deferring {
@@ -643,300 +928,14 @@ static int lanczos_loop(std::vector<lzx_ctx *> &cs, u32 steps, lzx_stats *stats)
         Deferring(std::vector<lzx_ctx *> &h, bool on) : cs(h) { for (lzx_ctx *c : cs) c->pb_deferring = on && c->defer_opt != 0; }
         ~Deferring() { for (lzx_ctx *c : cs) c->pb_deferring = false; }
     } deferring(cs, lazy && c0->op_opt != LZX_OP_LAPLACIAN);   // operator L: v is complete before k_lap_apply reads it
-    const bool mail_ok = multi && lzx_comm_mail_usable(cs);
-    // timing marks on every 4th iteration (every one when k is small); the sums below are scaled to all iterations run
-    const u32 every = c0->marks_every_opt > 0 ? (u32)c0->marks_every_opt : (k >= 8 ? 4u : 1u);
-    // operator L: after every SpMV, k_lap_apply turns A x into L x and the SpMV's alpha partials into those of L x; the vector
-    // kernels then stop at beta <= 2^-40 * 2 d_max (lzx_stop_threshold)
-    const bool lap = c0->op_opt == LZX_OP_LAPLACIAN;
-    const double stop = lzx_stop_threshold(c0);
-    for (u32 j = j0; lazy && j < j1; ++j) {
-        const bool first = j == 0, last = j == k - 1;
-        LZX_TRY(mk.begin_iteration(j, every));
-        if (overlap && j > 0) {
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipStreamWaitEvent(c->stream, c->ev_c0, 0));
-            }
-            LZX_TRY(mk.tick(CAT_COMM));
-        }
-        for (lzx_ctx *c : cs) {
-            LZX_HIP(hipSetDevice(c->device));
-            const double *uj = first ? basis_col(c, 0) : (c->basis_u ? basis_col(c, j) : c->d_u[j & 1]);   // u_0 = q_0
-            SpmvLaunch l{multi ? c->d_xbuf : uj, uj, c->d_v, c->d_partials};
-            l.live_rows_only = true;   // k_lazy_update below takes (A u)_i = 0 for rows without an edge
-            if (overlap && j > 0) l.chunk1_ready = c->ev_c1;
-            LZX_TRY(lzx_launch_spmv(c, l));
-            // operator L: w = d .* u_j - w over the rows with an edge, and D = u_j . (L u_j) in the SpMV's partials
-            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, uj, c->d_partials, lzx_spmv_partials(c), c->rows_live));
-        }
-        LZX_TRY(mk.tick(CAT_SPMV));
-        u32 np2 = 0;
-        const bool mail = multi && mail_ok;
-        if (mail) {
-            // in-process group: each rank's pair goes straight into every peer's mailbox (one barrier, no copies)
-            LZX_TRY(lzx_comm_mail_reduce2(cs, j & 1u, first));
-        } else if (multi && lzx_comm_fused_reduce2(c0)) {
-            // peer windows: the rank's two sums are closed and all-reduced by one single-workgroup launch
-            LZX_TRY(lzx_comm_reduce2_allreduce(c0, c0->d_partials, lzx_spmv_partials(c0), c0->d_partials2, first ? 0 : c0->np2_last));
-        } else if (multi) {
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                // [u_j . w, ||u_j||^2] of this rank (the second from the previous iteration's k_lazy_update)
-                LZX_TRY(lzx_launch_reduce2(c, c->d_partials, lzx_spmv_partials(c), c->d_partials2, first ? 0 : c->np2_last, c->d_scal + 0));
-            }
-            LZX_TRY(lzx_comm_allreduce_sum(cs, 0, 2));
-        }
-        // (no timing mark here: every mark is a barrier packet, ~5 us of drained pipeline between dependent kernels;
-        //  the reduction and its all-reduce are billed to the vector work, the exposed part of the all-gather to comm)
-        for (lzx_ctx *c : cs) {
-            LZX_HIP(hipSetDevice(c->device));
-            const double *uj = first ? basis_col(c, 0) : (c->basis_u ? basis_col(c, j) : c->d_u[j & 1]);
-            // the resident basis holds u_j (basis_u): nothing normalised is stored, the previous column is divided by
-            // beta_{j-2} on the way in, the next one written in place
-            double *q_store = (first || c->basis_u) ? nullptr : basis_col(c, j);
-            double *u_store = last ? nullptr : (c->basis_u ? basis_col(c, j + 1) : c->d_u[(j + 1) & 1]);
-            float *f_store = (c->qf32 && u_store) ? c->d_Qf + (size_t)(j + 1) * c->ldq : nullptr;   // N4: the column as it is stored
-            const double *pdiv = (c->basis_u && j >= 2) ? c->d_beta + (j - 2) : nullptr;
-            // one rank: both sums are closed in the kernel's prologue from the partials themselves (no reduce launch);
-            // the norm partials alternate between two arrays, the kernel reads one while writing the other
-            double *p_out = multi ? c->d_partials2 : ((j & 1) ? c->d_partials3 : c->d_partials2);
-            const double *p_in = multi ? nullptr : ((j & 1) ? c->d_partials2 : c->d_partials3);
-            if (!multi)
-                LZX_TRY(lzx_launch_lazy_update_local(c, c->d_v, c->rows_live, uj, first ? nullptr : basis_col(c, j - 1), c->d_partials,
-                                                     lzx_spmv_partials(c), p_in, first ? 0 : c->np2_last, first ? 1 : 0, c->d_alpha + j,
-                                                     first ? nullptr : c->d_beta + (j - 1), q_store, u_store, p_out, &np2, pdiv, f_store));
-            else
-            LZX_TRY(lzx_launch_lazy_update(c, c->d_v, c->rows_live, uj, first ? nullptr : basis_col(c, j - 1),
-                                           mail ? c->d_mail + (size_t)(j & 1u) * 64 * 2 : c->d_scal + 0, first ? 1 : 0,
-                                           c->d_alpha + j, first ? nullptr : c->d_beta + (j - 1), q_store, u_store, c->d_partials2, &np2, pdiv, f_store,
-                                           mail ? (u32)cs.size() : 0u));
-            c->np2_last = np2;
-        }
-        LZX_TRY(mk.tick(CAT_VEC));
-        if (last || !multi) {
-            if (last) break;
-            continue;
-        }
-        auto next_u = [&](lzx_ctx *c) -> const double * {
-            return c->basis_u ? basis_col(c, j + 1) : c->d_u[(j + 1) & 1];
-        };
-        for (size_t i = 0; i < cs.size(); ++i) {
-            src[i] = next_u(cs[i]);
-            dst[i] = cs[i]->d_xbuf;
-        }
-        if (!overlap) {
-            if (c0->xfp32) LZX_TRY(lzx_comm_allgather_fp32(cs, src.data(), true));   // N4: the same prefix, rounded to fp32 on the wire
-            else
-            LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs, false, true));   // only the prefix that has edges
-            LZX_HIP(hipSetDevice(c0->device));
-            LZX_TRY(mk.tick(CAT_COMM));
-        } else {
-            LZX_TRY(lzx_comm_order(cs, /*from main*/ false, /*to exchange*/ true));
-            LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs0, true, true));
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipEventRecord(c->ev_c0, c->stream2));
-            }
-            if (c0->sparse) {   // every peer gets only what its rows reference
-                for (size_t i = 0; i < cs.size(); ++i) src[i] = next_u(cs[i]);
-                LZX_TRY(lzx_comm_sparse_chunk1(cs, src.data(), true));
-            } else {
-                for (size_t i = 0; i < cs.size(); ++i) {
-                    src[i] = next_u(cs[i]) + cs[i]->xs0;
-                    dst[i] = cs[i]->d_xbuf + (size_t)cs[i]->world * cs[i]->xs0;
-                }
-                LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs - c0->xs0, true, true));
-            }
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipEventRecord(c->ev_c1, c->stream2));
-            }
-        }
-    }
-    const u32 reorth = (!lazy && c0->reorth_opt > 0) ? (u32)c0->reorth_opt : 0u;
-    // Option reference_order: the three reductions in serial/'s order (lzx_kernels.hip: k_ref_*).  The scalars then
-    // arrive in d_scal[0 / 1] the way the several-rank loop's all-reduced ones do, and the vector kernels are the same.
-    const bool ref = !lazy && !multi && c0->ref_order_opt > 0;
-    const bool scal = multi || ref;   // alpha_j / ||v||^2 come as ONE device scalar each instead of block partials
-    for (u32 j = j0; !lazy && j < j1; ++j) {
-        LZX_TRY(mk.begin_iteration(j, every));
-        // v = A q_j ; partials of alpha_j
-        if (overlap && j > 0) {
-            // chunk 0 of q_j (the high-degree end of every slice, where the staged hub entries and nearly all
-            // gathers are) has to be here; chunk 1 may still be on the wire while the SpMV works on chunk 0
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipStreamWaitEvent(c->stream, c->ev_c0, 0));
-            }
-            LZX_TRY(mk.tick(CAT_COMM));
-        }
-        for (lzx_ctx *c : cs) {
-            LZX_HIP(hipSetDevice(c->device));
-            const double *qj = c->d_Q + (size_t)j * c->ldq;
-            if (ref) {
-                LZX_TRY(lzx_launch_ref_spmv(c, qj, c->d_v));
-                if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, nullptr, 0, c->n_loc_pad));   // (alpha: k_ref_dot below)
-                LZX_TRY(lzx_launch_ref_dot(c, c->d_v, qj, c->d_scal + 0));   // alpha_j = <v, q_j>, left to right
-                continue;
-            }
-            SpmvLaunch l{multi ? c->d_xbuf : qj, qj, c->d_v, c->d_partials};
-            if (overlap && j > 0) l.chunk1_ready = c->ev_c1;
-            LZX_TRY(lzx_launch_spmv(c, l));
-            // operator L: v = d .* q_j - v; the alpha_j partials are formed again, on L q_j
-            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, qj, c->d_partials, lzx_spmv_partials(c), c->n_loc_pad));
-        }
-        LZX_TRY(mk.tick(CAT_SPMV));
-
-        // R1: the Arnoldi pass of serial/lib/lanczos.cc:85-90 -- A q_j against q_0 .. q_{j-2}, modified Gram-Schmidt in the
-        // reference's order (every inner product over the v the previous update left), as a chain of j launches: the
-        // first forms <v, q_0>, launch t applies vector t - 1 and forms the next inner product, the last one's is
-        // <v, q_j>: the alpha_j partials, which replace those the SpMV formed before the pass.  The partial buffers
-        // alternate so that the last launch writes d_partials3 (k_axpy_norm writes d_partials2 while reading them).
-        const bool re = reorth && j % reorth == 0 && j > 2;
-        u32 np_re = 0;
-        if (re) {
-            for (u32 t = 0; t < j; ++t) {
-                for (lzx_ctx *c : cs) {
-                    LZX_HIP(hipSetDevice(c->device));
-                    double *out = ((j - 1 - t) & 1) ? c->d_partials2 : c->d_partials3;
-                    const double *in = ((j - 1 - t) & 1) ? c->d_partials3 : c->d_partials2;
-                    const double *qm = t == 0 ? nullptr : c->d_Q + (size_t)(t - 1) * c->ldq;
-                    const double *qn = c->d_Q + (size_t)(t + 1 < j ? t : j) * c->ldq;
-                    u32 npo = 0;
-                    LZX_TRY(lzx_launch_mgs_step(c, c->d_v, qm, scal ? nullptr : in, scal ? 0u : np_re, scal ? c->d_scal + 2 : nullptr, qn, out, &npo));
-                    if (multi) LZX_TRY(lzx_launch_reduce(c, out, npo, c->d_scal + (t + 1 < j ? 2 : 0), 0));
-                    // reference_order: the inner product over the updated v, left to right (serial/lib/lanczos.cc:86-90, 163-171)
-                    if (ref) LZX_TRY(lzx_launch_ref_dot(c, c->d_v, qn, c->d_scal + (t + 1 < j ? 2 : 0)));
-                    if (c == cs.back()) np_re = npo;
-                }
-                if (multi) LZX_TRY(lzx_comm_allreduce_sum(cs, t + 1 < j ? 2 : 0));
-            }
-            LZX_TRY(mk.tick(CAT_VEC));
-        }
-
-        if (multi && !re) {
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_TRY(lzx_launch_reduce(c, c->d_partials, lzx_spmv_partials(c), c->d_scal + 0, 0));
-            }
-            LZX_TRY(lzx_comm_allreduce_sum(cs, 0));
-            LZX_TRY(mk.tick(CAT_COMM));
-        }
-
-        if (j == k - 1) {
-            // last step: only alpha_{k-1} is an output (the reference also updates v, then drops it)
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                if (scal) LZX_HIP(hipMemcpyAsync(c->d_alpha + j, c->d_scal + 0, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                else LZX_TRY(lzx_launch_reduce(c, re ? c->d_partials3 : c->d_partials, re ? np_re : np, c->d_alpha + j, 0));
-            }
-            LZX_TRY(mk.tick(CAT_VEC));
-            break;
-        }
-
-        u32 np2 = 0;
-        for (lzx_ctx *c : cs) {
-            LZX_HIP(hipSetDevice(c->device));
-            const double *qj = c->d_Q + (size_t)j * c->ldq;
-            const double *qjm1 = j > 0 ? c->d_Q + (size_t)(j - 1) * c->ldq : nullptr;
-            LZX_TRY(lzx_launch_axpy_norm(c, c->d_v, qj, qjm1, scal ? c->d_scal + 0 : (re ? c->d_partials3 : c->d_partials),
-                                         scal ? 1 : (re ? np_re : lzx_spmv_partials(c)), c->d_alpha + j,
-                                         j > 0 ? c->d_beta + (j - 1) : nullptr, c->d_partials2, &np2));
-            if (ref) LZX_TRY(lzx_launch_ref_dot(c, c->d_v, c->d_v, c->d_scal + 1));   // ||v||^2, left to right (k_scale takes the root)
-        }
-        if (multi) LZX_TRY(mk.tick(CAT_VEC));   // one rank: a single mark after k_scale covers both vector kernels
-
-        if (multi) {
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_TRY(lzx_launch_reduce(c, c->d_partials2, np2, c->d_scal + 1, 0));
-            }
-            LZX_TRY(lzx_comm_allreduce_sum(cs, 1));
-            LZX_TRY(mk.tick(CAT_COMM));
-        }
-
-        for (lzx_ctx *c : cs) {
-            LZX_HIP(hipSetDevice(c->device));
-            LZX_TRY(lzx_launch_scale(c, c->d_v, c->d_Q + (size_t)(j + 1) * c->ldq,
-                                     scal ? c->d_scal + 1 : c->d_partials2, scal ? 1 : np2, c->d_beta + j, stop));
-        }
-        LZX_TRY(mk.tick(CAT_VEC));
-
-        if (multi && !overlap) {
-            for (size_t i = 0; i < cs.size(); ++i) {
-                src[i] = cs[i]->d_Q + (size_t)(j + 1) * cs[i]->ldq;
-                dst[i] = cs[i]->d_xbuf;
-            }
-            if (c0->xfp32) LZX_TRY(lzx_comm_allgather_fp32(cs, src.data(), true));
-            else
-            LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs, false, true));   // only the prefix that has edges
-            LZX_HIP(hipSetDevice(c0->device));
-            LZX_TRY(mk.tick(CAT_COMM));
-        }
-        if (overlap) {
-            // exchange streams: both chunks of q_{j+1} back to back, an event after each.  They start once every
-            // handle's k_scale is done (which also means every SpMV that read the previous x is done).
-            LZX_TRY(lzx_comm_order(cs, /*from main*/ false, /*to exchange*/ true));
-            for (size_t i = 0; i < cs.size(); ++i) {
-                src[i] = cs[i]->d_Q + (size_t)(j + 1) * cs[i]->ldq;
-                dst[i] = cs[i]->d_xbuf;
-            }
-            LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs0, true, true));
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipEventRecord(c->ev_c0, c->stream2));
-            }
-            if (c0->sparse) {
-                for (size_t i = 0; i < cs.size(); ++i) src[i] = cs[i]->d_Q + (size_t)(j + 1) * cs[i]->ldq;
-                LZX_TRY(lzx_comm_sparse_chunk1(cs, src.data(), true));
-            } else {
-                for (size_t i = 0; i < cs.size(); ++i) {
-                    src[i] = cs[i]->d_Q + (size_t)(j + 1) * cs[i]->ldq + cs[i]->xs0;
-                    dst[i] = cs[i]->d_xbuf + (size_t)cs[i]->world * cs[i]->xs0;
-                }
-                LZX_TRY(lzx_comm_allgather(cs, src.data(), dst.data(), c0->xs - c0->xs0, true, true));
-            }
-            for (lzx_ctx *c : cs) {
-                LZX_HIP(hipSetDevice(c->device));
-                LZX_HIP(hipEventRecord(c->ev_c1, c->stream2));
-            }
-        }
-    }
-    mk.on = true;
+    for (u32 j = j0; j < j1; ++j) LZX_TRY(lazy ? lazy_step(run, j) : plain_step(run, j));
     LZX_TRY(sync_all(cs));
     const auto t1 = std::chrono::steady_clock::now();
     for (lzx_ctx *c : cs) {
         c->k_done = c->k_last = j1;
         if (j1 == k) c->k_prep = 0;   // complete: nothing left to resume
     }
-
-    if (stats) {
-        const u32 ran = j1 - j0;
-        memset(stats, 0, sizeof *stats);
-        stats->loop_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        stats->iters = ran;
-        stats->spmv_kernels = c0->pb ? 3 + (c0->pb_finish_grid && !(c0->pb_deferring && c0->pb_defer_ok) ? 1 : 0) : 1 + (c0->fin_grid > 0 ? 1 : 0);
-        stats->spmv_bytes = spmv_algorithmic_bytes(c0);
-        stats->spmv_ms_min = 1e300;
-        for (size_t i = 1; i < mk.used; ++i) {
-            float ms = 0.f;
-            LZX_HIP(hipEventElapsedTime(&ms, c0->ev_pool[i - 1], c0->ev_pool[i]));
-            switch (mk.cat[i]) {
-                case CAT_SPMV: stats->spmv_ms += ms; if (ms < stats->spmv_ms_min) stats->spmv_ms_min = ms; break;
-                case CAT_VEC: stats->vec_ms += ms; break;
-                case CAT_COMM: stats->comm_ms += ms; break;
-                default: break;
-            }
-        }
-        if (stats->spmv_ms_min == 1e300) stats->spmv_ms_min = 0.0;
-        if (mk.sampled > 0 && mk.sampled < ran) {   // marks were carried by `sampled` of the iterations: scale the sums
-            const double f = (double)ran / (double)mk.sampled;
-            stats->spmv_ms *= f;
-            stats->vec_ms *= f;
-            stats->comm_ms *= f;
-        }
-    }
+    if (stats) LZX_TRY(loop_stats(run, j1 - j0, std::chrono::duration<double, std::milli>(t1 - t0).count(), stats));
     return LZX_OK;
 }
 
