@@ -373,6 +373,46 @@ typedef struct lzx_solve_info {
 int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns, const double *shifts, double tol, uint32_t maxiter,
                           const double *W, uint32_t nw, double *X, uint32_t *iters, double *resid, lzx_solve_info *info);
 
+/* ---- PageRank: multi-shift conjugate gradients in the degree inner product -----------------------------
+ * PageRank and personalised PageRank of the handle's (undirected) graph for nd <= 16 damping factors from ONE Krylov sequence,
+ * on the device.  With d_i the stored entries of row i (the degree of option "operator" = LZX_OP_LAPLACIAN: a self loop counts
+ * once), w_i = max(d_i, 1) and W = diag(w): PageRank with damping delta, teleport vector v (v >= 0, scaled to sum 1) and the
+ * dangling mass returned to v -- networkx's default -- is x = y / sum(y) with (I - delta A W^(-1)) y = v.  It always works on A:
+ * the handle's "operator" option is ignored (same bits under either value).  One GPU handle only.  No reference counterpart.
+ *   method    A W^(-1) = W P W^(-1) with P = D^(-1) A (zero rows where d_i = 0), so y = (1 / delta) W z with (sigma I - P) z = b,
+ *             sigma = 1 / delta > 1, b = W^(-1) v.  P is self-adjoint in <a, b>_W = sum w_i a_i b_i and sigma I - P is positive
+ *             definite there: CG in that inner product on the seed system, the largest delta; every other delta follows by the
+ *             multi-shift recurrences of lzx_solve_shifted_f64.  One SpMV and two streaming kernels per iteration; the state is
+ *             2 + 2 nd' vectors of n_loc_pad + 64 doubles (nd' = distinct dampings), plus the handle's degree array (4 bytes per
+ *             row, built on the first call that needs it and kept as long as the graph).
+ *   stop      damping s is frozen once |zeta_{s,j}| ||r_j||_W <= tol ||b||_W; the rule is evaluated on the device, the host reads a
+ *             small status every 16 iterations (the results do not depend on that period).
+ *   v         [n] in the caller's order, or NULL: the uniform vector, made on the device (nothing is uploaded).
+ *   output    X[s * n + i]: x_s in the caller's damping and vertex order, summing to 1 (the division by sum(y) happens on the
+ *             device; a duplicate damping gets the same vector); iters[s] (or NULL): the iteration at which damping s froze
+ *             (the iterations launched if it did not); resid[s] (or NULL): the true L1 residual ||v - (I - delta_s A W^(-1)) y_s||_1
+ *             / ||v||_1, formed on the device with one SpMV per distinct damping.
+ *   errors    LZX_ERR_ARG: null handle, damping or X; nd = 0; a damping that is not finite or not in (0, 1); tol <= 0 or NaN;
+ *             maxiter = 0; v with a negative or non-finite entry or with sum 0; a curvature <p, (sigma_0 I - P) p>_W <= 0 during
+ *             the solve (the matrix handed over is not symmetric).  LZX_ERR_LIMIT: nd > 16, or maxiter reached before every
+ *             damping converged (X, iters and resid are still written).  LZX_ERR_STATE: a handle with a communicator, no graph.
+ *             LZX_ERR_NOMEM: the state does not fit (the message states the bytes).  Nothing of the solver is left allocated
+ *             after any return.
+ *   state     like lzx_spmv_f64 the call voids a prepared (chunked) single-vector decomposition; the resident basis, its
+ *             alpha / beta and the batch state are left alone.
+ *   determinism: identical arguments give identical bits; each x_s does not depend on the order of `damping` or on duplicates.
+ * info (or NULL): iterations (the last freeze), launched (>= iterations: the status period), converged (caller's dampings that
+ * met tol), nd; loop_ms (host clock, whole call), spmv_ms / vec_ms (device event time of the loop's SpMVs / of its vector
+ * kernels); mass[s]: sum of the unnormalised y_s in the caller's damping order (0 beyond nd). */
+typedef struct lzx_pagerank_info {
+    uint32_t iterations, launched, converged, nd;
+    double   loop_ms, spmv_ms, vec_ms;
+    double   mass[16];   /* sum of the unnormalised y_s, caller's damping order */
+} lzx_pagerank_info;
+int lzx_pagerank_f64(lzx_handle h, const double *v /* [n] caller order, or NULL = uniform */,
+                     uint32_t nd, const double *damping, double tol, uint32_t maxiter,
+                     double *X /* [nd][n] */, uint32_t *iters, double *resid, lzx_pagerank_info *info);
+
 /* ---- connected components and induced subgraphs --------------------------------------------------------
  * Everything above treats the graph as one piece; R-MAT graphs are not (tests/golden/rmat_n4096: 1 204 components, 1 200 of them
  * single vertices), and under L every component adds a copy of the eigenvalue 0.  These two calls name the pieces and hand a

@@ -77,6 +77,16 @@ class LzxSolveInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxPagerankInfo(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("launched", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("nd", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("vec_ms", ctypes.c_double), ("mass", ctypes.c_double * 16)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["mass"] = np.array(list(d["mass"])[:d["nd"]])
+        return d
+
+
 class LzxComponentsInfo(ctypes.Structure):
     _fields_ = [("n_components", ctypes.c_uint64), ("largest_size", ctypes.c_uint64), ("largest_label", ctypes.c_uint32),
                 ("rounds", ctypes.c_uint32), ("loop_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double)]
@@ -139,6 +149,8 @@ SYMBOLS = [
                                      ctypes.c_uint64, _f64p, ctypes.c_uint32, _f64p, _f64p, _f64p, ctypes.POINTER(LzxEigInfo)]),
     ("lzx_solve_shifted_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, ctypes.c_uint32,
                                              _f64p, _u32p, _f64p, ctypes.POINTER(LzxSolveInfo)]),
+    ("lzx_pagerank_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, _u32p, _f64p,
+                                        ctypes.POINTER(LzxPagerankInfo)]),
     ("lzx_components", ctypes.c_int, [_h, _u32p, ctypes.POINTER(LzxComponentsInfo)]),
     ("lzx_set_graph_induced", ctypes.c_int, [_h, _h, _u8p, _u32p, _u64p]),
 ]
@@ -688,6 +700,38 @@ class Engine:
         if normalized:
             X = X / (np.sign(X.sum(axis=1)) * np.linalg.norm(X, axis=1))[:, None]
         return X[0] if al.ndim == 0 else X
+
+    def pagerank(self, alpha=0.85, personalization=None, tol: float = 1e-10, maxiter: int = 1000):
+        """PageRank x = y / sum(y), (I - alpha A W^(-1)) y = v, as networkx.pagerank defines it on an undirected graph (dangling
+        mass back to v), by multi-shift CG in the degree inner product on the device (lzx_pagerank_f64).  personalization: (n,)
+        non-negative teleport vector (scaled to sum 1), None = uniform.  A scalar alpha returns x of shape (n,); a sequence
+        returns (X, info): X of shape (nd, n), info = the lzx_pagerank_info fields plus "iters" and "resid" (true L1 residuals),
+        one per damping.  The engine's operator option is ignored.  If maxiter runs out first, LzxError carries the partial
+        (X, info) as `.partial`."""
+        n = self.n
+        al = np.asarray(alpha, dtype=np.float64)
+        if al.ndim > 1:
+            raise ValueError(f"pagerank: alpha must be a scalar or a 1-D array, got shape {al.shape}")
+        a1 = np.ascontiguousarray(np.atleast_1d(al))
+        nd = len(a1)
+        v = None if personalization is None else np.ascontiguousarray(personalization, dtype=np.float64)
+        if v is not None and v.shape != (n,):
+            raise ValueError(f"pagerank: personalization must have shape ({n},), got {v.shape}")
+        X = np.zeros((max(nd, 1), n))
+        iters = np.zeros(max(nd, 1), dtype=np.uint32)
+        resid = np.zeros(max(nd, 1))
+        info = LzxPagerankInfo()
+        rc = self.L.lzx_pagerank_f64(self.h, None if v is None else _p(v, _f64p), nd, _p(a1, _f64p) if nd else None, tol, maxiter,
+                                     _p(X, _f64p), _p(iters, _u32p), _p(resid, _f64p), ctypes.byref(info))
+        d = info.as_dict()
+        d["iters"], d["resid"] = iters[:nd].copy(), resid[:nd].copy()
+        result = (X[:nd].copy(), d)
+        if rc == ERR_LIMIT and info.launched > 0:   # (info is written only by a run that got through its iterations)
+            err = LzxError(f"lzx_pagerank_f64 failed ({rc}): {self.L.lzx_last_error().decode(errors='replace')}")
+            err.partial = result
+            raise err
+        _check(rc, "lzx_pagerank_f64", self.L)
+        return result[0][0] if al.ndim == 0 else result
 
     # ---- connected components and induced subgraphs (include/lzx.h: lzx_components, lzx_set_graph_induced; DESIGN.md section 14) ----
     def components(self, want_labels: bool = True):

@@ -356,8 +356,8 @@ struct lzx_ctx {
     struct lzx_multi_state *multi = nullptr;
     int64_t multi_chunk_opt = -1;      // test shape multi_row_chunk: entries per chunk of a split row in the batched SpMM (-1: LZX_MULTI_CHUNK)
     int64_t eig_basis_cap_opt = -1;    // test shape eig_basis_bytes: lzx_eigsh_f64 treats a basis larger than this as out of device memory
-    int64_t solve_cap_opt = -1;        // test shape solve_state_bytes: lzx_solve_shifted_f64 treats a state larger than this as out of device memory
-    int64_t solve_poll_opt = -1;       // test shape solve_poll: iterations between the shifted solver's status polls (default 16)
+    int64_t solve_cap_opt = -1;        // test shape solve_state_bytes: lzx_solve_shifted_f64 and lzx_pagerank_f64 treat a state larger than this as out of device memory
+    int64_t solve_poll_opt = -1;       // test shape solve_poll: iterations between the status polls of those two (default 16)
 };
 
 // ---- lzx_graph.hip ----

@@ -14,8 +14,8 @@
 // exact in any order is formed by several threads), "defer_finish" (0: the blocked SpMV always launches k_pb_finish; default: in the lazy loop
 // k_lazy_update adds the totals of multi-item gather bands where it reads v and the launch is left out), "multi_row_chunk" (entries per
 // chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048), "eig_basis_bytes" (lzx_eigsh_f64 takes a basis larger than this
-// many bytes as out of device memory), "solve_state_bytes" (the same for the state of lzx_solve_shifted_f64), "solve_poll" (iterations
-// between lzx_solve_shifted_f64's status polls; default 16).
+// many bytes as out of device memory), "solve_state_bytes" (the same for the state of lzx_solve_shifted_f64 and of lzx_pagerank_f64), "solve_poll" (iterations
+// between the status polls of those two; default 16).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
