@@ -373,6 +373,59 @@ typedef struct lzx_solve_info {
 int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns, const double *shifts, double tol, uint32_t maxiter,
                           const double *W, uint32_t nw, double *X, uint32_t *iters, double *resid, lzx_solve_info *info);
 
+/* ---- many right-hand sides: a batch of independent conjugate-gradient solves ---------------------------
+ * S(sigma_c) x_c = b_c for c = 1 .. nb (nb <= 16), every column with a right-hand side AND a shift of its own, on the device, with
+ * the handle's operator: S(sigma) = sigma I - A or sigma I + L exactly as in lzx_solve_shifted_f64.  Effective resistances for a
+ * list of pairs, columns of (I + t L)^(-1) or Katz vectors for a set of seeds, electrical flows for several demands.  One GPU
+ * handle only.  No reference counterpart.
+ *   method    nb plain CG recurrences (x = 0, r_0 = p_0 = b_c), NOT coupled into a block Krylov space: each column has its own
+ *             alpha, beta, stop and failure.  They share one SpMM per iteration over the batched path's layout, [n][B] with the
+ *             columns interleaved and B = nb padded to 2, 4, 8 or 16 (padded columns are zero and frozen from the start): col_idx
+ *             is read once and one gathered line serves every column.  One SpMM and two streaming kernels per iteration; the
+ *             state is b, r, p, x and the batched work vector, (5 B + nw) n doubles, plus three partial arrays of n / 2048 x B.
+ *   stop      column c is frozen (its x, r and p are no longer written; no scalar of it is formed any more) once ||r_{c,j}|| <= tol ||b_c||;
+ *             iters[c] is the iteration count at the freeze, or maxiter if it never froze.  The rule is evaluated on the device;
+ *             the host reads a small status every 16 iterations (the results do not depend on that period).
+ *   curvature p_c . S(sigma_c) p_c = sigma_c p.p -+ p.Mp <= 0 or not finite stops THAT column only: status[c] = 2, x_c stays at the
+ *             iterate before the failing step (iters[c]: that iteration), the other columns go on.
+ *   status[c] 0 = converged, 1 = maxiter reached, 2 = S(sigma_c) is not positive definite.
+ *   returns   any column with status 2: LZX_ERR_ARG (the message names the first such column, its sigma, the iteration and the
+ *             curvature); otherwise any column with status 1: LZX_ERR_LIMIT.  In both cases X, iters, resid, status and info are
+ *             written for every column.
+ *   W         nw <= 8 deflation vectors (nw x n, caller order; NULL when nw = 0) shared by all columns, orthonormalised in order
+ *             on the device (a column within 1e-10, relative, of the span of those before it: LZX_ERR_ARG).  Every b_c is
+ *             projected onto span(W)^perp before the solve and every x_c after it; bnorm and the stop rule use the projected b.
+ *             Under L, sigma_c = 0 is allowed only with nw >= 1.
+ *   output    Bm[c * n + i] and X[c * n + i]: column c in the caller's vertex order; resid[c]: the true relative residual
+ *             ||b_c - S(sigma_c) x_c|| / ||b_c||, formed on the device with one more SpMM over X.
+ *   errors    LZX_ERR_ARG: null handle, Bm, shifts or X; nb = 0; tol <= 0 or NaN; maxiter = 0; a shift that is not finite or < 0;
+ *             sigma_c <= 0 under A; sigma_c = 0 under L without W; nw > 0 with W null; W rank-deficient; a column b_c that is
+ *             zero or lies in span(W) (the message names the column).  LZX_ERR_LIMIT: nb > 16, nw > 8.  LZX_ERR_STATE: a handle
+ *             with a communicator, or no graph.  LZX_ERR_NOMEM: the state does not fit (the message states the bytes).  The
+ *             checks that need no device come first.  Nothing of the solver is left allocated after any return.
+ *   state     like lzx_spmm_f64 the call does NOT void a prepared (chunked) single-vector decomposition and leaves the resident
+ *             single-vector basis alone; a resident batch basis stays too (lzx_multout_multi_f64 and lzx_probe_diag_f64 answer
+ *             afterwards with the bits they had before).
+ *   determinism: identical arguments give identical bits, and x_c, iters[c], resid[c] and bnorm[c] are bit-identical whatever
+ *             else is in the batch, whatever c's place in it and whatever nb pads to: every sum has a shape that depends on n
+ *             alone (runs of 32 rows left to right, one partial per 2048 rows, a fixed-order close; no floating-point atomics).
+ * info (or NULL): iterations (the largest iters[c]), launched (>= iterations: the status period), converged (columns that met
+ * tol), nb; loop_ms (host clock, whole call), spmv_ms / vec_ms (device event time of the loop's SpMMs / of its vector kernels);
+ * bnorm[c]: ||b_c|| after deflation, caller's column order (0 beyond nb). */
+typedef struct lzx_solve_multi_info {
+    uint32_t iterations;   /* the last freeze: iterations whose results were used */
+    uint32_t launched;     /* >= iterations (status poll period)                   */
+    uint32_t converged;    /* columns that met tol                                 */
+    uint32_t nb;
+    double   loop_ms, spmv_ms, vec_ms;   /* host clock of the call; device event time of SpMMs / vector kernels */
+    double   bnorm[16];    /* ||b_c|| after deflation, caller's column order (0 beyond nb) */
+} lzx_solve_multi_info;
+int lzx_solve_multi_f64(lzx_handle h, uint32_t nb, const double *Bm /* [nb][n] caller order */,
+                        const double *shifts /* [nb], one per column */, double tol, uint32_t maxiter,
+                        const double *W, uint32_t nw, double *X /* [nb][n] */,
+                        uint32_t *iters /* [nb] or NULL */, double *resid /* [nb] or NULL */,
+                        uint32_t *status /* [nb] or NULL */, lzx_solve_multi_info *info /* or NULL */);
+
 /* ---- PageRank: multi-shift conjugate gradients in the degree inner product -----------------------------
  * PageRank and personalised PageRank of the handle's (undirected) graph for nd <= 16 damping factors from ONE Krylov sequence,
  * on the device.  With d_i the stored entries of row i (the degree of option "operator" = LZX_OP_LAPLACIAN: a self loop counts

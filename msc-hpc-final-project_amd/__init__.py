@@ -77,6 +77,16 @@ class LzxSolveInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxSolveMultiInfo(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("launched", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("nb", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("vec_ms", ctypes.c_double), ("bnorm", ctypes.c_double * 16)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["bnorm"] = np.array(list(d["bnorm"])[:d["nb"]])
+        return d
+
+
 class LzxPagerankInfo(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("launched", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("nd", ctypes.c_uint32),
                 ("loop_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("vec_ms", ctypes.c_double), ("mass", ctypes.c_double * 16)]
@@ -149,6 +159,8 @@ SYMBOLS = [
                                      ctypes.c_uint64, _f64p, ctypes.c_uint32, _f64p, _f64p, _f64p, ctypes.POINTER(LzxEigInfo)]),
     ("lzx_solve_shifted_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, ctypes.c_uint32,
                                              _f64p, _u32p, _f64p, ctypes.POINTER(LzxSolveInfo)]),
+    ("lzx_solve_multi_f64", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, ctypes.c_uint32,
+                                           _f64p, _u32p, _f64p, _u32p, ctypes.POINTER(LzxSolveMultiInfo)]),
     ("lzx_pagerank_f64", ctypes.c_int, [_h, _f64p, ctypes.c_uint32, _f64p, ctypes.c_double, ctypes.c_uint32, _f64p, _u32p, _f64p,
                                         ctypes.POINTER(LzxPagerankInfo)]),
     ("lzx_components", ctypes.c_int, [_h, _u32p, ctypes.POINTER(LzxComponentsInfo)]),
@@ -681,6 +693,68 @@ class Engine:
             raise err
         _check(rc, "lzx_solve_shifted_f64", self.L)
         return result
+
+    def solve_multi(self, B, shifts, tol: float = 1e-10, maxiter: int = 1000, W=None):
+        """x_c = S(sigma_c)^(-1) b_c for up to 16 right-hand sides by a batch of independent CG solves that share one SpMM per
+        iteration (lzx_solve_multi_f64): S(sigma) = sigma I - A, or sigma I + L under option operator = OP_LAPLACIAN.  B: (nb, n);
+        shifts: a scalar (the same for every column) or nb values.  Returns (X, info): X of shape (nb, n); info: the
+        lzx_solve_multi_info fields plus "iters", "resid" (true relative residuals) and "status" (0 converged, 1 maxiter reached,
+        2 not positive definite), one per column.  W: (nw, n) or (n,) deflation vectors shared by all columns.  If maxiter runs
+        out first, LzxError carries the partial (X, info) as `.partial`."""
+        n = self.n
+        Bc = np.ascontiguousarray(B, dtype=np.float64)
+        if Bc.ndim != 2 or Bc.shape[1] != n:
+            raise ValueError(f"solve_multi: B must be a (nb, n) array with n = {n}, got shape {Bc.shape}")
+        nb = Bc.shape[0]
+        sh = np.asarray(shifts, dtype=np.float64)
+        if sh.ndim > 1 or (sh.ndim == 1 and len(sh) != nb):
+            raise ValueError(f"solve_multi: shifts must be a scalar or have one value per row of B ({nb}), got shape {sh.shape}")
+        s1 = np.ascontiguousarray(np.full(nb, float(sh)) if sh.ndim == 0 else sh)
+        Wc = None if W is None else np.ascontiguousarray(np.atleast_2d(W), dtype=np.float64)
+        if Wc is not None and Wc.shape[1] != n:
+            raise ValueError(f"solve_multi: W must have n = {n} columns, got shape {Wc.shape}")
+        nw = 0 if Wc is None else Wc.shape[0]
+        X = np.zeros((max(nb, 1), n))
+        iters = np.zeros(max(nb, 1), dtype=np.uint32)
+        status = np.zeros(max(nb, 1), dtype=np.uint32)
+        resid = np.zeros(max(nb, 1))
+        info = LzxSolveMultiInfo()
+        rc = self.L.lzx_solve_multi_f64(self.h, nb, _p(Bc, _f64p) if nb else None, _p(s1, _f64p) if nb else None, tol, maxiter,
+                                        None if Wc is None else _p(Wc, _f64p), nw, _p(X, _f64p), _p(iters, _u32p), _p(resid, _f64p),
+                                        _p(status, _u32p), ctypes.byref(info))
+        d = info.as_dict()
+        d["iters"], d["resid"], d["status"] = iters[:nb].copy(), resid[:nb].copy(), status[:nb].copy()
+        result = (X[:nb].copy(), d)
+        if rc != 0 and info.launched > 0:   # (info is written only by a run that got through its iterations)
+            err = LzxError(f"lzx_solve_multi_f64 failed ({rc}): {self.L.lzx_last_error().decode(errors='replace')}")
+            err.partial = result
+            raise err
+        _check(rc, "lzx_solve_multi_f64", self.L)
+        return result
+
+    def effective_resistance(self, pairs, tol: float = 1e-10, maxiter: int = 1000):
+        """R_uv = (e_u - e_v)^T L+ (e_u - e_v) for every (u, v) of `pairs` ((m, 2) vertex ids), by solve_multi in batches of 16
+        right-hand sides with sigma = 0 and W = 1 / sqrt(n).  Needs operator = OP_LAPLACIAN (ValueError otherwise) and a
+        CONNECTED graph: on a graph in several pieces run it on largest_component() (or another induced piece), whose null space
+        the constant vector spans.  A pair with u == v has resistance 0.  Returns an array of m values."""
+        if self.operator != OP_LAPLACIAN:
+            raise ValueError("effective_resistance: effective resistances are defined on the Laplacian; this engine's operator is the adjacency matrix")
+        pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = self.n
+        if pr.size and (pr.min() < 0 or pr.max() >= n):
+            raise ValueError(f"effective_resistance: vertex ids must lie in [0, {n})")
+        out = np.zeros(len(pr))
+        todo = np.flatnonzero(pr[:, 0] != pr[:, 1])
+        w = np.full(n, 1.0 / np.sqrt(n))
+        for first in range(0, len(todo), 16):
+            idx = todo[first:first + 16]
+            Bm = np.zeros((len(idx), n))
+            rows = np.arange(len(idx))
+            Bm[rows, pr[idx, 0]] = 1.0
+            Bm[rows, pr[idx, 1]] = -1.0
+            X, _ = self.solve_multi(Bm, 0.0, tol=tol, maxiter=maxiter, W=w)
+            out[idx] = X[rows, pr[idx, 0]] - X[rows, pr[idx, 1]]
+        return out
 
     def katz(self, alpha=None, beta: float = 1.0, normalized: bool = True, factor: float = 0.85, tol: float = 1e-10, maxiter: int = 1000):
         """Katz centrality x = beta (I - alpha A)^(-1) 1 as networkx.katz_centrality_numpy defines it (normalised by

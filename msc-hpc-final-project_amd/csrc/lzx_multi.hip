@@ -43,42 +43,7 @@
 #include "lzx_internal.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
-
-static constexpr u32 LZX_MULTI_CHUNK = 2048;   // entries per chunk of a split row (test shape multi_row_chunk)
-static constexpr u32 LZX_MULTI_RUN = 32;       // rows one thread sums left to right per column
-static constexpr u32 LZX_MULTI_SEG = 2048;     // rows per partial (64 runs: one per lane of the closing wavefront)
-static constexpr u32 LZX_MULTI_RUNS = LZX_MULTI_SEG / LZX_MULTI_RUN;
-static constexpr u32 LZX_MULTI_BLOCK = 256;
-static constexpr u32 LZX_MULTI_PAD = 0xffffffffu;   // work-list entry without output (padding)
-static constexpr u32 LZX_MULTI_PART = 0x80000000u;  // work-list dst flag: a chunk total, slot = dst & ~flag
-
-struct lzx_multi_state {
-    // per graph: the work list (built on first use, freed with the graph)
-    u32 chunk = 0;                     // L the list was built with
-    u64 n_wl = 0;                      // entries, padded to a multiple of 32 (the most segments one wavefront takes)
-    uint4 *d_wl = nullptr;             // {first entry lo, hi, length, dst}, longest first
-    u32 n_split = 0, n_parts = 0;
-    u32 *d_split_row = nullptr;        // [n_split] split rows, ascending
-    u32 *d_split_first = nullptr;      // [n_split + 1] their first chunk slot
-    u32 *d_run_split = nullptr;        // [runs + 1] first split row at or behind the run's first row
-    u32 n_seg = 0;                     // partials per column
-    // work vectors (width wB)
-    u32 wB = 0;
-    double *d_V = nullptr, *d_X = nullptr;   // [n][wB] each
-    double *d_part = nullptr;          // [n_parts][wB] chunk totals
-    double *d_pa = nullptr, *d_pn = nullptr; // [n_seg][wB]
-    // batch basis
-    u32 B = 0, b = 0, k = 0;
-    bool resident = false;             // a decomposition's basis is there
-    bool ring = false;                 // d_Q is three rotating slots (basis-free run), not a basis
-    bool probe = false;                // the resident basis was started from probes (lzx_probe_diag_f64 works on it)
-    double *d_Q = nullptr;             // [k][n][B], or [3][n][B] when ring
-    double *d_alpha = nullptr, *d_beta = nullptr, *d_T = nullptr;   // [B][k]
-    double *d_mx = nullptr;            // [k][B] running max of |alpha_i| + beta_{i-1}
-    u32 *d_kused = nullptr;            // [B]
-    std::vector<u32> h_kused;
-    std::vector<hipEvent_t> ev;
-};
+#include "lzx_multi_shared.h"
 
 template <typename T>
 static void mfree(T *&p)
@@ -102,7 +67,7 @@ static int malloc_n(T **p, u64 count, const char *what)
     return LZX_OK;
 }
 
-static void free_work(lzx_multi_state *m)
+void lzx_multi_free_work(lzx_multi_state *m)
 {
     mfree(m->d_V); mfree(m->d_X); mfree(m->d_part); mfree(m->d_pa); mfree(m->d_pn);
     m->wB = 0;
@@ -123,7 +88,7 @@ void lzx_multi_free(lzx_ctx *c, bool with_tables)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_basis(m);
-    free_work(m);
+    lzx_multi_free_work(m);
     if (!with_tables) return;
     mfree(m->d_wl); mfree(m->d_split_row); mfree(m->d_split_first); mfree(m->d_run_split);
     for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
@@ -132,28 +97,6 @@ void lzx_multi_free(lzx_ctx *c, bool with_tables)
 }
 
 // ==================================================================================================== kernels
-// in [b][n] (caller's vectors) -> out [n][B], column c divided by div[c]; padded columns 0
-struct MultiDiv { double v[16]; };
-template <u32 B>
-__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_pack(const double *in, u32 b, u64 n, MultiDiv div, double *out)
-{
-    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
-    if (i >= n * B) return;
-    const u32 c = (u32)(i % B);
-    const u64 r = i / B;
-    out[i] = c < b ? in[(u64)c * n + r] / div.v[c] : 0.0;
-}
-
-// in [n][B] -> out [b][n]
-template <u32 B>
-__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_unpack(const double *in, u32 b, u64 n, double *out)
-{
-    const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
-    if (i >= n * B) return;
-    const u32 c = (u32)(i % B);
-    if (c < b) out[(u64)c * n + i / B] = in[i];
-}
-
 
 // out [n][B]: column c < b is probe first + c divided by div (sqrt(n) for a start vector, 1 for lzx_probes_f64); padded columns 0
 template <u32 B>
@@ -163,142 +106,6 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_multi_probe(u64 seed, u64 f
     if (i >= n * B) return;
     const u32 c = (u32)(i % B);
     out[i] = c < b ? lzx_probe_value(seed, first + c, i / B) / div : 0.0;
-}
-
-template <u32 B>
-__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
-k_multi_spmm(const uint4 *__restrict__ wl, u64 n_waves, const u32 *__restrict__ col, const double *__restrict__ X, double *Y, double *part)
-{
-    constexpr u32 G = 64 / B;
-    const u64 w = (u64)blockIdx.x * (LZX_MULTI_BLOCK / 64) + (threadIdx.x >> 6);
-    if (w >= n_waves) return;
-    const u32 lane = threadIdx.x & 63, s = lane / B, c = lane % B;
-    const uint4 e = wl[w * G + s];
-    const u64 beg = (u64)e.x | ((u64)e.y << 32);
-    const u32 len = e.z;
-    double acc = 0.0;
-    u32 i = 0;
-    // eight gathers in flight, then added in entry order (the sum's order is the entries' whatever the loads do)
-    for (; i + 8 <= len; i += 8) {
-        u32 j[8];
-        double t[8];
-#pragma unroll
-        for (u32 u = 0; u < 8; ++u) j[u] = col[beg + i + u];
-#pragma unroll
-        for (u32 u = 0; u < 8; ++u) t[u] = X[(u64)j[u] * B + c];
-#pragma unroll
-        for (u32 u = 0; u < 8; ++u) acc += t[u];
-    }
-    for (; i < len; ++i) acc += X[(u64)col[beg + i] * B + c];
-    if (e.w == LZX_MULTI_PAD) return;
-    if (e.w & LZX_MULTI_PART) part[(u64)(e.w & ~LZX_MULTI_PART) * B + c] = acc;
-    else Y[(u64)e.w * B + c] = acc;
-}
-
-// Per row segment and column: LZX_MULTI_RUNS run totals in sh[run * B + c] -> one partial out[c], by a tree whose shape does
-// not depend on B (lane l holds run l, then wave_sum).  Call with all threads; ends with a barrier.
-template <u32 B>
-__device__ __forceinline__ void seg_partials(double *sh, double *out)
-{
-    static_assert(LZX_MULTI_RUNS == 64, "one run per lane");
-    __syncthreads();
-    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (u32 c = wave; c < B; c += LZX_MULTI_BLOCK / 64) {
-        const double x = wave_sum(sh[lane * B + c]);
-        if (lane == 0) out[c] = x;
-    }
-    __syncthreads();
-}
-
-// All B columns' totals of p[0 .. np) ([np][B]) closed identically in every workgroup: per column the shape of
-// block_sum_fixed_256 (thread t adds entries t, t + 256, ... in index order, then wave_sum, then the four waves in order).
-template <u32 B>
-__device__ __forceinline__ void close_cols(const double *p, u32 np, double *shw /* [4][B] */, double *out /* [B], LDS */)
-{
-    double s[B];
-#pragma unroll
-    for (u32 c = 0; c < B; ++c) s[c] = 0.0;
-    for (u32 i = threadIdx.x; i < np; i += LZX_MULTI_BLOCK) {
-        double t[B];
-#pragma unroll
-        for (u32 c = 0; c < B; c += 2) {
-            const double2 v = *reinterpret_cast<const double2 *>(p + (u64)i * B + c);
-            t[c] = v.x;
-            t[c + 1] = v.y;
-        }
-#pragma unroll
-        for (u32 c = 0; c < B; ++c) s[c] += t[c];
-    }
-#pragma unroll
-    for (u32 c = 0; c < B; ++c) {
-        const double w = wave_sum(s[c]);
-        if ((threadIdx.x & 63) == 0) shw[(threadIdx.x >> 6) * B + c] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < B) {
-        const u32 c = threadIdx.x;
-        out[c] = ((shw[c] + shw[B + c]) + shw[2 * B + c]) + shw[3 * B + c];
-    }
-    __syncthreads();
-}
-
-// Split rows: V[r] = their chunk totals added in chunk order; with Q: partials of alpha = v . q per (row segment, column).
-template <u32 B>
-__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
-k_multi_alpha(double *V, const double *__restrict__ part, const u32 *__restrict__ split_row, const u32 *__restrict__ split_first,
-                const u32 *__restrict__ run_split, u32 n_split, const double *__restrict__ Q, double *pa, u64 n, u32 n_seg,
-                const u64 *__restrict__ row_ptr, const double *__restrict__ X)
-{
-    // row_ptr != nullptr (operator L): V[r] = fma(d_r, X[r], -V[r]) once the row's total is complete -- the epilogue of the
-    // single-vector k_lap_apply, per column, so columns stay independent
-    __shared__ double sh[LZX_MULTI_RUNS * B];
-    for (u32 seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {
-        for (u32 u = threadIdx.x; u < LZX_MULTI_RUNS * B; u += LZX_MULTI_BLOCK) {
-            const u32 run = u / B, c = u % B;
-            const u64 r0 = (u64)seg * LZX_MULTI_SEG + (u64)run * LZX_MULTI_RUN;
-            const u64 r1 = std::min<u64>(r0 + LZX_MULTI_RUN, n);
-            double s = 0.0;
-            u32 ks = r0 < n ? run_split[r0 / LZX_MULTI_RUN] : n_split;
-            if (r0 < n && r1 == r0 + LZX_MULTI_RUN && (ks >= n_split || split_row[ks] >= r1)) {
-                // no split row in this run (nearly every run): eight rows' loads in flight, products added in row order
-                if (row_ptr) {
-                    for (u64 r = r0; r < r1; ++r) {
-                        const double v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -V[r * B + c]);
-                        V[r * B + c] = v;
-                        if (Q) s += v * Q[r * B + c];
-                    }
-                } else if (Q) {
-                    for (u64 r = r0; r < r1; r += 8) {
-                        double v[8], q[8];
-#pragma unroll
-                        for (u32 t = 0; t < 8; ++t) { v[t] = V[(r + t) * B + c]; q[t] = Q[(r + t) * B + c]; }
-#pragma unroll
-                        for (u32 t = 0; t < 8; ++t) s += v[t] * q[t];
-                    }
-                }
-            } else if (r0 < n) {
-                for (u64 r = r0; r < r1; ++r) {
-                    double v;
-                    if (ks < n_split && split_row[ks] == r) {
-                        v = 0.0;
-                        for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) v += part[(u64)p * B + c];
-                        if (row_ptr) v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -v);
-                        V[r * B + c] = v;
-                        ++ks;
-                    } else {
-                        v = V[r * B + c];
-                        if (row_ptr) {
-                            v = fma((double)(row_ptr[r + 1] - row_ptr[r]), X[r * B + c], -v);
-                            V[r * B + c] = v;
-                        }
-                    }
-                    if (Q) s += v * Q[r * B + c];
-                }
-            }
-            sh[u] = s;
-        }
-        if (Q) seg_partials<B>(sh, pa + (u64)seg * B);
-    }
 }
 
 // alpha_c closed from pa by every workgroup; u = v - alpha q_j - beta_{j-1} q_{j-1} in place of v; partials of ||u||^2.
@@ -446,11 +253,9 @@ k_multi_diag(const double *__restrict__ Q, u32 k, u64 n, u32 b, const double *__
 }
 
 // ==================================================================================================== host side
-static u32 pad_width(u32 b) { return b <= 2 ? 2 : b <= 4 ? 4 : b <= 8 ? 8 : 16; }
+u32 lzx_multi_pad_width(u32 b) { return b <= 2 ? 2 : b <= 4 ? 4 : b <= 8 ? 8 : 16; }
 
-static inline u32 grid_of(u64 threads) { return (u32)((threads + LZX_MULTI_BLOCK - 1) / LZX_MULTI_BLOCK); }
-
-static int check_handle(lzx_ctx *c, const char *fn)
+int lzx_multi_check_handle(lzx_ctx *c, const char *fn)
 {
     if (c->comm_kind != 0 || c->world > 1)
         LZX_FAIL(LZX_ERR_STATE, "%s: the batched path runs on one GPU handle; this handle is rank %d of a communicator of %d", fn, c->rank, c->world);
@@ -466,7 +271,7 @@ static int check_handle(lzx_ctx *c, const char *fn)
 
 // The work list, once per graph: every row of at most L entries is one segment, a longer row ceil(len / L) chunks of L
 // entries (the last one shorter) whose totals go to slots of d_part; all segments stably sorted by length, longest first.
-static int build_tables(lzx_ctx *c)
+int lzx_multi_build_tables(lzx_ctx *c)
 {
     lzx_multi_state *m = c->multi;
     const u32 L = c->multi_chunk_opt > 0 ? (u32)std::min<int64_t>(c->multi_chunk_opt, 1 << 30) : LZX_MULTI_CHUNK;
@@ -538,22 +343,22 @@ static int build_tables(lzx_ctx *c)
 }
 
 // the work vectors of width B; need_x: the second one too (packing, unpacking -- a probe run starts on the device without it)
-static int ensure_work(lzx_ctx *c, u32 B, bool need_x = true)
+int lzx_multi_ensure_work(lzx_ctx *c, u32 B, bool need_x)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n;
     int rc;
     if (m->wB != B || !m->d_V) {
-        free_work(m);
+        lzx_multi_free_work(m);
         if ((rc = malloc_n(&m->d_V, n * B, "work vector")) || (rc = malloc_n(&m->d_part, (u64)m->n_parts * B, "chunk totals")) ||
             (rc = malloc_n(&m->d_pa, (u64)m->n_seg * B, "partials")) || (rc = malloc_n(&m->d_pn, (u64)m->n_seg * B, "partials"))) {
-            free_work(m);
+            lzx_multi_free_work(m);
             return rc;
         }
         m->wB = B;
     }
     if (need_x && !m->d_X && (rc = malloc_n(&m->d_X, n * B, "work vector"))) {
-        free_work(m);
+        lzx_multi_free_work(m);
         return rc;
     }
     return LZX_OK;
@@ -570,7 +375,7 @@ static int ensure_basis(lzx_ctx *c, u32 k, u32 B, bool ring, const char *fn)
     const u64 bytes = (u64)slots * c->n * B * sizeof(double);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > (u64)total_b) {
-        free_work(m);
+        lzx_multi_free_work(m);
         LZX_FAIL(LZX_ERR_NOMEM, "%s: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8), the device has %llu", fn,
                  (unsigned long long)bytes, slots, (unsigned long long)c->n, B, (unsigned long long)total_b);
     }
@@ -580,7 +385,7 @@ static int ensure_basis(lzx_ctx *c, u32 k, u32 B, bool ring, const char *fn)
         (rc = malloc_n(&m->d_beta, (u64)B * k, "coefficients")) || (rc = malloc_n(&m->d_T, (u64)B * k, "coefficients")) ||
         (rc = malloc_n(&m->d_mx, (u64)k * B, "coefficients")) || (rc = malloc_n(&m->d_kused, B, "coefficients"))) {
         free_basis(m);
-        free_work(m);
+        lzx_multi_free_work(m);
         if (rc == LZX_ERR_NOMEM)
             lzx_set_error("%s: the batch basis needs %llu bytes (k = %u x n = %llu x B = %u x 8) and does not fit", fn,
                           (unsigned long long)bytes, slots, (unsigned long long)c->n, B);
@@ -589,24 +394,6 @@ static int ensure_basis(lzx_ctx *c, u32 k, u32 B, bool ring, const char *fn)
     m->k = k;
     m->B = B;
     m->ring = ring;
-    return LZX_OK;
-}
-
-// Y = A X on [n][B] vectors, split rows finished into Y; with Q: alpha partials into pa (the loop's first two launches)
-template <u32 B>
-static int launch_spmm(lzx_ctx *c, const double *X, double *Y, const double *Q)
-{
-    lzx_multi_state *m = c->multi;
-    const u64 n_waves = m->n_wl / (64 / B);
-    if (n_waves)
-        hipLaunchKernelGGL(k_multi_spmm<B>, dim3((u32)((n_waves + 3) / 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_wl, n_waves,
-                           c->d_col_idx, X, Y, m->d_part);
-    const bool lap = c->op_opt == LZX_OP_LAPLACIAN;
-    if (m->n_seg && (Q || m->n_split || lap))
-        hipLaunchKernelGGL(k_multi_alpha<B>, dim3(std::min<u32>(m->n_seg, (u32)c->cu_count * 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, Y,
-                           m->d_part, m->d_split_row, m->d_split_first, m->d_run_split, m->n_split, Q, m->d_pa, c->n, m->n_seg,
-                           lap ? c->d_row_ptr : nullptr, X);
-    LZX_HIP(hipGetLastError());
     return LZX_OK;
 }
 
@@ -634,10 +421,10 @@ static int multi_loop(lzx_ctx *c, u32 b, MultiStart start, bool ring, u32 k, dou
         x_norm[col] = div.v[col];
     }
     int rc = ensure_basis(c, k, B, ring, fn);
-    if (rc == LZX_OK) rc = ensure_work(c, B, X0 != nullptr);
+    if (rc == LZX_OK) rc = lzx_multi_ensure_work(c, B, X0 != nullptr);
     if (rc != LZX_OK) {   // nothing half-built is left behind
         free_basis(m);
-        free_work(m);
+        lzx_multi_free_work(m);
         return rc;
     }
     if (ring) mfree(m->d_X);   // the state is the three slots and V
@@ -743,7 +530,7 @@ static int spmm_run(lzx_ctx *c, u32 b, const double *X, double *Y)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n, nB = n * B;
-    LZX_TRY(ensure_work(c, B));
+    LZX_TRY(lzx_multi_ensure_work(c, B));
     MultiDiv one{};
     for (u32 col = 0; col < 16; ++col) one.v[col] = 1.0;
     LZX_HIP(hipMemcpyAsync(m->d_V, X, sizeof(double) * b * n, hipMemcpyHostToDevice, c->stream));
@@ -774,7 +561,7 @@ static int multout_run(lzx_ctx *c, u32 b, const double *T, u32 k, double *ans)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n, nB = n * B;
-    LZX_TRY(ensure_work(c, B));
+    LZX_TRY(lzx_multi_ensure_work(c, B));
     LZX_TRY(upload_T(c, B, b, T, k));
     hipLaunchKernelGGL(k_multi_multout<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q, k, n, m->d_T, m->d_kused, m->d_V);
     hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
@@ -789,7 +576,7 @@ static int diag_run(lzx_ctx *c, u32 b, const double *T, u32 k, double *out)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n;
-    LZX_TRY(ensure_work(c, B, false));
+    LZX_TRY(lzx_multi_ensure_work(c, B, false));
     LZX_TRY(upload_T(c, B, b, T, k));
     hipLaunchKernelGGL(k_multi_diag<B>, dim3(grid_of(n * B)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_Q, k, n, b, m->d_T, m->d_kused, m->d_V);
     LZX_HIP(hipGetLastError());
@@ -803,7 +590,7 @@ static int probes_run(lzx_ctx *c, u64 seed, u64 first, u32 b, double *Z)
 {
     lzx_multi_state *m = c->multi;
     const u64 n = c->n, nB = n * B;
-    LZX_TRY(ensure_work(c, B));
+    LZX_TRY(lzx_multi_ensure_work(c, B));
     hipLaunchKernelGGL(k_multi_probe<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, seed, first, b, n, 1.0, m->d_V);
     hipLaunchKernelGGL(k_multi_unpack<B>, dim3(grid_of(nB)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_V, b, n, m->d_X);
     LZX_HIP(hipGetLastError());
@@ -832,15 +619,15 @@ extern "C" int lzx_lanczos_multi_f64(lzx_handle h, uint32_t b, const double *X0,
     if (!alpha || !beta) LZX_FAIL(LZX_ERR_ARG, "%s: null alpha / beta", fn);
     if (!k_used || !x_norm) LZX_FAIL(LZX_ERR_ARG, "%s: null k_used / x_norm", fn);
     if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
-    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(lzx_multi_check_handle(h, fn));
     for (u32 col = 0; col < b; ++col) {
         const double *x = X0 + (u64)col * h->n;
         if (std::all_of(x, x + h->n, [](double v) { return v == 0.0; }))
             LZX_FAIL(LZX_ERR_ARG, "%s: column %u of X0 is all zero", fn, col);
     }
-    int rc = build_tables(h);
+    int rc = lzx_multi_build_tables(h);
     if (rc) return rc;
-    const u32 B = pad_width(b);
+    const u32 B = lzx_multi_pad_width(b);
     LZX_MULTI_DISPATCH(B, multi_loop, h, b, MultiStart{X0, 0, 0}, false, k, alpha, beta, k_used, x_norm, Q, stats, fn);
 }
 
@@ -852,7 +639,7 @@ extern "C" int lzx_multout_multi_f64(lzx_handle h, uint32_t b, const double *T, 
     if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
     if (!T || !ans) LZX_FAIL(LZX_ERR_ARG, "%s: null T / ans", fn);
     if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
-    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(lzx_multi_check_handle(h, fn));
     lzx_multi_state *m = h->multi;
     if (!m->resident) LZX_FAIL(LZX_ERR_STATE, "%s: no batched decomposition is resident", fn);
     if (b != m->b || k > m->k)
@@ -867,10 +654,10 @@ extern "C" int lzx_spmm_f64(lzx_handle h, uint32_t b, const double *X, double *Y
     if (b == 0) LZX_FAIL(LZX_ERR_ARG, "%s: b == 0", fn);
     if (b > 16) LZX_FAIL(LZX_ERR_LIMIT, "%s: b = %u columns (at most 16 per batch)", fn, b);
     if (!X || !Y) LZX_FAIL(LZX_ERR_ARG, "%s: null X / Y", fn);
-    LZX_TRY(check_handle(h, fn));
-    LZX_TRY(build_tables(h));
+    LZX_TRY(lzx_multi_check_handle(h, fn));
+    LZX_TRY(lzx_multi_build_tables(h));
     // (the resident batch keeps its basis: only the work vectors may change width)
-    LZX_MULTI_DISPATCH(pad_width(b), spmm_run, h, b, X, Y);
+    LZX_MULTI_DISPATCH(lzx_multi_pad_width(b), spmm_run, h, b, X, Y);
 }
 
 extern "C" int lzx_multi_release(lzx_handle h)
@@ -895,9 +682,9 @@ extern "C" int lzx_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint3
     static const char *fn = "lzx_probes_f64";
     LZX_TRY(check_probes(h, fn, first, b));
     if (!Z) LZX_FAIL(LZX_ERR_ARG, "%s: null Z", fn);
-    LZX_TRY(check_handle(h, fn));
-    LZX_TRY(build_tables(h));
-    LZX_MULTI_DISPATCH(pad_width(b), probes_run, h, seed, first, b, Z);
+    LZX_TRY(lzx_multi_check_handle(h, fn));
+    LZX_TRY(lzx_multi_build_tables(h));
+    LZX_MULTI_DISPATCH(lzx_multi_pad_width(b), probes_run, h, seed, first, b, Z);
 }
 
 extern "C" int lzx_lanczos_probes_f64(lzx_handle h, uint64_t seed, uint64_t first, uint32_t b, uint32_t k, uint32_t flags,
@@ -908,10 +695,10 @@ extern "C" int lzx_lanczos_probes_f64(lzx_handle h, uint64_t seed, uint64_t firs
     if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
     if (!alpha || !beta || !k_used) LZX_FAIL(LZX_ERR_ARG, "%s: null alpha / beta / k_used", fn);
     if (flags & ~(uint32_t)LZX_PROBE_KEEP_BASIS) LZX_FAIL(LZX_ERR_ARG, "%s: unknown flags 0x%x", fn, flags);
-    LZX_TRY(check_handle(h, fn));
-    LZX_TRY(build_tables(h));
+    LZX_TRY(lzx_multi_check_handle(h, fn));
+    LZX_TRY(lzx_multi_build_tables(h));
     const bool ring = !(flags & LZX_PROBE_KEEP_BASIS);
-    LZX_MULTI_DISPATCH(pad_width(b), multi_loop, h, b, MultiStart{nullptr, seed, first}, ring, k, alpha, beta, k_used, nullptr, nullptr,
+    LZX_MULTI_DISPATCH(lzx_multi_pad_width(b), multi_loop, h, b, MultiStart{nullptr, seed, first}, ring, k, alpha, beta, k_used, nullptr, nullptr,
                        stats, fn);
 }
 
@@ -921,7 +708,7 @@ extern "C" int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, dou
     if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
     if (!T || !out) LZX_FAIL(LZX_ERR_ARG, "%s: null T / out", fn);
     if (k == 0) LZX_FAIL(LZX_ERR_ARG, "%s: k == 0", fn);
-    LZX_TRY(check_handle(h, fn));
+    LZX_TRY(lzx_multi_check_handle(h, fn));
     lzx_multi_state *m = h->multi;
     if (!m->resident || !m->probe)
         LZX_FAIL(LZX_ERR_STATE, "%s: no probe basis is resident (run lzx_lanczos_probes_f64 with LZX_PROBE_KEEP_BASIS)", fn);
