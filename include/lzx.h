@@ -513,6 +513,73 @@ int lzx_components(lzx_handle h, uint32_t *labels /* [n], caller order */, lzx_c
 int lzx_set_graph_induced(lzx_handle dst, lzx_handle src, const uint8_t *keep /* [n of src], non-zero = keep */,
                           uint32_t *old_of_new /* [n_new] or NULL */, uint64_t *n_new /* or NULL */);
 
+/* ---- path-based centralities: batched breadth-first search and betweenness ------------------------------
+ * Everything above is spectral; these two calls serve the centralities defined by shortest paths of the unweighted, undirected
+ * graph -- BFS distances from a set of seeds, closeness, harmonic centrality, betweenness -- on the device, from the caller-order
+ * CSR the handle keeps.  One GPU handle only.  No reference counterpart.
+ *
+ * lzx_bfs_multi: a breadth-first search from every one of the ns sources (caller's vertex order; ns is not limited: the list
+ * is cut into batches of 16 in the caller's order; a source may appear more than once).  Per source s: dist[s][v] = the number
+ * of edges of a shortest path (-1: v is not reachable), paths[s][v] = the number of shortest paths (0 where unreachable, 1 at the
+ * source), reached[s] = vertices reached, the source included, sum_dist[s] = the sum of the distances to them, harmonic[s] = the
+ * sum over the reached v != s of 1 / dist, ecc[s] = the largest distance.  Every output may be NULL; only those asked for cross
+ * PCIe.  A self loop changes nothing; a source without an edge reaches itself only.
+ *
+ * lzx_betweenness_f64: bc[v] = the sum over the sources s of Brandes' dependency delta_s(v), v != s -- the raw sum: no 1/2 for
+ * undirectedness, no normalisation, no endpoints (sources == NULL: every vertex is a source, ns must equal n; the result is then
+ * twice networkx's unnormalised betweenness).  A source listed twice counts twice.
+ *
+ *   method    pull form, up to 16 sources per sweep over the edges.  Per batch the state is dist (i32), sigma (f64) and g (f64),
+ *             each [n][B] with B = the batch width padded to 2, 4, 8 or 16, plus one bc[n]: 20 B n + 8 n bytes.
+ *             Forward, level d = 1, 2, ...: every (vertex v, column c) with dist = -1 forms s = the sum of sigma[u][c] over
+ *             its neighbours u, in ascending column order, with dist[u][c] = d - 1; s > 0 sets dist = d, sigma = s -- in place:
+ *             a reader tests "= d - 1", a writer stores d.  The newly reached are counted per column with integer atomics (one
+ *             per wavefront and column); the host reads those B words per level, stops when none grew, and forms reached,
+ *             sum_dist, harmonic (added in ascending d as count / (double)d) and ecc from them: exact functions of the level
+ *             histogram.
+ *             Backward (betweenness), level d = L ... 1 with g[w][c] = (1 + delta[w][c]) / sigma[w][c]: every (u, c) with
+ *             dist = d forms s = the sum of g[w][c] over its neighbours with dist[w][c] = d + 1, then delta = sigma * s and
+ *             g = (1 + delta) / sigma (the deepest level finds s = 0: delta = 0, g = 1 / sigma) -- networkx's
+ *             coeff = (1 + delta[w]) / sigma[w]; delta[v] += sigma[v] * coeff with sigma factored out of the sum.  Then
+ *             bc[v] += delta[v][c] one column after the other in ascending c, batch after batch.
+ *             Both passes are one kernel shape, a masked SpMM over the batched path's work list (whole rows, and chunks of
+ *             longer rows whose totals are added in chunk order); a (row, column) whose own level fails the pass's condition
+ *             skips its gather.  No floating-point atomics.
+ *   bits      identical arguments give identical bits.  dist, paths, reached, sum_dist, harmonic and ecc of a source are the
+ *             same bits whatever else is in the call and wherever the source stands in it.  bc of a call with sources
+ *             (s_1 ... s_m) equals, bit for bit, ((bc(s_1) + bc(s_2)) + ...) of m single-source calls added left to right.
+ *   paths     exact while every count stays below 2^53; beyond that a rounded double, as in networkx (which keeps sigma as a
+ *             float too).  Not guarded.
+ *   cost      a forward level is one sweep over every entry of the rows still unreached, a backward level gathers only the
+ *             rows on that level: O(L nnz) per batch forward, one more forward sweep (the one that finds nothing) than levels.
+ *   state     the calls touch nothing of the handle's other state: they void no prepared or chunked decomposition and leave the
+ *             resident single-vector basis and the batch basis answering with the bits they had.  The exception is the batched
+ *             path's per-graph work list, which is built on first use and kept, as lzx_spmm_f64 does.  Everything else they
+ *             allocate is freed before they return, on every path.
+ *   info      (or NULL) sources and batches, the largest eccentricity among the sources, the edge sweeps launched (forward and
+ *             backward, over all batches), the host clock of the call and the device event time of the sweeps alone.
+ *   errors    LZX_ERR_ARG: null handle, ns == 0, null sources (lzx_bfs_multi), null sources with ns != n or null bc
+ *             (lzx_betweenness_f64), a source >= n (the message names its index and value).  LZX_ERR_STATE: no graph, a handle
+ *             with a communicator, a graph from a sharded hand-over over several ranks.  LZX_ERR_NOMEM: the message states the
+ *             bytes.  The checks that need no device come first.
+ *   limits    one GPU handle; unweighted, undirected graphs; no edge betweenness, no endpoints; no push / direction-optimising
+ *             search (a small frontier still costs a sweep over the unreached rows). */
+typedef struct lzx_bfs_info {
+    uint32_t ns, batches;      /* sources, batches of <= 16 */
+    uint32_t max_level;        /* largest eccentricity among the sources */
+    uint32_t sweeps;           /* edge sweeps launched, forward + backward, over all batches */
+    double   loop_ms, sweep_ms;/* host clock of the call; device event time of the sweeps alone */
+} lzx_bfs_info;
+int lzx_bfs_multi(lzx_handle h, uint32_t ns, const uint32_t *sources,
+                  int32_t *dist /* [ns][n] or NULL; -1 = not reachable */,
+                  double *paths /* [ns][n] or NULL: number of shortest paths from the source (0 where unreachable) */,
+                  uint64_t *reached /* [ns] or NULL: vertices reached, the source included */,
+                  uint64_t *sum_dist /* [ns] or NULL */, double *harmonic /* [ns] or NULL: sum over reached v != s of 1/d(s,v) */,
+                  uint32_t *ecc /* [ns] or NULL */, lzx_bfs_info *info /* or NULL */);
+int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NULL: every vertex, ns must equal n */,
+                        double *bc /* [n], caller order: sum over the sources s of Brandes' dependency delta_s(v), v != s */,
+                        lzx_bfs_info *info /* or NULL */);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

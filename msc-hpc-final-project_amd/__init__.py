@@ -24,10 +24,11 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll")
+                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
+_i32p = ctypes.POINTER(ctypes.c_int32)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _f64p = ctypes.POINTER(ctypes.c_double)
 _h = ctypes.c_void_p
@@ -105,6 +106,14 @@ class LzxComponentsInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxBfsInfo(ctypes.Structure):
+    _fields_ = [("ns", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("max_level", ctypes.c_uint32), ("sweeps", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -165,6 +174,8 @@ SYMBOLS = [
                                         ctypes.POINTER(LzxPagerankInfo)]),
     ("lzx_components", ctypes.c_int, [_h, _u32p, ctypes.POINTER(LzxComponentsInfo)]),
     ("lzx_set_graph_induced", ctypes.c_int, [_h, _h, _u8p, _u32p, _u64p]),
+    ("lzx_bfs_multi", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _i32p, _f64p, _u64p, _u64p, _f64p, _u32p, ctypes.POINTER(LzxBfsInfo)]),
+    ("lzx_betweenness_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _f64p, ctypes.POINTER(LzxBfsInfo)]),
 ]
 
 _LIB = None
@@ -867,6 +878,86 @@ class Engine:
                 raise ValueError(f"component_indicators: {int(r)} is not the label of a component")
             W[i, members] = 1.0 / np.sqrt(np.count_nonzero(members))
         return W
+
+    # ---- path-based centralities (include/lzx.h: lzx_bfs_multi, lzx_betweenness_f64) ----
+    def _sources(self, sources, what):
+        """(uint32 array or None for every vertex, ns)"""
+        if sources is None:
+            return None, self.n
+        src = np.atleast_1d(np.asarray(sources))
+        if src.ndim != 1 or src.size == 0:
+            raise ValueError(f"{what}: sources must be a non-empty 1-D sequence of vertex ids")
+        if src.min() < 0 or src.max() >= self.n:
+            raise ValueError(f"{what}: vertex ids must lie in [0, {self.n})")
+        return np.ascontiguousarray(src, dtype=np.uint32), len(src)
+
+    def bfs(self, sources, paths: bool = False, dist: bool = True):
+        """Breadth-first search from every source on the device, 16 sources per sweep over the edges (lzx_bfs_multi).  Returns
+        (dist, info) or, with paths=True, (dist, paths, info): dist (ns, n) int32 with -1 where unreachable (None with
+        dist=False: then no n-vector leaves the device), paths (ns, n) the number of shortest paths, info = the lzx_bfs_info
+        fields plus "reached", "sum_dist", "harmonic" and "ecc", one per source."""
+        src, ns = self._sources(np.arange(self.n, dtype=np.uint32) if sources is None else sources, "bfs")
+        D = np.empty((ns, self.n), dtype=np.int32) if dist else None
+        P = np.empty((ns, self.n)) if paths else None
+        reached, sum_dist = np.zeros(ns, dtype=np.uint64), np.zeros(ns, dtype=np.uint64)
+        harmonic, ecc = np.zeros(ns), np.zeros(ns, dtype=np.uint32)
+        info = LzxBfsInfo()
+        _check(self.L.lzx_bfs_multi(self.h, ns, _p(src, _u32p), _p(D, _i32p) if dist else None, _p(P, _f64p) if paths else None,
+                                    _p(reached, _u64p), _p(sum_dist, _u64p), _p(harmonic, _f64p), _p(ecc, _u32p), ctypes.byref(info)),
+               "lzx_bfs_multi", self.L)
+        d = info.as_dict()
+        d.update(reached=reached, sum_dist=sum_dist, harmonic=harmonic, ecc=ecc)
+        return (D, P, d) if paths else (D, d)
+
+    def closeness(self, sources=None):
+        """networkx.closeness_centrality(G, u) with wf_improved=True for every u of `sources` (None: every vertex), from the
+        per-source counts alone: ((r - 1) / sum_dist) * ((r - 1) / (n - 1)) with r the vertices u reaches; 0 for a vertex that
+        reaches only itself."""
+        info = self.bfs(np.arange(self.n, dtype=np.uint32) if sources is None else sources, dist=False)[1]
+        r1 = info["reached"].astype(np.float64) - 1.0
+        tot = info["sum_dist"].astype(np.float64)
+        out = np.zeros(len(r1))
+        ok = (tot > 0) & (self.n > 1)
+        out[ok] = (r1[ok] / tot[ok]) * (r1[ok] / (self.n - 1.0))
+        return out
+
+    def harmonic(self, sources=None):
+        """networkx.harmonic_centrality of every vertex of `sources` (None: every vertex): the sum of 1 / d(u, v) over the v != u
+        that u reaches."""
+        return self.bfs(np.arange(self.n, dtype=np.uint32) if sources is None else sources, dist=False)[1]["harmonic"]
+
+    def betweenness_raw(self, sources=None):
+        """(bc, info) of lzx_betweenness_f64: the sum over the sources (None: every vertex) of Brandes' dependencies, unscaled."""
+        src, ns = self._sources(sources, "betweenness")
+        bc = np.empty(self.n)
+        info = LzxBfsInfo()
+        _check(self.L.lzx_betweenness_f64(self.h, ns, None if src is None else _p(src, _u32p), _p(bc, _f64p), ctypes.byref(info)),
+               "lzx_betweenness_f64", self.L)
+        return bc, info.as_dict()
+
+    def betweenness(self, k=None, sources=None, normalized: bool = True, seed: int = 0):
+        """Betweenness centrality as networkx.betweenness_centrality defines it on an undirected graph without endpoints.
+        sources=None, k=None: exact; k: k distinct sources sampled with numpy.random.default_rng(seed); explicit `sources` are
+        scaled as a sample of len(sources).  Scaling (networkx 3.4's _rescale): 1 / ((n - 1)(n - 2)) when normalised and n > 2,
+        0.5 when not, both times n / k when sampling."""
+        n = self.n
+        if sources is not None and k is not None:
+            raise ValueError("betweenness: give k or sources, not both")
+        if k is not None:
+            if not 1 <= k <= n:
+                raise ValueError(f"betweenness: k must lie in [1, {n}]")
+            sources = np.random.default_rng(seed).choice(n, size=k, replace=False)
+        bc, _ = self.betweenness_raw(sources)
+        ks = None if sources is None else len(np.atleast_1d(sources))
+        if normalized:
+            scale = 1.0 / ((n - 1) * (n - 2)) if n > 2 else None
+        else:
+            scale = 0.5
+        if scale is not None:
+            if ks is not None:
+                scale = scale * n / ks
+            bc = bc * scale
+        return bc
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

@@ -157,6 +157,8 @@ static const Option g_options[] = {
     // lzx_solve_shifted_f64: a state of more than this many bytes is out of device memory; iterations between its status polls
     {"solve_state_bytes", &lzx_ctx::solve_cap_opt, OPT_SHAPE},
     {"solve_poll", &lzx_ctx::solve_poll_opt, OPT_SHAPE},
+    // lzx_bfs_multi / lzx_betweenness_f64: a state of more than this many bytes is out of device memory
+    {"bfs_state_bytes", &lzx_ctx::bfs_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

@@ -15,7 +15,8 @@
 // k_lazy_update adds the totals of multi-item gather bands where it reads v and the launch is left out), "multi_row_chunk" (entries per
 // chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048), "eig_basis_bytes" (lzx_eigsh_f64 takes a basis larger than this
 // many bytes as out of device memory), "solve_state_bytes" (the same for the state of lzx_solve_shifted_f64 and of lzx_pagerank_f64), "solve_poll" (iterations
-// between the status polls of those two; default 16).
+// between the status polls of those two; default 16), "bfs_state_bytes" (lzx_bfs_multi and lzx_betweenness_f64 take a state larger than this many
+// bytes as out of device memory; their long rows are the batched SpMM's: "multi_row_chunk").
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
