@@ -580,6 +580,56 @@ int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NU
                         double *bc /* [n], caller order: sum over the sources s of Brandes' dependency delta_s(v), v != s */,
                         lzx_bfs_info *info /* or NULL */);
 
+/* ---- triangles and clustering ---------------------------------------------------------------------
+ * lzx_triangles: the local structure of the handle's graph read as undirected and unweighted -- what networkx.triangles,
+ * clustering, transitivity and average_clustering return -- counted on the device over the caller-order CSR.
+ *   outputs   t_v = the number of triangles through v: tri[v] = t_v, caller order.  d_v = the number of stored entries of row v
+ *             NOT counting a diagonal entry (networkx removes v from its own neighbourhood).
+ *             clustering[v] = (double)(2 t_v) / (double)(d_v (d_v - 1)), and exactly 0.0 where d_v < 2 or t_v = 0: networkx's
+ *             expression, one correctly rounded fp64 division of two integers, so these are networkx's bits while
+ *             2 t_v < 2^53.  A self loop changes nothing in any output.  Every output may be NULL; only those asked for cross
+ *             PCIe.
+ *   info      (or NULL) triangles = T, every triangle of the graph counted once (sum t_v / 3); wedges = sum over v of
+ *             d_v (d_v - 1) / 2 (<= d_max nnz / 2 < 2^63: not guarded), so that transitivity = 3 T / wedges; max_triangles =
+ *             the largest t_v; avg_clustering = (1/n) sum c_v over EVERY vertex (networkx count_zeros=True), summed on the
+ *             device in a fixed order; the entries and the longest list of the oriented copy (below); the host clock of the
+ *             call, the device event time of building the oriented copy and of the counting launches.
+ *   method    vertices are ranked by (d_v, v) and every edge that is not a self loop is kept once, pointing from its lower to
+ *             its higher rank: an oriented CSR (64-bit row pointers) built by three launches and one exclusive scan -- degrees
+ *             without the diagonal; out-counts, scanned into the row pointers; the fill, a monotone filter of an ascending row,
+ *             so columns stay ascending by id.  A vertex of out-degree k has k neighbours of degree >= k, hence k^2 <= nnz:
+ *             every oriented list has fewer than 2^16 entries while nnz < 2^32.  A triangle of ranks a < b < c is found
+ *             exactly once, as c in N+(a) n N+(b) while row a handles its out-edge a -> b: the shorter of the two lists is
+ *             walked and the longer binary-searched.  A hit adds 1 to t_c; per out-edge the hits are added to t_b in one add
+ *             when non-zero; per row their total is added to t_a in one add.  Rows of at most 128 out-entries are counted a
+ *             group of lanes per row (4 to 32, from the mean oriented degree); longer rows a workgroup per row and slice of
+ *             its out-edges, a wavefront per out-edge, with N+(a) staged in LDS while it has at most 4096 entries (then the
+ *             hits on c are first counted in LDS and leave with one add per entry) and read where it lies beyond that.  All adds
+ *             are 64-bit INTEGER vector atomics (32-bit in LDS); there is no floating-point atomic anywhere.  No kernel waits
+ *             on another workgroup and every loop is bounded by a list length.
+ *   bits      identical arguments give identical bits.  tri, clustering, triangles, wedges and max_triangles are canonical:
+ *             any correct algorithm gives them, and they do not depend on how ties in the ranking fall.
+ *   state     the call touches none: it voids no prepared or chunked decomposition and leaves the resident bases and the batch
+ *             state alone.  Everything it allocates is freed before it returns, on every path: the oriented CSR
+ *             8 (n + 1) + 4 oriented_entries bytes (the columns are allocated once the scan has counted them), 4 n of
+ *             degrees, 8 n of counts, 8 n of coefficients, a few KiB of partials and the scan's scratch.
+ *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
+ *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted graphs; no per-edge support or k-truss, no core numbers, no sampling
+ *             estimator.  A matrix that is not symmetric is not detected: the call stays within its memory (the columns are
+ *             sized by the count the fill repeats) and its counts mean nothing. */
+typedef struct lzx_triangles_info {
+    uint64_t triangles;        /* T: triangles of the graph, each counted once */
+    uint64_t wedges;           /* sum over v of d_v (d_v - 1) / 2 */
+    uint64_t max_triangles;    /* largest t_v */
+    uint64_t oriented_entries; /* entries of the oriented copy = edges that are not self loops */
+    uint32_t oriented_max_degree, reserved_;
+    double   avg_clustering;   /* (1/n) sum c_v, every vertex counted (networkx count_zeros=True) */
+    double   loop_ms, orient_ms, count_ms;  /* host clock of the call; device event time of building the oriented copy / of the counting launches */
+} lzx_triangles_info;
+int lzx_triangles(lzx_handle h, uint64_t *tri /* [n] or NULL */, double *clustering /* [n] or NULL */,
+                  lzx_triangles_info *info /* or NULL */);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

@@ -24,7 +24,7 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes")
+                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -114,6 +114,15 @@ class LzxBfsInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxTrianglesInfo(ctypes.Structure):
+    _fields_ = [("triangles", ctypes.c_uint64), ("wedges", ctypes.c_uint64), ("max_triangles", ctypes.c_uint64),
+                ("oriented_entries", ctypes.c_uint64), ("oriented_max_degree", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+                ("avg_clustering", ctypes.c_double), ("loop_ms", ctypes.c_double), ("orient_ms", ctypes.c_double), ("count_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -176,6 +185,7 @@ SYMBOLS = [
     ("lzx_set_graph_induced", ctypes.c_int, [_h, _h, _u8p, _u32p, _u64p]),
     ("lzx_bfs_multi", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _i32p, _f64p, _u64p, _u64p, _f64p, _u32p, ctypes.POINTER(LzxBfsInfo)]),
     ("lzx_betweenness_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _f64p, ctypes.POINTER(LzxBfsInfo)]),
+    ("lzx_triangles", ctypes.c_int, [_h, _u64p, _f64p, ctypes.POINTER(LzxTrianglesInfo)]),
 ]
 
 _LIB = None
@@ -958,6 +968,52 @@ class Engine:
                 scale = scale * n / ks
             bc = bc * scale
         return bc
+
+    # ---- triangles and clustering (include/lzx.h: lzx_triangles) ----
+    def triangles_raw(self, want_triangles: bool = True, want_clustering: bool = True):
+        """(tri, clustering, info) of lzx_triangles: tri[v] = the triangles through v (uint64), clustering[v] = networkx's
+        clustering coefficient (float64), both in the caller's order and None when not wanted (then that vector does not leave the
+        device); info = the lzx_triangles_info fields (triangles, wedges, max_triangles, oriented_entries, oriented_max_degree,
+        avg_clustering, loop_ms, orient_ms, count_ms)."""
+        tri = np.empty(self.n, dtype=np.uint64) if want_triangles else None
+        clus = np.empty(self.n) if want_clustering else None
+        info = LzxTrianglesInfo()
+        _check(self.L.lzx_triangles(self.h, _p(tri, _u64p) if want_triangles else None, _p(clus, _f64p) if want_clustering else None,
+                                    ctypes.byref(info)), "lzx_triangles", self.L)
+        return tri, clus, info.as_dict()
+
+    def _nodes(self, nodes, what):
+        idx = np.atleast_1d(np.asarray(nodes))
+        if idx.ndim != 1 or not (np.issubdtype(idx.dtype, np.integer) or idx.size == 0) or (idx.size and (idx.min() < 0 or idx.max() >= self.n)):
+            raise ValueError(f"{what}: nodes must be a 1-D sequence of integer vertex ids in [0, {self.n})")
+        return idx.astype(np.int64)
+
+    def triangles(self, nodes=None):
+        """networkx.triangles: the number of triangles through every vertex (uint64 array, caller's order), or through `nodes`."""
+        tri = self.triangles_raw(want_clustering=False)[0]
+        return tri if nodes is None else tri[self._nodes(nodes, "triangles")]
+
+    def clustering(self, nodes=None):
+        """networkx.clustering of an unweighted, undirected graph: 2 t_v / (d_v (d_v - 1)) with d_v the neighbours other than v
+        itself, 0 where d_v < 2 (float64 array, caller's order), or of `nodes`."""
+        clus = self.triangles_raw(want_triangles=False)[1]
+        return clus if nodes is None else clus[self._nodes(nodes, "clustering")]
+
+    def transitivity(self):
+        """networkx.transitivity: 3 T / wedges, formed from networkx's own operands (6 T and 2 wedges, Python integers); 0 for a
+        graph without a triangle.  No n-vector leaves the device."""
+        info = self.triangles_raw(want_triangles=False, want_clustering=False)[2]
+        T, wedges = int(info["triangles"]), int(info["wedges"])
+        return 0.0 if T == 0 else (6 * T) / (2 * wedges)
+
+    def average_clustering(self, count_zeros: bool = True):
+        """networkx.average_clustering.  count_zeros=True: the mean over every vertex, formed on the device (no n-vector leaves
+        it); False: the mean of the non-zero coefficients, from the downloaded vector (0.0 when there is none)."""
+        if count_zeros:
+            return self.triangles_raw(want_triangles=False, want_clustering=False)[2]["avg_clustering"]
+        clus = self.triangles_raw(want_triangles=False)[1]
+        nz = clus[clus > 0.0]
+        return float(nz.sum() / len(nz)) if len(nz) else 0.0
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

@@ -159,6 +159,10 @@ static const Option g_options[] = {
     {"solve_poll", &lzx_ctx::solve_poll_opt, OPT_SHAPE},
     // lzx_bfs_multi / lzx_betweenness_f64: a state of more than this many bytes is out of device memory
     {"bfs_state_bytes", &lzx_ctx::bfs_cap_opt, OPT_SHAPE},
+    // lzx_triangles: oriented lists longer than this take the wide kernel (and only lists of at most 32 times this are staged in LDS);
+    // a state of more than this many bytes is out of device memory
+    {"tri_long_list", &lzx_ctx::tri_long_opt, OPT_SHAPE},
+    {"tri_state_bytes", &lzx_ctx::tri_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

@@ -359,6 +359,8 @@ struct lzx_ctx {
     int64_t solve_cap_opt = -1;        // test shape solve_state_bytes: lzx_solve_shifted_f64 and lzx_pagerank_f64 treat a state larger than this as out of device memory
     int64_t solve_poll_opt = -1;       // test shape solve_poll: iterations between the status polls of those two (default 16)
     int64_t bfs_cap_opt = -1;          // test shape bfs_state_bytes: lzx_bfs_multi and lzx_betweenness_f64 treat a state larger than this as out of device memory
+    int64_t tri_long_opt = -1;         // test shape tri_long_list: out-entries beyond which lzx_triangles gives a row to its wide kernel (<= 0: LZX_TRI_LONG)
+    int64_t tri_cap_opt = -1;          // test shape tri_state_bytes: lzx_triangles treats a state larger than this as out of device memory
 };
 
 // ---- lzx_graph.hip ----

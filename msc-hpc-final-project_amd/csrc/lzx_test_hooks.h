@@ -16,7 +16,10 @@
 // chunk of a split row in the batched SpMM of lzx_multi.hip; default 2048), "eig_basis_bytes" (lzx_eigsh_f64 takes a basis larger than this
 // many bytes as out of device memory), "solve_state_bytes" (the same for the state of lzx_solve_shifted_f64 and of lzx_pagerank_f64), "solve_poll" (iterations
 // between the status polls of those two; default 16), "bfs_state_bytes" (lzx_bfs_multi and lzx_betweenness_f64 take a state larger than this many
-// bytes as out of device memory; their long rows are the batched SpMM's: "multi_row_chunk").
+// bytes as out of device memory; their long rows are the batched SpMM's: "multi_row_chunk"), "tri_long_list" (lzx_triangles: a row of the
+// oriented copy with more than this many entries is counted by the wide kernel, a workgroup per row and a wavefront per out-edge, and only
+// lists of at most 32 times this many entries, 4096 at the most, are staged in LDS there; default 128), "tri_state_bytes" (lzx_triangles
+// takes a state larger than this many bytes as out of device memory).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"

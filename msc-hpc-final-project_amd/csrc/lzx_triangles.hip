@@ -1,0 +1,510 @@
+// lzx_triangles.hip -- triangles per vertex, clustering coefficients, transitivity and average clustering of the handle's graph,
+// on the device over the caller-order CSR the handle keeps (d_row_ptr / d_col_idx): include/lzx.h, lzx_triangles; DESIGN.md
+// section 18.
+//
+// Orientation.  d_v = the entries of row v without the diagonal.  Vertices are ranked by (d_v, v) and every edge that is not a
+// self loop is kept once, in the row of its lower-ranked end: the oriented CSR (64-bit row pointers, u32 columns).
+//   degrees    k_tri_degrees           one thread per row: the row's length, minus one if a binary search finds v in it
+//   out-counts k_tri_orient (count)    a group of G lanes per row counts the neighbours of higher rank; hipcub's exclusive scan
+//                                      turns the counts into the row pointers, in place
+//   fill       k_tri_orient (fill)     the same walk writes them: a ballot over the group orders the kept entries, so the
+//                                      columns stay ascending by id (a monotone filter of an ascending row)
+// A vertex of out-degree k has k neighbours of degree >= k: k^2 <= nnz, every oriented list has fewer than 2^16 entries while
+// nnz < 2^32.
+//
+// Counting.  A triangle of ranks a < b < c is found exactly once, as c in N+(a) n N+(b) while row a handles its out-edge a -> b:
+// the shorter of the two lists is walked, the longer binary-searched.  A hit adds 1 to t_c; per out-edge the hits are added to
+// t_b in one add (when non-zero), per row their total to t_a in one add.
+//   k_tri_count        rows of at most long_list out-entries: G lanes per row, the out-edges one after the other, the lanes
+//                      over the walked list
+//   k_tri_count_long   rows of more: a workgroup per (row, slice of its out-edges), a wavefront per out-edge.  N+(a) is staged
+//                      in LDS when it has at most `stage` entries (<= LZX_TRI_STAGE), and then the hits on c are first counted
+//                      in LDS, next to the staged entry, and leave with one add per entry; a longer list is read where it lies
+//                      and every hit is its own add.
+// Every add is a 64-bit integer vector atomic (32-bit in LDS): the counts do not depend on the order in which they land, nor on
+// how ties in the ranking could have fallen.  No kernel waits on another workgroup; every loop is bounded by a list length.
+//
+// Statistics.  k_tri_stats forms c_v = 2 t_v / (d_v (d_v - 1)) (one correctly rounded division; 0 where d_v < 2 or t_v = 0) and
+// block partials of sum c (fp64), sum t, sum d (d - 1) / 2 (u64) and max t; k_tri_close adds them in a fixed order.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+
+#include "lzx_internal.h"
+#include "lzx_spmv_body.h"
+#include "lzx_reduce.h"
+
+typedef unsigned long long ull;
+
+static constexpr u32 LZX_TRI_BLOCK = 256;
+static constexpr u32 LZX_TRI_STAT_GRID = 1024;   // block partials of the statistics pass (at most)
+static constexpr u32 LZX_TRI_LONG = 128;         // out-entries beyond which a row goes to k_tri_count_long (test shape tri_long_list)
+static constexpr u32 LZX_TRI_STAGE = 4096;       // entries of N+(a) staged in LDS by k_tri_count_long (at most)
+static constexpr u32 LZX_TRI_SLICES = 64;        // workgroups a long row's out-edges are dealt to (at most)
+
+// first position in the ascending list[0 .. len) whose entry is >= x
+__device__ __forceinline__ u32 tri_lower_bound(const u32 *list, u32 len, u32 x)
+{
+    u32 lo = 0, hi = len;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (list[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(LZX_TRI_BLOCK) k_tri_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 n)
+{
+    const u64 v = (u64)blockIdx.x * LZX_TRI_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const u64 beg = row_ptr[v];
+    const u32 len = (u32)(row_ptr[v + 1] - beg);
+    const u32 at = tri_lower_bound(col_idx + beg, len, (u32)v);
+    deg[v] = len - ((at < len && col_idx[beg + at] == (u32)v) ? 1u : 0u);
+}
+
+// G lanes per row.  fill == nullptr: count[row] = the neighbours of higher rank (and count[n] = 0, kmax = the largest count);
+// otherwise they are written in their order behind row_ptr_out[row].
+template <u32 G>
+__global__ void __launch_bounds__(LZX_TRI_BLOCK)
+k_tri_orient(const u64 *row_ptr, const u32 *col_idx, const u32 *deg, u32 n, u64 *count, const u64 *row_ptr_out, u32 *fill, u32 *kmax)
+{
+    constexpr ull group_mask = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
+    const u32 sub = threadIdx.x & (G - 1);
+    const u32 shift = (threadIdx.x & 63) & ~(G - 1);
+    const u64 row = (u64)blockIdx.x * (LZX_TRI_BLOCK / G) + threadIdx.x / G;
+    u64 beg = 0, end = 0, out0 = 0;
+    u32 dv = 0;
+    if (row < n) {
+        beg = row_ptr[row];
+        end = row_ptr[row + 1];
+        dv = deg[row];
+        if (fill) out0 = row_ptr_out[row];
+    }
+    u32 kept = 0;
+    for (u64 e0 = beg; e0 < end; e0 += G) {   // (the same trips for every lane of the group)
+        const u64 e = e0 + sub;
+        bool k = false;
+        u32 col = 0;
+        if (e < end) {
+            col = col_idx[e];
+            if (col != (u32)row) {
+                const u32 du = deg[col];
+                k = du > dv || (du == dv && col > (u32)row);
+            }
+        }
+        const ull m = (__ballot(k) >> shift) & group_mask;
+        if (fill && k) fill[out0 + kept + __builtin_popcountll(m & ((1ull << sub) - 1ull))] = col;
+        kept += (u32)__builtin_popcountll(m);
+    }
+    if (fill) return;
+    if (sub == 0 && row < n) count[row] = kept;
+    if (row == 0 && sub == 0) count[n] = 0;
+    u32 mx = kept;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (u32)__shfl_xor((int)mx, o, 64));
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(kmax, mx);
+}
+
+// rows of at most long_list out-entries: G lanes per row, 256 / G rows per workgroup
+template <u32 G>
+__global__ void __launch_bounds__(LZX_TRI_BLOCK)
+k_tri_count(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list)
+{
+    const u32 sub = threadIdx.x & (G - 1);
+    const u64 row = (u64)blockIdx.x * (LZX_TRI_BLOCK / G) + threadIdx.x / G;
+    u64 beg = 0;
+    u32 ka = 0;
+    if (row < n) {
+        beg = orp[row];
+        const u64 len = orp[row + 1] - beg;
+        ka = len > long_list ? 0u : (u32)len;   // k_tri_count_long's
+    }
+    const u32 *A = oci + beg;
+    u32 total = 0;
+    for (u32 i = 0; i < ka; ++i) {   // (the same trips for every lane of the group)
+        const u32 b = A[i];
+        const u64 bb = orp[b];
+        const u32 kb = (u32)(orp[b + 1] - bb);
+        const u32 *B = oci + bb;
+        const bool walk_a = ka <= kb;
+        const u32 *S = walk_a ? A : B, *L = walk_a ? B : A;
+        const u32 ks = walk_a ? ka : kb, kl = walk_a ? kb : ka;
+        u32 hits = 0;
+        for (u32 j = sub; j < ks; j += G) {
+            const u32 x = S[j];
+            const u32 at = tri_lower_bound(L, kl, x);
+            if (at < kl && L[at] == x) {
+                ++hits;
+                atomicAdd(&tri[x], 1ull);
+            }
+        }
+#pragma unroll
+        for (u32 o = G / 2; o > 0; o >>= 1) hits += (u32)__shfl_xor((int)hits, (int)o, 64);
+        if (sub == 0 && hits) atomicAdd(&tri[b], (ull)hits);
+        total += hits;
+    }
+    if (sub == 0 && total) atomicAdd(&tri[row], (ull)total);
+}
+
+// rows of more than long_list out-entries among the workgroup's 256 rows: the workgroup takes every gridDim.y-th group of four
+// out-edges of each, a wavefront per out-edge
+__global__ void __launch_bounds__(LZX_TRI_BLOCK)
+k_tri_count_long(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list, u32 stage)
+{
+    __shared__ u32 s_rows[LZX_TRI_BLOCK];
+    __shared__ u32 s_count;
+    __shared__ u32 s_a[LZX_TRI_STAGE];     // N+(a)
+    __shared__ u32 s_hit[LZX_TRI_STAGE];   // hits on s_a[j] as the triangle's highest rank
+    __shared__ ull s_tot[LZX_TRI_BLOCK / 64];
+    if (threadIdx.x == 0) s_count = 0;
+    __syncthreads();
+    const u64 mine = (u64)blockIdx.x * LZX_TRI_BLOCK + threadIdx.x;
+    if (mine < n && orp[mine + 1] - orp[mine] > long_list) s_rows[atomicAdd(&s_count, 1u)] = (u32)mine;
+    __syncthreads();
+    const u32 count = s_count;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr u32 W = LZX_TRI_BLOCK / 64;
+    for (u32 r = 0; r < count; ++r) {
+        const u32 row = s_rows[r];
+        const u64 beg = orp[row];
+        const u32 ka = (u32)(orp[row + 1] - beg);
+        const u32 *A = oci + beg;
+        const bool staged = ka <= stage;   // (stage <= LZX_TRI_STAGE)
+        if (staged)
+            for (u32 j = threadIdx.x; j < ka; j += LZX_TRI_BLOCK) {
+                s_a[j] = A[j];
+                s_hit[j] = 0;
+            }
+        __syncthreads();
+        ull total = 0;
+        for (u32 i = blockIdx.y * W + wave; i < ka; i += gridDim.y * W) {   // (the same trips for every lane of the wavefront)
+            const u32 b = staged ? s_a[i] : A[i];
+            const u64 bb = orp[b];
+            const u32 kb = (u32)(orp[b + 1] - bb);
+            const u32 *B = oci + bb;
+            u32 hits = 0;
+            if (ka <= kb) {   // walk N+(a), search N+(b)
+                for (u32 j = lane; j < ka; j += 64) {
+                    const u32 x = staged ? s_a[j] : A[j];
+                    const u32 at = tri_lower_bound(B, kb, x);
+                    if (at < kb && B[at] == x) {
+                        ++hits;
+                        if (staged) atomicAdd(&s_hit[j], 1u);
+                        else atomicAdd(&tri[x], 1ull);
+                    }
+                }
+            } else {          // walk N+(b), search N+(a)
+                for (u32 j = lane; j < kb; j += 64) {
+                    const u32 x = B[j];
+                    if (staged) {
+                        const u32 at = tri_lower_bound(s_a, ka, x);
+                        if (at < ka && s_a[at] == x) {
+                            ++hits;
+                            atomicAdd(&s_hit[at], 1u);
+                        }
+                    } else {
+                        const u32 at = tri_lower_bound(A, ka, x);
+                        if (at < ka && A[at] == x) {
+                            ++hits;
+                            atomicAdd(&tri[x], 1ull);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) hits += (u32)__shfl_xor((int)hits, o, 64);
+            if (lane == 0 && hits) atomicAdd(&tri[b], (ull)hits);
+            total += hits;
+        }
+        if (lane == 0) s_tot[wave] = total;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            ull t = 0;
+            for (u32 w = 0; w < W; ++w) t += s_tot[w];
+            if (t) atomicAdd(&tri[row], t);
+        }
+        if (staged)
+            for (u32 j = threadIdx.x; j < ka; j += LZX_TRI_BLOCK)
+                if (s_hit[j]) atomicAdd(&tri[s_a[j]], (ull)s_hit[j]);
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ ull tri_wave_sum(ull v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ ull tri_wave_max(ull v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const ull other = __shfl_xor(v, o, 64);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+// c_v, and block partials: sum c (fp64), sum t, sum d (d - 1) / 2, max t
+__global__ void __launch_bounds__(LZX_TRI_BLOCK)
+k_tri_stats(const ull *tri, const u32 *deg, u32 n, double *clus, double *part_c, ull *part_t, ull *part_w, ull *part_m)
+{
+    __shared__ double s_c[LZX_TRI_BLOCK / 64];
+    __shared__ ull s_t[LZX_TRI_BLOCK / 64], s_w[LZX_TRI_BLOCK / 64], s_m[LZX_TRI_BLOCK / 64];
+    double sc = 0.0;
+    ull st = 0, sw = 0, sm = 0;
+    for (u64 i = (u64)blockIdx.x * LZX_TRI_BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * LZX_TRI_BLOCK) {
+        const ull t = tri[i], d = deg[i];
+        const ull pairs2 = d < 2 ? 0ull : d * (d - 1);
+        const double c = (pairs2 == 0 || t == 0) ? 0.0 : (double)(2 * t) / (double)pairs2;
+        clus[i] = c;
+        sc += c;
+        st += t;
+        sw += pairs2 >> 1;
+        sm = t > sm ? t : sm;
+    }
+    sc = wave_sum(sc);
+    st = tri_wave_sum(st);
+    sw = tri_wave_sum(sw);
+    sm = tri_wave_max(sm);
+    if ((threadIdx.x & 63) == 0) {
+        s_c[threadIdx.x >> 6] = sc;
+        s_t[threadIdx.x >> 6] = st;
+        s_w[threadIdx.x >> 6] = sw;
+        s_m[threadIdx.x >> 6] = sm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part_c[blockIdx.x] = ((s_c[0] + s_c[1]) + s_c[2]) + s_c[3];
+        part_t[blockIdx.x] = s_t[0] + s_t[1] + s_t[2] + s_t[3];
+        part_w[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        ull mx = s_m[0];
+        for (u32 w = 1; w < LZX_TRI_BLOCK / 64; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
+        part_m[blockIdx.x] = mx;
+    }
+}
+
+// out4: the mean of c (a double's bits), sum t, sum d (d - 1) / 2, max t
+__global__ void __launch_bounds__(LZX_VEC_BLOCK)
+k_tri_close(const double *part_c, const ull *part_t, const ull *part_w, const ull *part_m, u32 np, u32 n, ull *out4)
+{
+    __shared__ double sh[4];
+    __shared__ ull s_t[LZX_VEC_BLOCK / 64], s_w[LZX_VEC_BLOCK / 64], s_m[LZX_VEC_BLOCK / 64];
+    const double total = block_sum_fixed_256(part_c, np, sh);
+    ull st = 0, sw = 0, sm = 0;
+    for (u32 i = threadIdx.x; i < np; i += LZX_VEC_BLOCK) {
+        st += part_t[i];
+        sw += part_w[i];
+        sm = part_m[i] > sm ? part_m[i] : sm;
+    }
+    st = tri_wave_sum(st);
+    sw = tri_wave_sum(sw);
+    sm = tri_wave_max(sm);
+    if ((threadIdx.x & 63) == 0) {
+        s_t[threadIdx.x >> 6] = st;
+        s_w[threadIdx.x >> 6] = sw;
+        s_m[threadIdx.x >> 6] = sm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out4[0] = (ull)__double_as_longlong(total / (double)n);
+        out4[1] = s_t[0] + s_t[1] + s_t[2] + s_t[3];
+        out4[2] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        ull mx = s_m[0];
+        for (u32 w = 1; w < LZX_VEC_BLOCK / 64; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
+        out4[3] = mx;
+    }
+}
+
+namespace {
+struct TriRun {   // everything the call allocates: gone on every return path
+    lzx_ctx *c = nullptr;
+    void *arena = nullptr, *tmp = nullptr, *oci = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~TriRun()
+    {
+        if (c) {
+            (void)hipSetDevice(c->device);
+            (void)hipStreamSynchronize(c->stream);
+        }
+        if (arena) (void)hipFree(arena);
+        if (tmp) (void)hipFree(tmp);
+        if (oci) (void)hipFree(oci);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+}   // namespace
+
+template <u32 G>
+static void launch_orient(hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
+{
+    const u32 rows_per_block = LZX_TRI_BLOCK / G;
+    const u32 grid = (u32)((c->n + rows_per_block - 1) / rows_per_block);
+    hipLaunchKernelGGL(k_tri_orient<G>, dim3(grid), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg, (u32)c->n, count, orp, fill, kmax);
+}
+
+static void orient_pass(u32 G, hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
+{
+    switch (G) {
+    case 4: launch_orient<4>(st, c, deg, count, orp, fill, kmax); break;
+    case 8: launch_orient<8>(st, c, deg, count, orp, fill, kmax); break;
+    case 16: launch_orient<16>(st, c, deg, count, orp, fill, kmax); break;
+    case 32: launch_orient<32>(st, c, deg, count, orp, fill, kmax); break;
+    default: launch_orient<64>(st, c, deg, count, orp, fill, kmax); break;
+    }
+}
+
+template <u32 G>
+static void launch_count(hipStream_t st, u32 n, const u64 *orp, const u32 *oci, ull *tri, u32 long_list)
+{
+    const u32 rows_per_block = LZX_TRI_BLOCK / G;
+    const u32 grid = (u32)(((u64)n + rows_per_block - 1) / rows_per_block);
+    hipLaunchKernelGGL(k_tri_count<G>, dim3(grid), dim3(LZX_TRI_BLOCK), 0, st, orp, oci, tri, n, long_list);
+}
+
+extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lzx_triangles_info *info)
+{
+    const char *fn_name = "lzx_triangles";
+    // what needs no device
+    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn_name);
+    if (c->comm_kind != 0 || c->world > 1)
+        LZX_FAIL(LZX_ERR_STATE, "%s: triangles are counted on one GPU handle; this handle is rank %d of a communicator of %d", fn_name, c->rank, c->world);
+    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn_name);
+    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn_name);
+    const auto t0 = std::chrono::steady_clock::now();
+    const u32 n = (u32)c->n;
+
+    // one arena: row pointers u64 [n + 1], t u64 [n], c f64 [n], the partials, the four result words, two u32 words, the degrees
+    // u32 [n]; the oriented columns u32 [oriented_entries] follow once the scan has counted them
+    const u64 n_al = ((u64)n + 1) & ~1ull;
+    const u32 np = (u32)std::min<u64>(LZX_TRI_STAT_GRID, ((u64)n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK);
+    const u64 bytes = sizeof(u64) * ((u64)n + 1) + sizeof(ull) * n + sizeof(double) * n + (u64)np * (sizeof(double) + 3 * sizeof(ull)) +
+                      4 * sizeof(ull) + 2 * sizeof(u32) + sizeof(u32) * n_al;
+    if (c->tri_cap_opt >= 0 && bytes > (u64)c->tri_cap_opt)
+        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (row pointers, degrees, counts, coefficients, before the oriented columns) needs %llu bytes of device memory",
+                 fn_name, n, (unsigned long long)bytes);
+    LZX_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TriRun run;
+    run.c = c;
+#define LZX_TRI_ALLOC(ptr, size, what)                                                                                                     \
+    do {                                                                                                                                   \
+        const hipError_t e_ = hipMalloc(&(ptr), (size));                                                                                   \
+        if (e_ != hipSuccess) {                                                                                                            \
+            (void)hipGetLastError();                                                                                                       \
+            (ptr) = nullptr;                                                                                                               \
+            LZX_FAIL(e_ == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: %s of %u vertices needs %llu bytes of device memory: %s", \
+                     fn_name, what, n, (unsigned long long)(size), hipGetErrorString(e_));                                                 \
+        }                                                                                                                                  \
+    } while (0)
+    LZX_TRI_ALLOC(run.arena, bytes, "the state (row pointers, degrees, counts, coefficients)");
+    u64 *d_orp = static_cast<u64 *>(run.arena);
+    ull *d_tri = reinterpret_cast<ull *>(d_orp + n + 1);
+    double *d_clus = reinterpret_cast<double *>(d_tri + n);
+    double *d_pc = d_clus + n;
+    ull *d_pt = reinterpret_cast<ull *>(d_pc + np), *d_pw = d_pt + np, *d_pm = d_pw + np, *d_out = d_pm + np;
+    u32 *d_kmax = reinterpret_cast<u32 *>(d_out + 4);
+    u32 *d_deg = d_kmax + 2;
+    const size_t scan_len = (size_t)n + 1;   // (hipcub takes the count's type from its argument: not limited to 2^31)
+    size_t tmp_bytes = 0;
+    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_orp, d_orp, scan_len, st));
+    tmp_bytes = std::max<size_t>(tmp_bytes, 16);
+    LZX_TRI_ALLOC(run.tmp, tmp_bytes, "the scan's scratch for the row pointers");
+    LZX_HIP(hipEventCreate(&run.ev0));
+    LZX_HIP(hipEventCreate(&run.ev1));
+
+    // ---- the oriented copy ----
+    const u64 mean = c->nnz / std::max<u64>(c->n_active, 1);
+    u32 Go = 4;
+    while (Go < 64 && 2 * Go <= mean) Go *= 2;
+    const u32 gb = (n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK;
+    LZX_HIP(hipEventRecord(run.ev0, st));
+    LZX_HIP(hipMemsetAsync(d_kmax, 0, 2 * sizeof(u32), st));
+    LZX_HIP(hipMemsetAsync(d_tri, 0, sizeof(ull) * n, st));
+    hipLaunchKernelGGL(k_tri_degrees, dim3(gb), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, n);
+    LZX_HIP(hipGetLastError());
+    orient_pass(Go, st, c, d_deg, d_orp, nullptr, nullptr, d_kmax);
+    LZX_HIP(hipGetLastError());
+    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(run.tmp, tmp_bytes, d_orp, d_orp, scan_len, st));
+    u64 m = 0;
+    u32 kmax = 0;
+    LZX_HIP(hipMemcpyAsync(&m, d_orp + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipMemcpyAsync(&kmax, d_kmax, sizeof(u32), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    // the oriented columns: the scan's total, which is what the fill writes whatever was handed over ((nnz - self loops) / 2 of a
+    // symmetric matrix)
+    const u64 col_bytes = sizeof(u32) * std::max<u64>(m, 1);
+    if (c->tri_cap_opt >= 0 && bytes + col_bytes > (u64)c->tri_cap_opt)
+        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (an oriented copy of %llu entries, degrees, counts, coefficients) needs %llu bytes of device memory", fn_name,
+                 n, (unsigned long long)m, (unsigned long long)(bytes + col_bytes));
+    LZX_TRI_ALLOC(run.oci, col_bytes, "the oriented copy's columns");
+#undef LZX_TRI_ALLOC
+    u32 *d_oci = static_cast<u32 *>(run.oci);
+    if (m) {
+        orient_pass(Go, st, c, d_deg, nullptr, d_orp, d_oci, nullptr);
+        LZX_HIP(hipGetLastError());
+    }
+    LZX_HIP(hipEventRecord(run.ev1, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    float orient_ms = 0.f;
+    LZX_HIP(hipEventElapsedTime(&orient_ms, run.ev0, run.ev1));
+
+    // ---- counting: lanes per row about half the mean oriented degree ----
+    const u64 mean_out = m / std::max<u64>(c->n_active, 1);
+    u32 G = 4;
+    while (G < 32 && 2 * G <= mean_out) G *= 2;
+    const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
+    const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
+    LZX_HIP(hipEventRecord(run.ev0, st));
+    if (m) {
+        switch (G) {
+        case 4: launch_count<4>(st, n, d_orp, d_oci, d_tri, long_list); break;
+        case 8: launch_count<8>(st, n, d_orp, d_oci, d_tri, long_list); break;
+        case 16: launch_count<16>(st, n, d_orp, d_oci, d_tri, long_list); break;
+        default: launch_count<32>(st, n, d_orp, d_oci, d_tri, long_list); break;
+        }
+        LZX_HIP(hipGetLastError());
+        if (kmax > long_list) {
+            const u32 slices = std::min<u32>(std::max<u32>(kmax / 64, 1), LZX_TRI_SLICES);
+            hipLaunchKernelGGL(k_tri_count_long, dim3(gb, slices), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n, long_list, stage);
+            LZX_HIP(hipGetLastError());
+        }
+    }
+    LZX_HIP(hipEventRecord(run.ev1, st));
+
+    // ---- coefficients and statistics ----
+    hipLaunchKernelGGL(k_tri_stats, dim3(np), dim3(LZX_TRI_BLOCK), 0, st, d_tri, d_deg, n, d_clus, d_pc, d_pt, d_pw, d_pm);
+    LZX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_tri_close, dim3(1), dim3(LZX_VEC_BLOCK), 0, st, d_pc, d_pt, d_pw, d_pm, np, n, d_out);
+    LZX_HIP(hipGetLastError());
+    ull out4[4] = {0, 0, 0, 0};
+    LZX_HIP(hipMemcpyAsync(out4, d_out, sizeof(out4), hipMemcpyDeviceToHost, st));
+    if (tri) LZX_HIP(hipMemcpyAsync(tri, d_tri, sizeof(ull) * n, hipMemcpyDeviceToHost, st));
+    if (clustering) LZX_HIP(hipMemcpyAsync(clustering, d_clus, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    float count_ms = 0.f;
+    LZX_HIP(hipEventElapsedTime(&count_ms, run.ev0, run.ev1));
+    if (info) {
+        double avg;
+        static_assert(sizeof(avg) == sizeof(out4[0]), "a double's bits in a 64-bit word");
+        memcpy(&avg, &out4[0], sizeof(avg));
+        info->triangles = out4[1] / 3;
+        info->wedges = out4[2];
+        info->max_triangles = out4[3];
+        info->oriented_entries = m;
+        info->oriented_max_degree = kmax;
+        info->reserved_ = 0;
+        info->avg_clustering = avg;
+        info->orient_ms = orient_ms;
+        info->count_ms = count_ms;
+        info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return LZX_OK;
+}
