@@ -128,10 +128,7 @@ k_eig_update(const double *__restrict__ Q, u32 ldq, u32 J, const double *__restr
         nrm += x.y * x.y;
     }
     if (!npart) return;
-    nrm = wave_sum(nrm);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = nrm;
-    __syncthreads();
-    if (threadIdx.x == 0) npart[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(nrm, sh, npart);
 }
 
 // beta = sqrt(sum of npart) closed by every workgroup; beta <= stop: beta = 0 and q_next = 0 (the breakdown rule);
@@ -196,10 +193,7 @@ k_eig_resid(const double *__restrict__ v, const double *__restrict__ x, double t
         s += dx * dx;
         s += dy * dy;
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) npart[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(s, sh, npart);
 }
 
 // probe p of seed in the caller's order (include/lzx.h: lzx_probes_f64)
@@ -410,11 +404,6 @@ struct EigRun {
 };
 }  // namespace
 
-static inline double ms_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, double tol, uint32_t max_restarts, const double *x0,
                              uint64_t seed, const double *W, uint32_t nw, double *evals, double *evecs, double *resid, lzx_eig_info *info)
 {
@@ -545,7 +534,7 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
         }
         const bool done = !brk && conv >= nev;
         if (done || restarts >= max_restarts || exhausted) {
-            host_ms += ms_since(th0);
+            host_ms += lzx_ms_since(th0);
             break;
         }
         // thick restart: keep p wanted-most Ritz vectors
@@ -557,7 +546,7 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
         for (u32 i = 0; i < p; ++i) Hh[(size_t)i * m + i] = th[i];
         if (!brk)
             for (u32 i = 0; i < p; ++i) Hh[(size_t)p * m + i] = bh[m - 1] * Yfull[(size_t)(m - 1) * m + i];
-        host_ms += ms_since(th0);
+        host_ms += lzx_ms_since(th0);
         LZX_HIP(hipEventRecord(r.ev[0], c->stream));
         LZX_TRY(r.rotate(nw, me, Yr, ldy, p));
         if (!brk) LZX_HIP(hipMemcpyAsync(r.col(nw + p), r.col(nw + m), sizeof(double) * c->ldq, hipMemcpyDeviceToDevice, c->stream));
@@ -614,7 +603,7 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
         info->restarts = restarts;
         info->matvecs = matvecs;
         info->m = m;
-        info->loop_ms = ms_since(t_start);
+        info->loop_ms = lzx_ms_since(t_start);
         info->spmv_ms = r.spmv_ms;
         info->orth_ms = r.orth_ms;
         info->host_ms = host_ms;

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -388,6 +390,124 @@ int lzx_cgs_normalise(lzx_ctx *c, const double *w, double *q, const LzxCgsScratc
 // column i of Q made unit, orthogonalised against columns [0, i), made unit again; its final norm (0: it lay in their span,
 // relative 1e-10) -> *beta_out (device)
 int lzx_cgs_orthonormalise(lzx_ctx *c, double *Q, u32 i, const LzxCgsScratch &s, double *beta_out);
+
+// ---- lzx_solve.hip: the multi-shift CG loop under lzx_solve_shifted_f64 and lzx_pagerank_f64 (lzx_pagerank.hip), and the host
+// scaffolding those two share with lzx_solve_multi_f64 (lzx_solve_multi.hip) ----
+static constexpr u32 LZX_SOLVE_MAX_NS = 16;
+struct CgState {
+    double rr;                  // r_j . r_j
+    double alpha_prev, beta_prev;   // alpha_{j-1}, beta_{j-1} of the seed (1 and 0 at j = 0)
+    double curv;                // done == 2: p . S p of the iteration that failed
+    double zeta[LZX_SOLVE_MAX_NS];       // zeta_{s,j} (slot 0, the seed: 1)
+    double zeta_prev[LZX_SOLVE_MAX_NS];  // zeta_{s,j-1}
+    u32 live;                   // bit s: x_s (and p_s) are still written
+    u32 done;                   // 0 running, 1 every shift frozen, 2 S(sigma_0) is not positive definite
+    u32 err_iter;               // done == 2: the iteration
+    u32 iters[LZX_SOLVE_MAX_NS];   // the iteration count at which shift s froze
+};
+struct CgMid {                  // k_cg_update (workgroup 0) -> k_cg_direction of the same iteration
+    double alpha, curv;
+    u32 err;
+};
+// Every product and norm is the plain one, or (deg != nullptr, the kernels' DEG form) the one weighted by w_i = max(d_i, 1).
+struct CgArgs {
+    double *r, *p, *x0;         // the seed's vectors
+    const double *w;            // M p (the SpMV's output)
+    const u32 *deg;             // DEG: d_i in the internal order (0 on padding and tail); otherwise null
+    double *X, *P;              // x_s, p_s of shift s >= 1 at (s - 1) * ldq
+    u32 ldq, n;                 // n: rows streamed (n_loc_pad, even)
+    u32 ns;                     // distinct shifts
+    double sigma0, sgn;         // S p = sigma0 p - sgn (M p): sgn = 1 under A, -1 under L; DEG: S p = sigma0 p - (M p) / d, sgn unused
+    double tolb;                // tol ||b||
+    double delta[LZX_SOLVE_MAX_NS];   // sigma_s - sigma0
+    const double *pp;           // partials of p . p: at entry those of ||b||^2, from iteration 1 on pp_part
+    u32 npp;
+    const double *pm;           // partials of p . M p (the SpMV, or k_lap_apply under L)
+    u32 npm;
+    double *rr_part, *pp_part;  // [lzx_cgs_grid] written by k_cg_update / k_cg_direction
+    CgState *st;                // [2]
+    CgMid *mid;
+};
+__device__ __forceinline__ double lzx_deg_weight(u32 d) { return d ? (double)d : 1.0; }
+
+// what a CG call holds on the device; its end waits for the stream and gives everything back
+struct LzxCgRun {
+    lzx_ctx *c = nullptr;
+    double *d_V = nullptr;       // vectors
+    double *d_s = nullptr;       // partials, scalars, the two state copies
+    std::vector<hipEvent_t> ev;
+    void release()
+    {
+        if (c) {
+            (void)hipSetDevice(c->device);
+            (void)hipStreamSynchronize(c->stream);
+        }
+        if (d_V) (void)hipFree(d_V);
+        if (d_s) (void)hipFree(d_s);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        d_V = d_s = nullptr;
+        ev.clear();
+    }
+    ~LzxCgRun() { release(); }
+};
+struct LzxCgLoop {
+    u32 launched = 0;
+    double spmv_ms = 0.0, vec_ms = 0.0;   // event time of the operator / of the vector kernels
+};
+inline double lzx_ms_since(std::chrono::steady_clock::time_point t)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+// *out = alloc_bytes of device memory for a state of state_bytes (`what` describes it), or the error: a state above the test
+// shape solve_state_bytes counts as out of device memory
+int lzx_cg_alloc_state(lzx_ctx *c, const char *fn, const char *what, u64 state_bytes, u64 alloc_bytes, double **out);
+// the distinct values of v[0 .. n), ascending or descending; slot[i]: the place of v[i] among them
+std::vector<double> lzx_cg_distinct(const double *v, u32 n, bool descending, std::vector<u32> &slot);
+// From b (b . b = bb; a.pp: its partials): r = p = p_s = b and both parity states, then the loop -- the SpMV of p, k_lap_apply
+// behind it where lap, k_cg_update and k_cg_direction in their plain or (a.deg) degree-weighted form -- until every shift froze,
+// the curvature failed (hs.done == 2) or maxiter.  hs: the final state.
+int lzx_cg_multishift(LzxCgRun &run, CgArgs a, const double *b, double bb, bool lap, u32 maxiter, CgState &hs, LzxCgLoop &t);
+
+// The loop of a CG entry point, no host synchronisation between two polls: iteration j queues op(j) (the SpMV or SpMM), an
+// event, vec(j) (the vector kernels) and an event.  Every `solve_poll` iterations (default 16), and after the last, the state
+// the last iteration wrote (d_st[launched & 1]) is read into hs and the events' intervals are added to t; over(hs) ends the loop.
+template <typename State, typename Op, typename Vec, typename Over>
+int lzx_cg_polled_loop(LzxCgRun &run, const State *d_st, State &hs, u32 maxiter, LzxCgLoop &t, Op op, Vec vec, Over over)
+{
+    lzx_ctx *c = run.c;
+    const u32 poll = c->solve_poll_opt > 0 ? (u32)std::min<int64_t>(c->solve_poll_opt, 1024) : 16;
+    for (u32 i = 0; i < 2 * poll + 1; ++i) {
+        hipEvent_t ev;
+        LZX_HIP(hipEventCreate(&ev));
+        run.ev.push_back(ev);
+    }
+    u32 k = 0;   // iterations since the last poll
+    LZX_HIP(hipEventRecord(run.ev[0], c->stream));
+    for (u32 j = 0; j < maxiter; ++j) {
+        LZX_TRY(op(j));
+        LZX_HIP(hipEventRecord(run.ev[2 * k + 1], c->stream));
+        LZX_TRY(vec(j));
+        LZX_HIP(hipGetLastError());
+        LZX_HIP(hipEventRecord(run.ev[2 * k + 2], c->stream));
+        ++k;
+        t.launched = j + 1;
+        if (k == poll || t.launched == maxiter) {
+            LZX_HIP(hipMemcpyAsync(&hs, d_st + (t.launched & 1), sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+            LZX_HIP(hipStreamSynchronize(c->stream));
+            for (u32 i = 0; i < k; ++i) {
+                float x = 0.f, y = 0.f;
+                LZX_HIP(hipEventElapsedTime(&x, run.ev[2 * i], run.ev[2 * i + 1]));
+                LZX_HIP(hipEventElapsedTime(&y, run.ev[2 * i + 1], run.ev[2 * i + 2]));
+                t.spmv_ms += x;
+                t.vec_ms += y;
+            }
+            k = 0;
+            if (over(hs)) break;
+            LZX_HIP(hipEventRecord(run.ev[0], c->stream));
+        }
+    }
+    return LZX_OK;
+}
 
 // ---- lzx_pb.hip ----
 // Builds the propagation-blocked structure for this rank's non-hub entries. d_nh_off: exclusive prefix of the

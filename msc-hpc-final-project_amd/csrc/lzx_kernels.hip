@@ -40,10 +40,7 @@ k_long_finish(const u32 *item_first, const double *long_partial, u32 n_long, con
         v[r] = s;
         dot = s * q_loc[r];
     }
-    dot = wave_sum(dot);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = dot;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(dot, sh, partials);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -83,10 +80,7 @@ k_axpy_norm(double *v, const double *__restrict__ qj, const double *__restrict__
         nrm += w.x * w.x;
         nrm += w.y * w.y;
     }
-    nrm = wave_sum(nrm);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = nrm;
-    __syncthreads();
-    if (threadIdx.x == 0) partials_out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(nrm, sh, partials_out);
 }
 
 // Several ranks, lazy normalisation (lzx_api.hip): the vector that was exchanged and multiplied is the UNNORMALISED
@@ -193,10 +187,7 @@ k_lazy_update(const double *__restrict__ w, u32 w_rows, const double *__restrict
             nrm += t.y * t.y;
         }
     }
-    nrm = wave_sum(nrm);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = nrm;
-    __syncthreads();
-    if (threadIdx.x == 0) partials_out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(nrm, sh, partials_out);
 }
 
 // the same two sums, stored into slot [rank] of every peer's mailbox (in-process groups; lzx_internal.h: d_mail)
@@ -397,10 +388,7 @@ k_iso_sumsq(const double *q0, u32 r0, u32 r1, double *partials)
     __shared__ double sh[4];
     double s = 0.0;
     for (u32 i = r0 + blockIdx.x * LZX_VEC_BLOCK + threadIdx.x; i < r1; i += gridDim.x * LZX_VEC_BLOCK) s += q0[i] * q0[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(s, sh, partials);
 }
 
 __global__ void __launch_bounds__(LZX_VEC_BLOCK)
@@ -452,10 +440,7 @@ k_mgs_step(double *v, const double *__restrict__ q_m, const double *d_partials, 
         acc += w.x * p.x;
         acc += w.y * p.y;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials_out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    block_partial(acc, sh, partials_out);
 }
 
 // convergence monitor: per-block partials of |y - y_prev|^2 (first half of `partials`) and |y|^2 (second half)

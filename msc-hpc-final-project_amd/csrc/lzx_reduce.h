@@ -1,6 +1,15 @@
-// lzx_reduce.h -- the fixed-order block reduction every vector kernel closes the loop's partial sums with (device code;
-// include after lzx_spmv_body.h, which has wave_sum).
+// lzx_reduce.h -- the fixed-order block reduction every vector kernel closes the loop's partial sums with, and the one that
+// writes a workgroup's partial (device code; include after lzx_spmv_body.h, which has wave_sum).
 #pragma once
+
+// out[workgroup] = the sum of s over the 256 threads of the workgroup, wavefronts added in order.  sh: >= 4 doubles of LDS.
+__device__ __forceinline__ void block_partial(double s, double *sh, double *out)
+{
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
 
 // Sum p[0..np) identically in every workgroup of a 256-thread launch. sh: >= 4 doubles of LDS.
 __device__ __forceinline__ double block_sum_fixed_256(const double *p, u32 np, double *sh)

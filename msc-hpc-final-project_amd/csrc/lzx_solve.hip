@@ -1,5 +1,7 @@
 // lzx_solve.hip -- (sigma_s I - A) x_s = b or (sigma_s I + L) x_s = b for up to 16 shifts at once by multi-shift conjugate
-// gradients (Frommer 2003; Jegerlehner): include/lzx.h, lzx_solve_shifted_f64; DESIGN.md section 13.
+// gradients (Frommer 2003; Jegerlehner): include/lzx.h, lzx_solve_shifted_f64; DESIGN.md section 13.  The loop and its two
+// kernels also run PageRank (lzx_pagerank.hip) in their degree-weighted form; the first host part
+// (state allocation, distinct values, lzx_cg_multishift) is declared in lzx_internal.h and serves lzx_solve_multi.hip too.
 //
 // One Krylov sequence: plain CG on the seed system S(sigma_0) (the smallest shift), every other shift s following it through
 // the scalars zeta_s, alpha_s, beta_s.  Its residual is zeta_{s,j} r_j, so no shift needs a matvec of its own.
@@ -16,6 +18,10 @@
 // Both kernels close every sum in every workgroup with block_sum_fixed_256 (no atomics, no grid barrier): runs are bit-identical.
 // The scalars of the iteration are kept in two device copies by iteration parity: the kernels of iteration j read copy j & 1,
 // workgroup 0 of k_cg_direction writes copy (j + 1) & 1.
+//
+// Both kernels are templates on the inner product.  DEG = false: the plain one, no degree is read.  DEG = true: <a, b>_W =
+// sum w_i a_i b_i with w_i = max(d_i, 1), and S p = sigma0 p - (M p) / d (0 where d = 0).  The two forms share every line but
+// those products; neither is the other with a weight of 1 (the library is built without contraction: equal operations, equal bits).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -26,44 +32,7 @@
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
-static constexpr u32 LZX_SOLVE_MAX_NS = 16;
 static constexpr u32 LZX_SOLVE_MAX_W = 8;
-static constexpr u32 LZX_SOLVE_POLL = 16;
-
-namespace {
-struct CgState {
-    double rr;                  // r_j . r_j
-    double alpha_prev, beta_prev;   // alpha_{j-1}, beta_{j-1} of the seed (1 and 0 at j = 0)
-    double curv;                // done == 2: p . S p of the iteration that failed
-    double zeta[LZX_SOLVE_MAX_NS];       // zeta_{s,j} (slot 0, the seed: 1)
-    double zeta_prev[LZX_SOLVE_MAX_NS];  // zeta_{s,j-1}
-    u32 live;                   // bit s: x_s (and p_s) are still written
-    u32 done;                   // 0 running, 1 every shift frozen, 2 S(sigma_0) is not positive definite
-    u32 err_iter;               // done == 2: the iteration
-    u32 iters[LZX_SOLVE_MAX_NS];   // the iteration count at which shift s froze
-};
-struct CgMid {                  // k_cg_update (workgroup 0) -> k_cg_direction of the same iteration
-    double alpha, curv;
-    u32 err;
-};
-struct CgArgs {
-    double *r, *p, *x0;         // the seed's vectors
-    const double *w;            // M p (the SpMV's output)
-    double *X, *P;              // x_s, p_s of shift s >= 1 at (s - 1) * ldq
-    u32 ldq, n;                 // n: rows streamed (n_loc_pad, even)
-    u32 ns;                     // distinct shifts
-    double sigma0, sgn;         // S p = sigma0 p - sgn (M p): sgn = 1 under A, -1 under L
-    double tolb;                // tol ||b||
-    double delta[LZX_SOLVE_MAX_NS];   // sigma_s - sigma0
-    const double *pp;           // partials of p . p (k_cg_direction of the previous iteration, or of ||b||^2)
-    u32 npp;
-    const double *pm;           // partials of p . M p (the SpMV, or k_lap_apply under L)
-    u32 npm;
-    double *rr_part, *pp_part;  // [gridDim.x] written by k_cg_update / k_cg_direction
-    CgState *st;                // [2]
-    CgMid *mid;
-};
-}  // namespace
 
 // o = s word by word (a struct copy through registers would be indexed dynamically: scratch)
 __device__ __forceinline__ void copy_state(CgState &o, const CgState &s)
@@ -74,16 +43,9 @@ __device__ __forceinline__ void copy_state(CgState &o, const CgState &s)
     for (u32 i = 0; i < sizeof(CgState) / 8; ++i) dst[i] = src[i];
 }
 
-__device__ __forceinline__ void block_partial(double s, double *sh, double *out)
-{
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 // p . S p closed, alpha_j = r.r / p.Sp; not positive (or not finite): the error is recorded, nothing written.
-// r -= alpha_j (sigma0 p - sgn w), x_0 += alpha_j p while the seed is live; partials of r . r.
+// r -= alpha_j S p, x_0 += alpha_j p while the seed is live; partials of r . r.
+template <bool DEG>
 __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_update(CgArgs a, u32 j)
 {
     __shared__ double sh[4];
@@ -91,7 +53,9 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_update(CgArgs a, u32 j)
     if (s.done) return;
     const double pp = block_sum_fixed_256(a.pp, a.npp, sh);
     const double pm = block_sum_fixed_256(a.pm, a.npm, sh);
-    const double curv = a.sigma0 * pp - a.sgn * pm;
+    double curv;   // <p, P p>_W = p . (A p): the SpMV's partials as they stand
+    if constexpr (DEG) curv = a.sigma0 * pp - pm;
+    else curv = a.sigma0 * pp - a.sgn * pm;
     const bool bad = !(curv > 0.0) || !isfinite(curv);
     const double alpha = s.rr / curv;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -106,9 +70,17 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_update(CgArgs a, u32 j)
     for (u32 i = (blockIdx.x * LZX_VEC_BLOCK + threadIdx.x) * 2; i < a.n; i += stride) {
         const double2 p = *reinterpret_cast<const double2 *>(a.p + i);
         const double2 w = *reinterpret_cast<const double2 *>(a.w + i);
+        uint2 d = make_uint2(0, 0);
+        if constexpr (DEG) d = *reinterpret_cast<const uint2 *>(a.deg + i);
         double2 r = *reinterpret_cast<const double2 *>(a.r + i);
-        r.x -= alpha * (a.sigma0 * p.x - a.sgn * w.x);
-        r.y -= alpha * (a.sigma0 * p.y - a.sgn * w.y);
+        if constexpr (DEG) {
+            const double qx = d.x ? w.x / (double)d.x : 0.0, qy = d.y ? w.y / (double)d.y : 0.0;
+            r.x -= alpha * (a.sigma0 * p.x - qx);
+            r.y -= alpha * (a.sigma0 * p.y - qy);
+        } else {
+            r.x -= alpha * (a.sigma0 * p.x - a.sgn * w.x);
+            r.y -= alpha * (a.sigma0 * p.y - a.sgn * w.y);
+        }
         *reinterpret_cast<double2 *>(a.r + i) = r;
         if (seed) {
             double2 x = *reinterpret_cast<const double2 *>(a.x0 + i);
@@ -116,8 +88,13 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_update(CgArgs a, u32 j)
             x.y += alpha * p.y;
             *reinterpret_cast<double2 *>(a.x0 + i) = x;
         }
-        acc += r.x * r.x;
-        acc += r.y * r.y;
+        if constexpr (DEG) {
+            acc += lzx_deg_weight(d.x) * (r.x * r.x);
+            acc += lzx_deg_weight(d.y) * (r.y * r.y);
+        } else {
+            acc += r.x * r.x;
+            acc += r.y * r.y;
+        }
     }
     block_partial(acc, sh, a.rr_part);
 }
@@ -125,6 +102,7 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_update(CgArgs a, u32 j)
 // r.r closed, beta_j; per shift zeta_{j+1}, alpha_s, beta_s and the freeze rule |zeta_{s,j+1}| ||r_{j+1}|| <= tol ||b|| (the seed:
 // ||r_{j+1}|| <= tol ||b||), the same in every workgroup; workgroup 0 writes the next state.  p = r + beta_j p (partials of
 // p . p); for each shift s >= 1 live at entry: x_s += alpha_s p_s, and p_s = zeta r + beta_s p_s unless it froze just now.
+template <bool DEG>
 __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_direction(CgArgs a, u32 j)
 {
     __shared__ double sh[4];
@@ -183,12 +161,19 @@ __global__ void __launch_bounds__(LZX_VEC_BLOCK) k_cg_direction(CgArgs a, u32 j)
     const u32 stride = gridDim.x * LZX_VEC_BLOCK * 2;
     for (u32 i = (blockIdx.x * LZX_VEC_BLOCK + threadIdx.x) * 2; i < a.n; i += stride) {
         const double2 r = *reinterpret_cast<const double2 *>(a.r + i);
+        uint2 d = make_uint2(0, 0);
+        if constexpr (DEG) d = *reinterpret_cast<const uint2 *>(a.deg + i);
         double2 p = *reinterpret_cast<const double2 *>(a.p + i);
         p.x = r.x + beta * p.x;
         p.y = r.y + beta * p.y;
         *reinterpret_cast<double2 *>(a.p + i) = p;
-        acc += p.x * p.x;
-        acc += p.y * p.y;
+        if constexpr (DEG) {
+            acc += lzx_deg_weight(d.x) * (p.x * p.x);
+            acc += lzx_deg_weight(d.y) * (p.y * p.y);
+        } else {
+            acc += p.x * p.x;
+            acc += p.y * p.y;
+        }
         for (u32 u = 1; u < a.ns; ++u) {
             if (!((live >> u) & 1u)) continue;
             double *xs = a.X + (size_t)(u - 1) * a.ldq + i, *ps = a.P + (size_t)(u - 1) * a.ldq + i;
@@ -227,31 +212,72 @@ k_cg_resid(const double *__restrict__ b, const double *__restrict__ x, const dou
     block_partial(acc, sh, part);
 }
 
-// ==================================================================================================== host
-namespace {
-struct SolveRun {
-    lzx_ctx *c = nullptr;
-    double *d_V = nullptr;       // vectors, see the layout above
-    double *d_s = nullptr;       // scratch
-    std::vector<hipEvent_t> ev;
-    ~SolveRun()
-    {
-        if (c) {
-            (void)hipSetDevice(c->device);
-            (void)hipStreamSynchronize(c->stream);
-        }
-        if (d_V) (void)hipFree(d_V);
-        if (d_s) (void)hipFree(d_s);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t)
+// ==================================================================================================== host: shared by the CG entry points
+int lzx_cg_alloc_state(lzx_ctx *c, const char *fn, const char *what, u64 state_bytes, u64 alloc_bytes, double **out)
 {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    const bool capped = c->solve_cap_opt >= 0 && state_bytes > (u64)c->solve_cap_opt;
+    const hipError_t e = capped ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void **>(out), alloc_bytes);
+    if (e == hipSuccess) return LZX_OK;
+    (void)hipGetLastError();
+    *out = nullptr;
+    LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the state of %s needs %llu bytes of device memory: %s", fn, what,
+             (unsigned long long)state_bytes, hipGetErrorString(e));
 }
-}  // namespace
 
+std::vector<double> lzx_cg_distinct(const double *v, u32 n, bool descending, std::vector<u32> &slot)
+{
+    const auto before = [descending](double x, double y) { return descending ? x > y : x < y; };
+    std::vector<double> uq(v, v + n);
+    std::sort(uq.begin(), uq.end(), before);
+    uq.erase(std::unique(uq.begin(), uq.end()), uq.end());
+    slot.resize(n);
+    for (u32 s = 0; s < n; ++s) slot[s] = (u32)(std::lower_bound(uq.begin(), uq.end(), v[s], before) - uq.begin());
+    return uq;
+}
+
+int lzx_cg_multishift(LzxCgRun &run, CgArgs a, const double *b, double bb, bool lap, u32 maxiter, CgState &hs, LzxCgLoop &t)
+{
+    lzx_ctx *c = run.c;
+    const u32 G = lzx_cgs_grid(c);
+    // r = p = p_s = b, the state of iteration 0
+    LZX_HIP(hipMemcpyAsync(a.r, b, sizeof(double) * a.ldq, hipMemcpyDeviceToDevice, c->stream));
+    LZX_HIP(hipMemcpyAsync(a.p, b, sizeof(double) * a.ldq, hipMemcpyDeviceToDevice, c->stream));
+    for (u32 u = 1; u < a.ns; ++u)
+        LZX_HIP(hipMemcpyAsync(a.P + (size_t)(u - 1) * a.ldq, b, sizeof(double) * a.ldq, hipMemcpyDeviceToDevice, c->stream));
+    CgState s0;
+    std::memset(&s0, 0, sizeof(s0));
+    s0.rr = bb;
+    s0.alpha_prev = 1.0;
+    for (u32 u = 0; u < LZX_SOLVE_MAX_NS; ++u) s0.zeta[u] = s0.zeta_prev[u] = 1.0;
+    s0.live = (1u << a.ns) - 1u;
+    for (u32 i = 0; i < 2; ++i) LZX_HIP(hipMemcpyAsync(a.st + i, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
+    hs = s0;
+    return lzx_cg_polled_loop(
+        run, a.st, hs, maxiter, t,
+        [&](u32) -> int {
+            SpmvLaunch l{a.p, a.p, c->d_v, c->d_partials};
+            LZX_TRY(lzx_launch_spmv(c, l));
+            if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, a.p, c->d_partials, a.npm, c->n_loc_pad));
+            return LZX_OK;
+        },
+        [&](u32 j) -> int {
+            if (j == 1) {
+                a.pp = a.pp_part;
+                a.npp = G;
+            }
+            if (a.deg) {
+                hipLaunchKernelGGL(k_cg_update<true>, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
+                hipLaunchKernelGGL(k_cg_direction<true>, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
+            } else {
+                hipLaunchKernelGGL(k_cg_update<false>, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
+                hipLaunchKernelGGL(k_cg_direction<false>, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
+            }
+            return LZX_OK;
+        },
+        [](const CgState &s) { return s.done != 0; });
+}
+
+// ==================================================================================================== host: lzx_solve_shifted_f64
 extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns, const double *shifts, double tol, uint32_t maxiter,
                                      const double *W, uint32_t nw, double *X, uint32_t *iters, double *resid, lzx_solve_info *info)
 {
@@ -277,19 +303,16 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
     if (!c->d_row_ptr || !c->d_v) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
     const bool lap = c->op_opt == LZX_OP_LAPLACIAN;
     // distinct shifts ascending: unique slot u of every caller shift; the seed is u = 0
-    std::vector<double> uq(shifts, shifts + ns);
-    std::sort(uq.begin(), uq.end());
-    uq.erase(std::unique(uq.begin(), uq.end()), uq.end());
+    std::vector<u32> slot;
+    const std::vector<double> uq = lzx_cg_distinct(shifts, ns, false, slot);
     const u32 nu = (u32)uq.size();
-    std::vector<u32> slot(ns);
-    for (u32 s = 0; s < ns; ++s) slot[s] = (u32)(std::lower_bound(uq.begin(), uq.end(), shifts[s]) - uq.begin());
     const double sigma0 = uq[0];
     if (!lap && sigma0 <= 0.0) LZX_FAIL(LZX_ERR_ARG, "%s: shift %g <= 0 under A: sigma I - A is never positive definite there", fn, sigma0);
     if (lap && sigma0 == 0.0 && nw == 0)
         LZX_FAIL(LZX_ERR_ARG, "%s: shift 0 under L needs deflation vectors (nw >= 1) spanning the null space b is orthogonal to", fn);
     const u64 n = c->n;
 
-    SolveRun run;
+    LzxCgRun run;
     run.c = c;
     LZX_HIP(hipSetDevice(c->device));
     if (lap) LZX_TRY(lzx_ensure_degrees(c));
@@ -299,19 +322,14 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
 
     const u32 ncols = 2 + 2 * nu + nw;
     const u64 state_bytes = (u64)ncols * c->ldq * sizeof(double);
-    const bool capped = c->solve_cap_opt >= 0 && state_bytes > (u64)c->solve_cap_opt;
-    hipError_t e = capped ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void **>(&run.d_V), state_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        run.d_V = nullptr;
-        LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the state of %u vectors (b, r, p, 2 per shift, %u deflation) needs %llu bytes of device memory: %s",
-                 fn, ncols, nw, (unsigned long long)state_bytes, hipGetErrorString(e));
-    }
+    char what[80];
+    std::snprintf(what, sizeof what, "%u vectors (b, r, p, 2 per shift, %u deflation)", ncols, nw);
+    LZX_TRY(lzx_cg_alloc_state(c, fn, what, state_bytes, state_bytes, &run.d_V));
     auto col = [&](u32 i) { return run.d_V + (size_t)i * c->ldq; };
     double *vb = col(0), *vr = col(1), *vp = col(2), *vx0 = col(3), *vX = col(4), *vP = col(3 + nu), *vW = col(2 + 2 * nu);
 
     const u32 Gc = lzx_cgs_grid(c);
-    const u32 G = Gc;   // the loop's two kernels: the same grid as the CGS2 launches
+    const u32 G = Gc;   // the loop's two kernels (lzx_cg_multishift): the same grid as the CGS2 launches
     const u32 st_words = (u32)((sizeof(CgState) + 7) / 8), mid_words = (u32)((sizeof(CgMid) + 7) / 8);
     const u64 scratch = (u64)std::max(nw, 1u) * Gc + 2 * LZX_SOLVE_MAX_W + Gc + 2ull * G + 64 + 2ull * st_words + mid_words;
     LZX_HIP(hipMalloc(reinterpret_cast<void **>(&run.d_s), sizeof(double) * scratch));
@@ -348,19 +366,6 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
     if (!(bb > 1e-20 * bb_in)) LZX_FAIL(LZX_ERR_ARG, "%s: b lies in the span of W", fn);
     const double bnorm = std::sqrt(bb);
 
-    // r = p = p_s = b, the state of iteration 0
-    LZX_HIP(hipMemcpyAsync(vr, vb, sizeof(double) * c->ldq, hipMemcpyDeviceToDevice, c->stream));
-    LZX_HIP(hipMemcpyAsync(vp, vb, sizeof(double) * c->ldq, hipMemcpyDeviceToDevice, c->stream));
-    for (u32 u = 1; u < nu; ++u)
-        LZX_HIP(hipMemcpyAsync(vP + (size_t)(u - 1) * c->ldq, vb, sizeof(double) * c->ldq, hipMemcpyDeviceToDevice, c->stream));
-    CgState s0;
-    std::memset(&s0, 0, sizeof(s0));
-    s0.rr = bb;
-    s0.alpha_prev = 1.0;
-    for (u32 u = 0; u < LZX_SOLVE_MAX_NS; ++u) s0.zeta[u] = s0.zeta_prev[u] = 1.0;
-    s0.live = (1u << nu) - 1u;
-    LZX_HIP(hipMemcpyAsync(d_st, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
-
     CgArgs a{};
     a.r = vr;
     a.p = vp;
@@ -375,6 +380,8 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
     a.sgn = lap ? -1.0 : 1.0;
     a.tolb = tol * bnorm;
     for (u32 u = 0; u < nu; ++u) a.delta[u] = uq[u] - sigma0;
+    a.pp = sc.npart;
+    a.npp = Gc;
     a.pm = c->d_partials;
     a.npm = lzx_spmv_partials(c);
     a.rr_part = rr_part;
@@ -382,45 +389,10 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
     a.st = d_st;
     a.mid = d_mid;
 
-    const u32 poll = c->solve_poll_opt > 0 ? (u32)std::min<int64_t>(c->solve_poll_opt, 1024) : LZX_SOLVE_POLL;
-    for (u32 i = 0; i < 2 * poll + 1; ++i) {
-        hipEvent_t ev;
-        LZX_HIP(hipEventCreate(&ev));
-        run.ev.push_back(ev);
-    }
-    CgState hs = s0;
-    double spmv_ms = 0.0, vec_ms = 0.0;
-    u32 launched = 0;
-    u32 k = 0;   // iterations since the last poll
-    LZX_HIP(hipEventRecord(run.ev[0], c->stream));
-    for (u32 j = 0; j < maxiter; ++j) {
-        SpmvLaunch l{vp, vp, c->d_v, c->d_partials};
-        LZX_TRY(lzx_launch_spmv(c, l));
-        if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, vp, c->d_partials, a.npm, c->n_loc_pad));
-        LZX_HIP(hipEventRecord(run.ev[2 * k + 1], c->stream));
-        a.pp = j == 0 ? sc.npart : pp_part;
-        a.npp = j == 0 ? Gc : G;
-        hipLaunchKernelGGL(k_cg_update, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
-        hipLaunchKernelGGL(k_cg_direction, dim3(G), dim3(LZX_VEC_BLOCK), 0, c->stream, a, j);
-        LZX_HIP(hipGetLastError());
-        LZX_HIP(hipEventRecord(run.ev[2 * k + 2], c->stream));
-        ++k;
-        launched = j + 1;
-        if (k == poll || launched == maxiter) {
-            LZX_HIP(hipMemcpyAsync(&hs, d_st + (launched & 1), sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-            LZX_HIP(hipStreamSynchronize(c->stream));
-            for (u32 i = 0; i < k; ++i) {
-                float x = 0.f, y = 0.f;
-                LZX_HIP(hipEventElapsedTime(&x, run.ev[2 * i], run.ev[2 * i + 1]));
-                LZX_HIP(hipEventElapsedTime(&y, run.ev[2 * i + 1], run.ev[2 * i + 2]));
-                spmv_ms += x;
-                vec_ms += y;
-            }
-            k = 0;
-            if (hs.done) break;
-            LZX_HIP(hipEventRecord(run.ev[0], c->stream));
-        }
-    }
+    CgState hs;
+    LzxCgLoop lp;
+    LZX_TRY(lzx_cg_multishift(run, a, vb, bb, lap, maxiter, hs, lp));
+    const u32 launched = lp.launched;
     if (hs.done == 2)
         LZX_FAIL(LZX_ERR_ARG, "%s: S(sigma_0) is not positive definite: p . S p = %.6e at iteration %u (sigma_0 = %.17g)", fn, hs.curv, hs.err_iter,
                  sigma0);
@@ -458,9 +430,9 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
         info->launched = launched;
         info->converged = conv;
         info->ns = ns;
-        info->loop_ms = ms_since(t_start);
-        info->spmv_ms = spmv_ms;
-        info->vec_ms = vec_ms;
+        info->loop_ms = lzx_ms_since(t_start);
+        info->spmv_ms = lp.spmv_ms;
+        info->vec_ms = lp.vec_ms;
         info->bnorm = bnorm;
     }
     if (conv < ns)

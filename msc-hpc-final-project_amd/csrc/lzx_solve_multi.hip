@@ -33,7 +33,6 @@
 
 static constexpr u32 LZX_MCG_MAX_NB = 16;
 static constexpr u32 LZX_MCG_MAX_W = 8;
-static constexpr u32 LZX_MCG_POLL = 16;
 static constexpr u32 LZX_MCG_WGRID = 64;   // workgroups (and partials) of the sums over one plain W column
 
 namespace {
@@ -356,21 +355,13 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_mcg_direction(McgArgs a, u3
 }
 
 // ---- the deflation vectors: plain columns of n doubles, orthonormalised once per solve
-__device__ __forceinline__ void mcg_block_partial(double s, double *sh, double *out)
-{
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 // part[workgroup] = partial of a . b (LZX_MCG_WGRID workgroups)
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_mcg_wdot(const double *__restrict__ a, const double *__restrict__ b, u64 n, double *part)
 {
     __shared__ double sh[4];
     double acc = 0.0;
     for (u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * LZX_MULTI_BLOCK) acc += a[i] * b[i];
-    mcg_block_partial(acc, sh, part);
+    block_partial(acc, sh, part);
 }
 
 // t = the closed sum of part.  mode 0: w -= t v (a projection step).  mode 1: w /= sqrt(t) where t > 0.  mode 2: the final norm
@@ -391,29 +382,14 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_mcg_wapply(double *w, const
 
 // ==================================================================================================== host
 namespace {
-struct McgRun {
-    lzx_ctx *c = nullptr;
+struct McgRun : LzxCgRun {       // d_V: b, r, p, x ([n][B] each), then W
     bool own_work = false;       // the batched path's work vectors were made (or re-made at this width) by this call
-    double *d_vec = nullptr;     // b, r, p, x ([n][B] each), then W
-    double *d_s = nullptr;       // partials, scalars, the two state copies
-    std::vector<hipEvent_t> ev;
     ~McgRun()
     {
-        if (c) {
-            (void)hipSetDevice(c->device);
-            (void)hipStreamSynchronize(c->stream);
-        }
-        if (d_vec) (void)hipFree(d_vec);
-        if (d_s) (void)hipFree(d_s);
+        release();
         if (c && own_work && c->multi) lzx_multi_free_work(c->multi);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
 };
-
-double mcg_ms_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
 
 struct McgCall {
     uint32_t nb;
@@ -444,6 +420,7 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
     run.c = c;
     const u64 part_doubles = (u64)n_seg * B;
     const u64 state_bytes = ((5ull * B + nw) * n + 3 * part_doubles) * sizeof(double);
+    // (the cap again, ahead of lzx_cg_alloc_state's: before the work vectors are made, and this text ends without a runtime error)
     if (c->solve_cap_opt >= 0 && state_bytes > (u64)c->solve_cap_opt)
         LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of 5 x %u interleaved columns and %u deflation vectors needs %llu bytes of device memory", fn, B, nw,
                  (unsigned long long)state_bytes);
@@ -451,17 +428,10 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
     // lzx_multi_ensure_work frees first), it frees them at return
     run.own_work = !(m->d_V && m->wB == B);
     LZX_TRY(lzx_multi_ensure_work(c, B, false));
-    {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&run.d_vec), sizeof(double) * (4 * nB + (u64)nw * n));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            run.d_vec = nullptr;
-            LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP,
-                     "%s: the state of 5 x %u interleaved columns and %u deflation vectors needs %llu bytes of device memory: %s", fn, B, nw,
-                     (unsigned long long)state_bytes, hipGetErrorString(e));
-        }
-    }
-    double *vB = run.d_vec, *vR = vB + nB, *vP = vR + nB, *vX = vP + nB, *vW = vX + nB;
+    char what[80];
+    std::snprintf(what, sizeof what, "5 x %u interleaved columns and %u deflation vectors", B, nw);
+    LZX_TRY(lzx_cg_alloc_state(c, fn, what, state_bytes, sizeof(double) * (4 * nB + (u64)nw * n), &run.d_V));
+    double *vB = run.d_V, *vR = vB + nB, *vP = vR + nB, *vX = vP + nB, *vW = vX + nB;
 
     // scalars: [rr partials | pp partials | W partials | tmp | state x 2 | mid]
     const u32 st_words = (u32)((sizeof(McgState) + 7) / 8), mid_words = (u32)((sizeof(McgMid) + 7) / 8);
@@ -562,40 +532,17 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
     a.st = d_st;
     a.mid = d_mid;
 
-    const u32 poll = c->solve_poll_opt > 0 ? (u32)std::min<int64_t>(c->solve_poll_opt, 1024) : LZX_MCG_POLL;
-    for (u32 i = 0; i < 2 * poll + 1; ++i) {
-        hipEvent_t ev;
-        LZX_HIP(hipEventCreate(&ev));
-        run.ev.push_back(ev);
-    }
     McgState hs = s0;
-    double spmv_ms = 0.0, vec_ms = 0.0;
-    u32 launched = 0, k = 0;   // k: iterations since the last poll
-    LZX_HIP(hipEventRecord(run.ev[0], c->stream));
-    for (u32 j = 0; j < q.maxiter; ++j) {
-        LZX_TRY(launch_spmm<B>(c, vP, m->d_V, vP));
-        LZX_HIP(hipEventRecord(run.ev[2 * k + 1], c->stream));
-        hipLaunchKernelGGL(k_mcg_update<B>, dim3(vgrid), blk, 0, c->stream, a, j);
-        hipLaunchKernelGGL(k_mcg_direction<B>, dim3(vgrid), blk, 0, c->stream, a, j);
-        LZX_HIP(hipGetLastError());
-        LZX_HIP(hipEventRecord(run.ev[2 * k + 2], c->stream));
-        ++k;
-        launched = j + 1;
-        if (k == poll || launched == q.maxiter) {
-            LZX_HIP(hipMemcpyAsync(&hs, d_st + (launched & 1), sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-            LZX_HIP(hipStreamSynchronize(c->stream));
-            for (u32 i = 0; i < k; ++i) {
-                float x = 0.f, y = 0.f;
-                LZX_HIP(hipEventElapsedTime(&x, run.ev[2 * i], run.ev[2 * i + 1]));
-                LZX_HIP(hipEventElapsedTime(&y, run.ev[2 * i + 1], run.ev[2 * i + 2]));
-                spmv_ms += x;
-                vec_ms += y;
-            }
-            k = 0;
-            if (hs.live == 0) break;
-            LZX_HIP(hipEventRecord(run.ev[0], c->stream));
-        }
-    }
+    LzxCgLoop lp;
+    LZX_TRY(lzx_cg_polled_loop(
+        run, d_st, hs, q.maxiter, lp, [&](u32) { return launch_spmm<B>(c, vP, m->d_V, vP); },
+        [&](u32 j) {
+            hipLaunchKernelGGL(k_mcg_update<B>, dim3(vgrid), blk, 0, c->stream, a, j);
+            hipLaunchKernelGGL(k_mcg_direction<B>, dim3(vgrid), blk, 0, c->stream, a, j);
+            return LZX_OK;
+        },
+        [](const McgState &s) { return s.live == 0; }));
+    const u32 launched = lp.launched;
 
     // every x_c: projected onto the complement of W, its true residual (one more SpMM), caller order
     LZX_TRY(project(vX));
@@ -629,9 +576,9 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
         q.info->launched = launched;
         q.info->converged = conv;
         q.info->nb = nb;
-        q.info->loop_ms = mcg_ms_since(q.t_start);
-        q.info->spmv_ms = spmv_ms;
-        q.info->vec_ms = vec_ms;
+        q.info->loop_ms = lzx_ms_since(q.t_start);
+        q.info->spmv_ms = lp.spmv_ms;
+        q.info->vec_ms = lp.vec_ms;
         for (u32 col = 0; col < LZX_MCG_MAX_NB; ++col) q.info->bnorm[col] = bnorm[col];
     }
     if (first_bad < nb)

@@ -102,6 +102,7 @@ def main():
             predicted = (sv["spmv_ms"] + sv["vec_ms"] * byte_ratio) / (sv["spmv_ms"] + sv["vec_ms"])
             emit(workload=name, case=f"nd = ns = {ns}", iterations=it_p,
                  pagerank_ms_per_iter=round(per_p, 4), pagerank_spmv_ms=round(pr["spmv_ms"] / it_p, 4), pagerank_vec_ms=round(pr["vec_ms"] / it_p, 4),
+                 pagerank_loop_ms=round(pr["loop_ms"], 3), solver_loop_ms=round(sv["loop_ms"], 3),
                  solver_ms_per_iter=round(per_s, 4), solver_spmv_ms=round(sv["spmv_ms"] / it_s, 4), solver_vec_ms=round(sv["vec_ms"] / it_s, 4),
                  spread_max_over_min=round(spread, 3), ratio=round(per_p / per_s, 3), ratio_predicted=round(predicted, 3),
                  vec_ratio=round((pr["vec_ms"] / it_p) / (sv["vec_ms"] / it_s), 3), vec_ratio_predicted=round(byte_ratio, 3),

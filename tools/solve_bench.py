@@ -7,8 +7,8 @@ C2 and C3 graphs (bench.WORKLOADS, imported), in one process:
   - Katz for four alpha in {0.5, 0.7, 0.85, 0.95} / lambda_max, tol 1e-10: one multi-shift call against four single-shift calls;
   - on C2 only, the route a user has without it: scipy cg over Engine.spmv (S x = x / alpha - A x), alpha = 0.85 / lambda_max.
 
-Byte model of the vector kernels per iteration, per row of n_loc_pad: k_cg_update reads p, w, r, x_0
-and writes r, x_0 (48 B); k_cg_direction reads r, p and writes p (24 B), and reads and writes x_s, p_s of every live shift
+Byte model of the vector kernels per iteration, per row of n_loc_pad: k_cg_update<false> reads p, w, r, x_0
+and writes r, x_0 (48 B); k_cg_direction<false> reads r, p and writes p (24 B), and reads and writes x_s, p_s of every live shift
 other than the seed (32 B each): 8 (9 + 4 (ns - 1)) B per row.
 
     python tools/solve_bench.py [--workloads c2,c3] [--iters 40] [--out FILE] [--no-scipy]

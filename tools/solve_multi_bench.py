@@ -89,6 +89,7 @@ def main():
             vec_bytes = 72.0 * B * n
             emit(workload=name, case=f"nb = {nb} (B = {B})", iterations=it_m,
                  multi_ms_per_iter=round(per_m, 4), multi_spmm_ms=round(mi["spmv_ms"] / it_m, 4), multi_vec_ms=round(mi["vec_ms"] / it_m, 4),
+                 multi_loop_ms=round(mi["loop_ms"], 3), single_loop_ms=round(si["loop_ms"], 3),
                  single_ms_per_iter=round(per_s, 4), nb_singles_ms_per_iter=round(nb * per_s, 4),
                  speedup_over_nb_singles=round(nb * per_s / per_m, 3), spread_max_over_min=round(spread, 3),
                  spmm_model_mb=round(spmm_bytes / 1e6, 1), spmm_tbs=round(spmm_bytes / (mi["spmv_ms"] / it_m * 1e-3) / 1e12, 3),
