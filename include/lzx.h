@@ -615,7 +615,7 @@ int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NU
  *             degrees, 8 n of counts, 8 n of coefficients, a few KiB of partials and the scan's scratch.
  *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
  *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  The checks that need no device come first.
- *   limits    one GPU handle; undirected, unweighted graphs; no per-edge support or k-truss, no core numbers, no sampling
+ *   limits    one GPU handle; undirected, unweighted graphs; no per-edge support or k-truss, no sampling
  *             estimator.  A matrix that is not symmetric is not detected: the call stays within its memory (the columns are
  *             sized by the count the fill repeats) and its counts mean nothing. */
 typedef struct lzx_triangles_info {
@@ -629,6 +629,58 @@ typedef struct lzx_triangles_info {
 } lzx_triangles_info;
 int lzx_triangles(lzx_handle h, uint64_t *tri /* [n] or NULL */, double *clustering /* [n] or NULL */,
                   lzx_triangles_info *info /* or NULL */);
+
+/* ---- core numbers and onion layers ------------------------------------------------------------------
+ * lzx_core_numbers: the k-core decomposition of the handle's graph read as undirected and unweighted -- what
+ * networkx.core_number and networkx.onion_layers return -- peeled on the device over the caller-order CSR.
+ *   outputs   d_v = the number of stored entries of row v NOT counting a diagonal entry: a self loop changes nothing in any
+ *             output (networkx raises on a graph with self loops; compare with the loops removed).  Rounds are numbered from
+ *             1 and k_0 = 0.  Round r has k_r = max(k_{r-1}, the smallest remaining degree among the remaining vertices) and
+ *             removes, all at once, every remaining vertex whose remaining degree is <= k_r; each of them gets core[v] = k_r
+ *             (networkx.core_number) and layer[v] = r (networkx.onion_layers), caller order.  An isolated vertex has core 0 and
+ *             layer 1.  Every output may be NULL; only those asked for cross PCIe.
+ *   info      (or NULL) degeneracy = the largest core number = the last k; main_core_size = the vertices whose core number is
+ *             the degeneracy; core0 = the vertices of core number 0 (no neighbour other than themselves); levels = the distinct
+ *             core numbers that occur; rounds = the peeling rounds = the largest layer; the host clock of the call and the
+ *             device event time of the peeling loop (one event pair around it, the host's reads included).  The host forms the
+ *             integers from the boundaries of the queue's windows.
+ *   method    push peeling, O(nnz) edge work in all.  State: the remaining degrees, the layers (0 = not yet removed: the mark),
+ *             the core numbers and one queue, u32 [n] each.  Every vertex is appended to the queue exactly once over the whole
+ *             call, so each round's frontier is a window of it, and what a launch appends behind the window is the next one.
+ *             When the frontier is empty a level starts: one thread per vertex, an unmarked vertex of remaining degree <= k is
+ *             marked and appended and the others contribute to a minimum; the host tries k + 1 first and, only if that
+ *             appends nothing, repeats the sweep with the minimum.  A round is one peel of its window: a group of lanes per row
+ *             (4 to 32, from the mean degree), rows of more than 64 times that many entries in a second launch, a workgroup per
+ *             row and slice of its entries; for every neighbour u != v that is not marked, old = atomicSub(&deg[u], 1), and the
+ *             one lane that sees old == k + 1 marks u (layer r + 1, core k) and appends it.  Appends and the minimum are
+ *             aggregated per wavefront: a ballot, then one atomic per wavefront.  The mark test saves traffic only: a decrement
+ *             of a removed vertex can never return k + 1, and on a symmetric matrix no counter goes below 0.  All atomics are
+ *             32-bit INTEGER vector atomics; there is no floating-point anywhere.  No kernel waits on another workgroup, every
+ *             device loop is bounded by a row length or a window length, every append is clamped to the queue's n entries.
+ *             The host reads one word per round (the queue's end) and two per level start, and stops when n vertices are
+ *             queued; the last window is not peeled (nobody is left to push to).
+ *   bits      core, layer and every integer of info are canonical: any correct algorithm gives them.  The order inside a
+ *             window is not deterministic and is no output.
+ *   state     the call touches none: it voids no prepared or chunked decomposition and leaves the resident bases and the batch
+ *             state alone.  Everything it allocates (16 n bytes and two words) is freed before it returns, on every path.
+ *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
+ *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  LZX_ERR_LIMIT: more than n + 1 rounds (cannot happen).
+ *             The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted graphs; no k-truss or per-edge support; no degeneracy ordering (the
+ *             order inside a round is not deterministic).  A matrix that is not symmetric is not detected: its numbers mean
+ *             nothing, but the call stays within its memory and ends -- the mark is taken by a compare-and-swap, so no vertex
+ *             is queued twice even where a counter wraps. */
+typedef struct lzx_core_info {
+    uint64_t main_core_size;  /* vertices whose core number equals the degeneracy */
+    uint64_t core0;           /* vertices of core number 0 (no neighbour other than themselves) */
+    uint32_t degeneracy;      /* the largest core number */
+    uint32_t levels;          /* distinct core numbers that occur */
+    uint32_t rounds;          /* peeling rounds = the largest onion layer */
+    uint32_t reserved_;
+    double   loop_ms, peel_ms;/* host clock of the call; device event time of the peeling launches */
+} lzx_core_info;
+int lzx_core_numbers(lzx_handle h, uint32_t *core /* [n] or NULL */, uint32_t *layer /* [n] or NULL */,
+                     lzx_core_info *info /* or NULL */);
 
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the

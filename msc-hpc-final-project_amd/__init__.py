@@ -24,7 +24,7 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes")
+                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -123,6 +123,14 @@ class LzxTrianglesInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
 
 
+class LzxCoreInfo(ctypes.Structure):
+    _fields_ = [("main_core_size", ctypes.c_uint64), ("core0", ctypes.c_uint64), ("degeneracy", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+                ("rounds", ctypes.c_uint32), ("reserved_", ctypes.c_uint32), ("loop_ms", ctypes.c_double), ("peel_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -186,6 +194,7 @@ SYMBOLS = [
     ("lzx_bfs_multi", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _i32p, _f64p, _u64p, _u64p, _f64p, _u32p, ctypes.POINTER(LzxBfsInfo)]),
     ("lzx_betweenness_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _f64p, ctypes.POINTER(LzxBfsInfo)]),
     ("lzx_triangles", ctypes.c_int, [_h, _u64p, _f64p, ctypes.POINTER(LzxTrianglesInfo)]),
+    ("lzx_core_numbers", ctypes.c_int, [_h, _u32p, _u32p, ctypes.POINTER(LzxCoreInfo)]),
 ]
 
 _LIB = None
@@ -1014,6 +1023,54 @@ class Engine:
         clus = self.triangles_raw(want_triangles=False)[1]
         nz = clus[clus > 0.0]
         return float(nz.sum() / len(nz)) if len(nz) else 0.0
+
+    # ---- core numbers and onion layers (include/lzx.h: lzx_core_numbers) ----
+    def core_number_raw(self, want_core: bool = True, want_layers: bool = True):
+        """(core, layer, info) of lzx_core_numbers: core[v] = networkx.core_number, layer[v] = networkx.onion_layers (uint32, the
+        caller's order; None when not wanted, and then that vector does not leave the device); info = the lzx_core_info fields
+        (main_core_size, core0, degeneracy, levels, rounds, loop_ms, peel_ms).  Self loops are ignored."""
+        core = np.empty(self.n, dtype=np.uint32) if want_core else None
+        layer = np.empty(self.n, dtype=np.uint32) if want_layers else None
+        info = LzxCoreInfo()
+        _check(self.L.lzx_core_numbers(self.h, _p(core, _u32p) if want_core else None, _p(layer, _u32p) if want_layers else None,
+                                       ctypes.byref(info)), "lzx_core_numbers", self.L)
+        return core, layer, info.as_dict()
+
+    def core_number(self, nodes=None):
+        """networkx.core_number: the largest k such that the vertex lies in the k-core (uint32 array, caller's order), or of `nodes`."""
+        core = self.core_number_raw(want_layers=False)[0]
+        return core if nodes is None else core[self._nodes(nodes, "core_number")]
+
+    def onion_layers(self, nodes=None):
+        """networkx.onion_layers: the peeling round, from 1, in which the vertex is removed (uint32 array, caller's order), or of
+        `nodes`."""
+        layer = self.core_number_raw(want_core=False)[1]
+        return layer if nodes is None else layer[self._nodes(nodes, "onion_layers")]
+
+    def degeneracy(self):
+        """The largest core number.  No n-vector leaves the device."""
+        return int(self.core_number_raw(want_core=False, want_layers=False)[2]["degeneracy"])
+
+    def k_core(self, k=None, **options):
+        """networkx.k_core: induced(core >= k) -- (engine on the k-core, old_of_new), built on the device; k=None selects the main
+        core (k = the degeneracy).  `options` as for induced()."""
+        core, _, info = self.core_number_raw(want_layers=False)
+        top = int(info["degeneracy"])
+        k = top if k is None else int(k)
+        if k > top:
+            raise ValueError(f"k_core: k = {k} is above the degeneracy {top} of this graph: the {k}-core is empty")
+        return self.induced(core >= max(k, 0), **options)
+
+    def k_shell(self, k=None, **options):
+        """networkx.k_shell: induced(core == k) -- (engine on the vertices of core number exactly k, old_of_new); k=None selects the
+        main core's shell (k = the degeneracy).  An empty shell is a ValueError."""
+        core, _, info = self.core_number_raw(want_layers=False)
+        top = int(info["degeneracy"])
+        k = top if k is None else int(k)
+        keep = core == k if k >= 0 else np.zeros(self.n, dtype=bool)
+        if not keep.any():
+            raise ValueError(f"k_shell: no vertex of this graph has core number {k} (the degeneracy is {top})")
+        return self.induced(keep, **options)
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

@@ -1,0 +1,321 @@
+// lzx_core.hip -- core numbers and onion layers of the handle's graph (networkx.core_number, networkx.onion_layers), on the
+// device over the caller-order CSR the handle keeps (d_row_ptr / d_col_idx): include/lzx.h, lzx_core_numbers; DESIGN.md section 19.
+//
+// Definitions.  d_v = the entries of row v without the diagonal.  Rounds are numbered from 1 and k_0 = 0; round r has
+// k_r = max(k_{r-1}, the smallest remaining degree of a remaining vertex) and removes, all at once, every remaining vertex whose
+// remaining degree is <= k_r: core[v] = k_r, layer[v] = r.
+//
+// Push peeling.  deg[v] is the remaining degree, layer[v] != 0 marks a vertex that is removed or queued for removal, and `order`
+// is one queue in which every vertex is placed exactly once over the whole call, so that each round's frontier is a window
+// [beg, end) of it and what a launch appends behind `end` is the next window.
+//   degrees      k_core_degrees       one thread per row: the row's length, minus one if a binary search finds v in it (what
+//                                     k_tri_degrees does, restated here so that lzx_triangles' file stays as it is)
+//   level start  k_core_level         one thread per vertex, when the frontier is empty: an unmarked vertex with deg <= k is
+//                                     marked (layer = r, core = k) and appended, the others contribute to a minimum.  The host
+//                                     tries k + 1 first -- after a level is peeled out every remaining degree is at least that --
+//                                     and only if nothing was appended repeats the sweep with the minimum it got back.
+//   peel         k_core_peel<G>       G lanes per row of the window; for every neighbour u != v that is not marked,
+//                                     old = atomicSub(&deg[u], 1), and the one lane that sees old == k + 1 marks u
+//                                     (layer = r + 1, core = k) and appends it
+//                k_core_peel_long     the window's rows of more than long_row entries: a workgroup per (row, slice of its entries)
+// Appends are aggregated per wavefront (a ballot, one atomic add on the queue's end by the first lane, a broadcast), and so is the
+// minimum; the loops around them run the same trips on every lane of a wavefront.
+//
+// The "not marked" test saves traffic only; no output depends on whether a lane sees a fresh or a stale mark:
+//   - decrements only lower a counter.  A vertex is marked when its counter is at most k: at a level start it is <= k, in the
+//     peel it has just gone from k + 1 to k.  A later decrement of it therefore returns at most k, never k + 1, while the level
+//     lasts, and the counters of marked vertices are never read again once k moves on: a removed vertex is appended once.
+//   - on a symmetric matrix deg[u] counts the neighbours of u that have not been peeled yet, each of which decrements it at most
+//     once (a vertex is peeled once), so no counter goes below 0.
+// A matrix that is not symmetric is not detected and its numbers mean nothing; its counters may wrap.  The call still stays
+// inside its memory and ends: the mark is taken by a compare-and-swap, which only the first claimant of a vertex wins (on a
+// symmetric matrix the only one), so no vertex is queued twice, the queue's end never passes n -- every append is clamped to the
+// n entries all the same -- every window is a fresh piece of the queue, and a level start always finds the vertex of the minimum.
+//
+// All atomics are 32-bit integer vector atomics; nothing is floating-point.  The order inside a window is not deterministic and
+// is no output; core, layer, rounds and levels are.  No kernel waits on another workgroup; every device loop is bounded by a row
+// length or a window length.  The host reads one word per peeling round (the queue's end) and two per level start (the end and
+// the minimum), as lzx_components reads its flag.
+#include <algorithm>
+#include <chrono>
+
+#include "lzx_internal.h"
+
+typedef unsigned long long ull;
+
+static constexpr u32 LZX_CORE_BLOCK = 256;
+static constexpr u32 LZX_CORE_SLICES = 64;   // workgroups a long row's entries are dealt to (at most)
+static constexpr u32 LZX_CORE_NONE = 0xffffffffu;
+
+// the calling lanes for which `take` holds get consecutive places behind *tail: one atomic per wavefront.  Every lane of the
+// wavefront must call it together.  Returns the lane's place (meaningless where !take).
+__device__ __forceinline__ u32 core_wave_append(bool take, u32 *tail)
+{
+    const ull m = __ballot(take);
+    if (m == 0) return 0;   // (the same for every lane)
+    const u32 lane = threadIdx.x & 63;
+    const int first = __builtin_ctzll(m);
+    u32 base = 0;
+    if (lane == (u32)first) base = atomicAdd(tail, (u32)__builtin_popcountll(m));
+    base = (u32)__shfl((int)base, first, 64);
+    return base + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+}
+
+__global__ void __launch_bounds__(LZX_CORE_BLOCK)
+k_core_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *counters, u32 n)
+{
+    const u64 v = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
+    if (v == 0) counters[0] = 0;   // the queue's end
+    if (v >= n) return;
+    const u64 beg = row_ptr[v];
+    const u32 len = (u32)(row_ptr[v + 1] - beg);
+    u32 lo = 0, hi = len;
+    while (lo < hi) {   // first position of the ascending row whose entry is >= v
+        const u32 mid = (lo + hi) >> 1;
+        if (col_idx[beg + mid] < (u32)v) lo = mid + 1;
+        else hi = mid;
+    }
+    deg[v] = len - ((lo < len && col_idx[beg + lo] == (u32)v) ? 1u : 0u);
+    layer[v] = 0;
+}
+
+// counters[0] = the queue's end, counters[1] = the minimum (LZX_CORE_NONE before the launch)
+__global__ void __launch_bounds__(LZX_CORE_BLOCK)
+k_core_level(const u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 n, u32 k, u32 r)
+{
+    const u64 v = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
+    bool take = false;
+    u32 m = LZX_CORE_NONE;
+    if (v < n && layer[v] == 0) {
+        const u32 d = deg[v];
+        if (d <= k) take = true;
+        else m = d;
+    }
+    const u32 at = core_wave_append(take, &counters[0]);
+    if (take) {
+        layer[v] = r;
+        core[v] = k;
+        if (at < n) order[at] = (u32)v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = min(m, (u32)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m != LZX_CORE_NONE) atomicMin(&counters[1], m);
+}
+
+// one neighbour u of a window's vertex (have: this lane holds one, it is not the vertex itself): the decrement, the mark, the append
+__device__ __forceinline__ void core_push(bool have, u32 u, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *tail, u32 n, u32 k, u32 r)
+{
+    bool take = false;
+    if (have && layer[u] == 0) {
+        const u32 old = atomicSub(&deg[u], 1u);
+        if (old == k + 1) take = atomicCAS(&layer[u], 0u, r + 1) == 0u;
+    }
+    const u32 at = core_wave_append(take, tail);
+    if (take) {
+        core[u] = k;
+        if (at < n) order[at] = u;
+    }
+}
+
+// rows of the window order[wbeg .. wbeg + wlen) with at most long_row entries: G lanes per row, 256 / G rows per workgroup
+template <u32 G>
+__global__ void __launch_bounds__(LZX_CORE_BLOCK)
+k_core_peel(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 n, u32 wbeg, u32 wlen,
+            u32 k, u32 r, u32 long_row)
+{
+    const u32 sub = threadIdx.x & (G - 1);
+    const u64 idx = (u64)blockIdx.x * (LZX_CORE_BLOCK / G) + threadIdx.x / G;
+    u64 beg = 0;
+    u32 len = 0, v = 0;
+    if (idx < wlen) {
+        v = order[wbeg + idx];
+        beg = row_ptr[v];
+        const u64 l = row_ptr[v + 1] - beg;
+        len = l > long_row ? 0u : (u32)l;   // k_core_peel_long's
+    }
+    u32 trips = (len + G - 1) / G;
+#pragma unroll
+    for (int o = 32; o >= (int)G; o >>= 1) trips = max(trips, (u32)__shfl_xor((int)trips, o, 64));
+    for (u32 t = 0; t < trips; ++t) {   // (the same trips for every lane of the wavefront: the appends are formed together)
+        const u32 e = t * G + sub;
+        u32 u = v;
+        if (e < len) u = col_idx[beg + e];
+        core_push(u != v, u, deg, layer, core, order, &counters[0], n, k, r);
+    }
+}
+
+// rows of more than long_row entries among the workgroup's 256 window places: the workgroup takes every gridDim.y-th run of 256
+// entries of each
+__global__ void __launch_bounds__(LZX_CORE_BLOCK)
+k_core_peel_long(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 n, u32 wbeg,
+                 u32 wlen, u32 k, u32 r, u32 long_row)
+{
+    __shared__ u32 s_rows[LZX_CORE_BLOCK];
+    __shared__ u32 s_count;
+    if (threadIdx.x == 0) s_count = 0;
+    __syncthreads();
+    const u64 idx = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
+    if (idx < wlen) {
+        const u32 mine = order[wbeg + idx];
+        if (row_ptr[mine + 1] - row_ptr[mine] > long_row) s_rows[atomicAdd(&s_count, 1u)] = mine;
+    }
+    __syncthreads();
+    const u32 count = s_count;
+    for (u32 i = 0; i < count; ++i) {
+        const u32 v = s_rows[i];
+        const u64 beg = row_ptr[v], end = row_ptr[v + 1];
+        // (the same trips for every lane of the workgroup)
+        for (u64 e0 = beg + (u64)blockIdx.y * LZX_CORE_BLOCK; e0 < end; e0 += (u64)gridDim.y * LZX_CORE_BLOCK) {
+            const u64 e = e0 + threadIdx.x;
+            u32 u = v;
+            if (e < end) u = col_idx[e];
+            core_push(u != v, u, deg, layer, core, order, &counters[0], n, k, r);
+        }
+    }
+}
+
+namespace {
+struct CoreRun {   // everything the call allocates: gone on every return path
+    lzx_ctx *c = nullptr;
+    void *arena = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~CoreRun()
+    {
+        if (c) {
+            (void)hipSetDevice(c->device);
+            (void)hipStreamSynchronize(c->stream);
+        }
+        if (arena) (void)hipFree(arena);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+}   // namespace
+
+template <u32 G>
+static void launch_peel(hipStream_t st, const lzx_ctx *c, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 wbeg, u32 wlen, u32 k,
+                        u32 r, u32 long_row)
+{
+    const u32 rows_per_block = LZX_CORE_BLOCK / G;
+    const u32 grid = (u32)(((u64)wlen + rows_per_block - 1) / rows_per_block);
+    hipLaunchKernelGGL(k_core_peel<G>, dim3(grid), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg, layer, core, order, counters,
+                       (u32)c->n, wbeg, wlen, k, r, long_row);
+}
+
+extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, lzx_core_info *info)
+{
+    const char *fn_name = "lzx_core_numbers";
+    // what needs no device
+    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn_name);
+    if (c->comm_kind != 0 || c->world > 1)
+        LZX_FAIL(LZX_ERR_STATE, "%s: core numbers are peeled on one GPU handle; this handle is rank %d of a communicator of %d", fn_name, c->rank, c->world);
+    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn_name);
+    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn_name);
+    const auto t0 = std::chrono::steady_clock::now();
+    const u32 n = (u32)c->n;
+
+    // one arena: deg, layer, core, order (u32 [n] each, rounded to 8 bytes), the queue's end and the minimum
+    const u64 n_al = ((u64)n + 1) & ~1ull;
+    const u64 bytes = 4 * n_al * sizeof(u32) + 2 * sizeof(u32);
+    if (c->core_cap_opt >= 0 && bytes > (u64)c->core_cap_opt)
+        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (remaining degrees, layers, core numbers, the queue) needs %llu bytes of device memory", fn_name,
+                 n, (unsigned long long)bytes);
+    LZX_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    CoreRun run;
+    run.c = c;
+    const hipError_t e = hipMalloc(&run.arena, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        run.arena = nullptr;
+        LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP,
+                 "%s: the state of %u vertices (remaining degrees, layers, core numbers, the queue) needs %llu bytes of device memory: %s", fn_name, n,
+                 (unsigned long long)bytes, hipGetErrorString(e));
+    }
+    u32 *d_deg = static_cast<u32 *>(run.arena), *d_layer = d_deg + n_al, *d_core = d_layer + n_al, *d_order = d_core + n_al;
+    u32 *d_counters = d_order + n_al;
+    LZX_HIP(hipEventCreate(&run.ev0));
+    LZX_HIP(hipEventCreate(&run.ev1));
+
+    // lanes per row of the window: about half the mean degree of the rows that have an edge.  Rows of more than 64 G entries
+    // (256 ... 2048: more than 64 trips of a group) go to the long-row launch.
+    const u64 mean = c->nnz / std::max<u64>(c->n_active, 1);
+    u32 G = 4;
+    while (G < 32 && 2 * G <= mean) G *= 2;
+    const u32 long_row = c->core_long_opt > 0 ? (u32)std::min<int64_t>(c->core_long_opt, 0xffffffff) : 64 * G;
+    const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_CORE_BLOCK), 1), LZX_CORE_SLICES);
+    const u32 gb = (n + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK;
+
+    LZX_HIP(hipEventRecord(run.ev0, st));
+    hipLaunchKernelGGL(k_core_degrees, dim3(gb), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, d_layer, d_counters, n);
+    LZX_HIP(hipGetLastError());
+    u32 k = 0, rounds = 0, levels = 0;
+    u32 queued = 0;        // the queue's end: vertices marked so far
+    u32 level_pos = 0;     // the queue position at which the current level began
+    u32 core0 = 0;
+    while (queued < n) {
+        // ---- the frontier is empty: the next level.  k + 1 first (0 at the start); the minimum if that appends nothing ----
+        u32 k_try = levels == 0 ? 0u : (k == LZX_CORE_NONE ? k : k + 1);
+        u32 end = queued;
+        for (int attempt = 0; attempt < 2 && end == queued; ++attempt) {
+            u32 words[2] = {0, 0};
+            LZX_HIP(hipMemsetAsync(d_counters + 1, 0xff, sizeof(u32), st));
+            hipLaunchKernelGGL(k_core_level, dim3(gb), dim3(LZX_CORE_BLOCK), 0, st, d_deg, d_layer, d_core, d_order, d_counters, n, k_try, rounds + 1);
+            LZX_HIP(hipGetLastError());
+            LZX_HIP(hipMemcpyAsync(words, d_counters, sizeof(words), hipMemcpyDeviceToHost, st));
+            LZX_HIP(hipStreamSynchronize(st));
+            end = std::min(words[0], n);
+            if (end == queued) k_try = words[1];   // nobody at this k: the smallest remaining degree is the next
+        }
+        if (end == queued) LZX_FAIL(LZX_ERR_LIMIT, "%s: no vertex of remaining degree %u among the %u left after %u rounds", fn_name, k_try, n - queued, rounds);
+        k = k_try;
+        ++levels;
+        level_pos = queued;
+        u32 wbeg = queued;
+        queued = end;
+        // ---- the rounds of this level: window [wbeg, queued) ----
+        for (;;) {
+            ++rounds;
+            if ((u64)rounds > (u64)n + 1) LZX_FAIL(LZX_ERR_LIMIT, "%s: %u rounds on %u vertices", fn_name, rounds, n);
+            if (rounds == 1 && k == 0) core0 = queued;
+            if (queued >= n) break;   // everything is queued: the last window has nobody left to push to
+            const u32 wlen = queued - wbeg;
+            switch (G) {
+            case 4: launch_peel<4>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
+            case 8: launch_peel<8>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
+            case 16: launch_peel<16>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
+            default: launch_peel<32>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
+            }
+            LZX_HIP(hipGetLastError());
+            if (c->max_degree > long_row) {
+                hipLaunchKernelGGL(k_core_peel_long, dim3((wlen + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK, slices), dim3(LZX_CORE_BLOCK), 0, st,
+                                   c->d_row_ptr, c->d_col_idx, d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, rounds, long_row);
+                LZX_HIP(hipGetLastError());
+            }
+            u32 word = 0;
+            LZX_HIP(hipMemcpyAsync(&word, d_counters, sizeof(u32), hipMemcpyDeviceToHost, st));
+            LZX_HIP(hipStreamSynchronize(st));
+            end = std::min(word, n);
+            if (end == queued) break;   // nothing fell to k: the level is peeled out
+            wbeg = queued;
+            queued = end;
+        }
+    }
+    LZX_HIP(hipEventRecord(run.ev1, st));
+    if (core) LZX_HIP(hipMemcpyAsync(core, d_core, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
+    if (layer) LZX_HIP(hipMemcpyAsync(layer, d_layer, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    float peel_ms = 0.f;
+    LZX_HIP(hipEventElapsedTime(&peel_ms, run.ev0, run.ev1));
+    if (info) {
+        info->main_core_size = (u64)n - level_pos;
+        info->core0 = core0;
+        info->degeneracy = k;
+        info->levels = levels;
+        info->rounds = rounds;
+        info->reserved_ = 0;
+        info->peel_ms = peel_ms;
+        info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return LZX_OK;
+}

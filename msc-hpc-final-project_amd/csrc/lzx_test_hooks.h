@@ -19,7 +19,10 @@
 // bytes as out of device memory; their long rows are the batched SpMM's: "multi_row_chunk"), "tri_long_list" (lzx_triangles: a row of the
 // oriented copy with more than this many entries is counted by the wide kernel, a workgroup per row and a wavefront per out-edge, and only
 // lists of at most 32 times this many entries, 4096 at the most, are staged in LDS there; default 128), "tri_state_bytes" (lzx_triangles
-// takes a state larger than this many bytes as out of device memory).
+// takes a state larger than this many bytes as out of device memory), "core_long_row" (lzx_core_numbers: a row of the frontier with more than
+// this many entries is peeled by the long-row launch, a workgroup per row and slice of its entries; default 64 times the lanes per row,
+// 256 to 2048 from the mean degree), "core_state_bytes" (lzx_core_numbers takes a state larger than this many bytes as out of device
+// memory, before the device is touched).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
