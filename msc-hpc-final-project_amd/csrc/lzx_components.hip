@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
@@ -73,12 +74,8 @@ k_cc_sweep_long(const u64 *row_ptr, const u32 *col_idx, const u32 *f, const u32 
     __shared__ u32 s_rows[LZX_CC_BLOCK];
     __shared__ u32 s_count;
     __shared__ u32 s_min[LZX_CC_BLOCK / 64];
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
     const u64 mine = (u64)blockIdx.x * LZX_CC_BLOCK + threadIdx.x;
-    if (mine < n && row_ptr[mine + 1] - row_ptr[mine] > long_row) s_rows[atomicAdd(&s_count, 1u)] = (u32)mine;
-    __syncthreads();
-    const u32 count = s_count;
+    const u32 count = lzx_collect_long_rows(mine < n && row_ptr[mine + 1] - row_ptr[mine] > long_row, (u32)mine, s_rows, &s_count);
     for (u32 r = 0; r < count; ++r) {
         const u32 row = s_rows[r];
         const u64 beg = row_ptr[row], end = row_ptr[row + 1];
@@ -146,18 +143,12 @@ k_cc_stats(const u32 *f, const u32 *sizes, u32 n, double *part_count, unsigned l
             key = k > key ? k : key;
         }
     cnt = wave_sum(cnt);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o, 64);
-        key = other > key ? other : key;
-    }
+    key = wave_max_u64(key);
     if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = cnt; s_k[threadIdx.x >> 6] = key; }
     __syncthreads();
     if (threadIdx.x == 0) {
         part_count[blockIdx.x] = ((s_c[0] + s_c[1]) + s_c[2]) + s_c[3];
-        unsigned long long k = s_k[0];
-        for (u32 w = 1; w < LZX_CC_BLOCK / 64; ++w) k = s_k[w] > k ? s_k[w] : k;
-        part_key[blockIdx.x] = k;
+        part_key[blockIdx.x] = block_max_u64(s_k);
     }
 }
 
@@ -169,50 +160,19 @@ k_cc_close(const double *part_count, const unsigned long long *part_key, u32 np,
     const double total = block_sum_fixed_256(part_count, np, sh);
     unsigned long long key = 0;
     for (u32 i = threadIdx.x; i < np; i += LZX_VEC_BLOCK) key = part_key[i] > key ? part_key[i] : key;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o, 64);
-        key = other > key ? other : key;
-    }
+    key = wave_max_u64(key);
     if ((threadIdx.x & 63) == 0) s_k[threadIdx.x >> 6] = key;
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long k = s_k[0];
-        for (u32 w = 1; w < LZX_VEC_BLOCK / 64; ++w) k = s_k[w] > k ? s_k[w] : k;
+        out2[1] = block_max_u64(s_k);
         out2[0] = (unsigned long long)total;
-        out2[1] = k;
     }
-}
-
-namespace {
-struct CcRun {   // everything the call allocates: gone on every return path
-    void *arena = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~CcRun()
-    {
-        if (arena) (void)hipFree(arena);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-}   // namespace
-
-template <u32 G>
-static void launch_sweep(hipStream_t st, const lzx_ctx *c, const u32 *f, const u32 *gf, u32 *fn, u32 *changed, u32 long_row)
-{
-    const u32 rows_per_block = LZX_CC_BLOCK / G;
-    const u32 grid = (u32)((c->n + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(k_cc_sweep<G>, dim3(grid), dim3(LZX_CC_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, f, gf, fn, changed, (u32)c->n, long_row);
 }
 
 extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_info *info)
 {
     const char *fn_name = "lzx_components";
-    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn_name);
-    if (c->comm_kind != 0 || c->world > 1)
-        LZX_FAIL(LZX_ERR_STATE, "%s: components are labelled on one GPU handle; this handle is rank %d of a communicator of %d", fn_name, c->rank, c->world);
-    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn_name);
-    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn_name);
+    LZX_TRY(lzx_graph_call_check(c, fn_name, "components are labelled"));
     LZX_HIP(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
@@ -222,14 +182,10 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
     const u64 n_al = ((u64)n + 1) & ~1ull;
     const u32 np = (u32)std::min<u64>(LZX_CC_STAT_GRID, ((u64)n + LZX_CC_BLOCK - 1) / LZX_CC_BLOCK);
     const u64 bytes = 4 * n_al * sizeof(u32) + (u64)np * (sizeof(double) + sizeof(unsigned long long)) + 2 * sizeof(unsigned long long) + 8;
-    CcRun run;
-    hipError_t e = hipMalloc(&run.arena, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        run.arena = nullptr;
-        LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the labels of %u vertices (parents, grandparents, next parents, sizes) need %llu bytes of device memory: %s",
-                 fn_name, n, (unsigned long long)bytes, hipGetErrorString(e));
-    }
+    LzxGraphRun run(c);
+    char what[96];
+    std::snprintf(what, sizeof what, "the state of %u vertices (parents, grandparents, next parents, sizes)", n);
+    LZX_TRY(lzx_alloc_state(fn_name, what, -1, bytes, bytes, &run.arena));
     u32 *d_f = static_cast<u32 *>(run.arena), *d_gf = d_f + n_al, *d_fn = d_gf + n_al, *d_sizes = d_fn + n_al;
     double *d_pc = reinterpret_cast<double *>(d_sizes + n_al);
     unsigned long long *d_pk = reinterpret_cast<unsigned long long *>(d_pc + np), *d_out = d_pk + np;
@@ -238,9 +194,7 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // lanes per row: about half the mean degree of the rows that have an edge, so that a typical row is two loads per lane
-    const u64 mean = c->nnz / std::max<u64>(c->n_active, 1);
-    u32 G = 4;
-    while (G < 32 && 2 * G <= mean) G *= 2;
+    const u32 G = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32);
     const u32 long_row = 64 * G;
     const u32 gb = (n + LZX_CC_BLOCK - 1) / LZX_CC_BLOCK;
 
@@ -251,12 +205,10 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
     for (;;) {
         if (rounds > n) LZX_FAIL(LZX_ERR_LIMIT, "%s: no fixed point after %u rounds on %u vertices", fn_name, rounds, n);
         LZX_HIP(hipEventRecord(run.ev0, st));
-        switch (G) {
-        case 4: launch_sweep<4>(st, c, d_f, d_gf, d_fn, d_changed, long_row); break;
-        case 8: launch_sweep<8>(st, c, d_f, d_gf, d_fn, d_changed, long_row); break;
-        case 16: launch_sweep<16>(st, c, d_f, d_gf, d_fn, d_changed, long_row); break;
-        default: launch_sweep<32>(st, c, d_f, d_gf, d_fn, d_changed, long_row); break;
-        }
+        lzx_with_lanes<32>(G, [&](auto g) {
+            hipLaunchKernelGGL(k_cc_sweep<g>, dim3(lzx_row_grid(n, LZX_CC_BLOCK / g)), dim3(LZX_CC_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_f, d_gf,
+                               d_fn, d_changed, n, long_row);
+        });
         LZX_HIP(hipGetLastError());
         if (c->max_degree > long_row) {
             hipLaunchKernelGGL(k_cc_sweep_long, dim3(gb), dim3(LZX_CC_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_f, d_gf, d_fn, d_changed, n, long_row);
@@ -291,7 +243,7 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
         info->largest_label = 0xffffffffu - (u32)(out2[1] & 0xffffffffull);
         info->rounds = rounds;
         info->sweep_ms = sweep_ms;
-        info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        info->loop_ms = lzx_ms_since(t0);
     }
     return LZX_OK;
 }

@@ -8,8 +8,7 @@
 // Push peeling.  deg[v] is the remaining degree, layer[v] != 0 marks a vertex that is removed or queued for removal, and `order`
 // is one queue in which every vertex is placed exactly once over the whole call, so that each round's frontier is a window
 // [beg, end) of it and what a launch appends behind `end` is the next window.
-//   degrees      k_core_degrees       one thread per row: the row's length, minus one if a binary search finds v in it (what
-//                                     k_tri_degrees does, restated here so that lzx_triangles' file stays as it is)
+//   degrees      k_core_degrees       one thread per row: lzx_degree_no_diagonal (lzx_graph_call.h), and layer = 0, the queue empty
 //   level start  k_core_level         one thread per vertex, when the frontier is empty: an unmarked vertex with deg <= k is
 //                                     marked (layer = r, core = k) and appended, the others contribute to a minimum.  The host
 //                                     tries k + 1 first -- after a level is peeled out every remaining degree is at least that --
@@ -18,7 +17,7 @@
 //                                     old = atomicSub(&deg[u], 1), and the one lane that sees old == k + 1 marks u
 //                                     (layer = r + 1, core = k) and appends it
 //                k_core_peel_long     the window's rows of more than long_row entries: a workgroup per (row, slice of its entries)
-// Appends are aggregated per wavefront (a ballot, one atomic add on the queue's end by the first lane, a broadcast), and so is the
+// Appends are aggregated per wavefront (lzx_wave_append: a ballot, one atomic add on the queue's end, a broadcast), and so is the
 // minimum; the loops around them run the same trips on every lane of a wavefront.
 //
 // The "not marked" test saves traffic only; no output depends on whether a lane sees a fresh or a stale mark:
@@ -40,26 +39,11 @@
 #include <chrono>
 
 #include "lzx_internal.h"
-
-typedef unsigned long long ull;
+#include "lzx_graph_call.h"
 
 static constexpr u32 LZX_CORE_BLOCK = 256;
 static constexpr u32 LZX_CORE_SLICES = 64;   // workgroups a long row's entries are dealt to (at most)
 static constexpr u32 LZX_CORE_NONE = 0xffffffffu;
-
-// the calling lanes for which `take` holds get consecutive places behind *tail: one atomic per wavefront.  Every lane of the
-// wavefront must call it together.  Returns the lane's place (meaningless where !take).
-__device__ __forceinline__ u32 core_wave_append(bool take, u32 *tail)
-{
-    const ull m = __ballot(take);
-    if (m == 0) return 0;   // (the same for every lane)
-    const u32 lane = threadIdx.x & 63;
-    const int first = __builtin_ctzll(m);
-    u32 base = 0;
-    if (lane == (u32)first) base = atomicAdd(tail, (u32)__builtin_popcountll(m));
-    base = (u32)__shfl((int)base, first, 64);
-    return base + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-}
 
 __global__ void __launch_bounds__(LZX_CORE_BLOCK)
 k_core_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *counters, u32 n)
@@ -67,15 +51,7 @@ k_core_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32
     const u64 v = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
     if (v == 0) counters[0] = 0;   // the queue's end
     if (v >= n) return;
-    const u64 beg = row_ptr[v];
-    const u32 len = (u32)(row_ptr[v + 1] - beg);
-    u32 lo = 0, hi = len;
-    while (lo < hi) {   // first position of the ascending row whose entry is >= v
-        const u32 mid = (lo + hi) >> 1;
-        if (col_idx[beg + mid] < (u32)v) lo = mid + 1;
-        else hi = mid;
-    }
-    deg[v] = len - ((lo < len && col_idx[beg + lo] == (u32)v) ? 1u : 0u);
+    deg[v] = lzx_degree_no_diagonal(row_ptr, col_idx, v);
     layer[v] = 0;
 }
 
@@ -91,7 +67,7 @@ k_core_level(const u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u
         if (d <= k) take = true;
         else m = d;
     }
-    const u32 at = core_wave_append(take, &counters[0]);
+    const u32 at = lzx_wave_append(take, &counters[0]);
     if (take) {
         layer[v] = r;
         core[v] = k;
@@ -110,7 +86,7 @@ __device__ __forceinline__ void core_push(bool have, u32 u, u32 *deg, u32 *layer
         const u32 old = atomicSub(&deg[u], 1u);
         if (old == k + 1) take = atomicCAS(&layer[u], 0u, r + 1) == 0u;
     }
-    const u32 at = core_wave_append(take, tail);
+    const u32 at = lzx_wave_append(take, tail);
     if (take) {
         core[u] = k;
         if (at < n) order[at] = u;
@@ -152,15 +128,9 @@ k_core_peel_long(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u
 {
     __shared__ u32 s_rows[LZX_CORE_BLOCK];
     __shared__ u32 s_count;
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
     const u64 idx = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
-    if (idx < wlen) {
-        const u32 mine = order[wbeg + idx];
-        if (row_ptr[mine + 1] - row_ptr[mine] > long_row) s_rows[atomicAdd(&s_count, 1u)] = mine;
-    }
-    __syncthreads();
-    const u32 count = s_count;
+    const u32 mine = idx < wlen ? order[wbeg + idx] : 0u;
+    const u32 count = lzx_collect_long_rows(idx < wlen && row_ptr[mine + 1] - row_ptr[mine] > long_row, mine, s_rows, &s_count);
     for (u32 i = 0; i < count; ++i) {
         const u32 v = s_rows[i];
         const u64 beg = row_ptr[v], end = row_ptr[v + 1];
@@ -174,64 +144,22 @@ k_core_peel_long(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u
     }
 }
 
-namespace {
-struct CoreRun {   // everything the call allocates: gone on every return path
-    lzx_ctx *c = nullptr;
-    void *arena = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~CoreRun()
-    {
-        if (c) {
-            (void)hipSetDevice(c->device);
-            (void)hipStreamSynchronize(c->stream);
-        }
-        if (arena) (void)hipFree(arena);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-}   // namespace
-
-template <u32 G>
-static void launch_peel(hipStream_t st, const lzx_ctx *c, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 wbeg, u32 wlen, u32 k,
-                        u32 r, u32 long_row)
-{
-    const u32 rows_per_block = LZX_CORE_BLOCK / G;
-    const u32 grid = (u32)(((u64)wlen + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(k_core_peel<G>, dim3(grid), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg, layer, core, order, counters,
-                       (u32)c->n, wbeg, wlen, k, r, long_row);
-}
-
 extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, lzx_core_info *info)
 {
     const char *fn_name = "lzx_core_numbers";
-    // what needs no device
-    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn_name);
-    if (c->comm_kind != 0 || c->world > 1)
-        LZX_FAIL(LZX_ERR_STATE, "%s: core numbers are peeled on one GPU handle; this handle is rank %d of a communicator of %d", fn_name, c->rank, c->world);
-    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn_name);
-    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn_name);
+    LZX_TRY(lzx_graph_call_check(c, fn_name, "core numbers are peeled"));
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
 
     // one arena: deg, layer, core, order (u32 [n] each, rounded to 8 bytes), the queue's end and the minimum
     const u64 n_al = ((u64)n + 1) & ~1ull;
     const u64 bytes = 4 * n_al * sizeof(u32) + 2 * sizeof(u32);
-    if (c->core_cap_opt >= 0 && bytes > (u64)c->core_cap_opt)
-        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (remaining degrees, layers, core numbers, the queue) needs %llu bytes of device memory", fn_name,
-                 n, (unsigned long long)bytes);
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    CoreRun run;
-    run.c = c;
-    const hipError_t e = hipMalloc(&run.arena, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        run.arena = nullptr;
-        LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP,
-                 "%s: the state of %u vertices (remaining degrees, layers, core numbers, the queue) needs %llu bytes of device memory: %s", fn_name, n,
-                 (unsigned long long)bytes, hipGetErrorString(e));
-    }
+    LzxGraphRun run(c);
+    char what[96];
+    std::snprintf(what, sizeof what, "the state of %u vertices (remaining degrees, layers, core numbers, the queue)", n);
+    LZX_TRY(lzx_alloc_state(fn_name, what, c->core_cap_opt, bytes, bytes, &run.arena));
     u32 *d_deg = static_cast<u32 *>(run.arena), *d_layer = d_deg + n_al, *d_core = d_layer + n_al, *d_order = d_core + n_al;
     u32 *d_counters = d_order + n_al;
     LZX_HIP(hipEventCreate(&run.ev0));
@@ -239,9 +167,7 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
 
     // lanes per row of the window: about half the mean degree of the rows that have an edge.  Rows of more than 64 G entries
     // (256 ... 2048: more than 64 trips of a group) go to the long-row launch.
-    const u64 mean = c->nnz / std::max<u64>(c->n_active, 1);
-    u32 G = 4;
-    while (G < 32 && 2 * G <= mean) G *= 2;
+    const u32 G = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32);
     const u32 long_row = c->core_long_opt > 0 ? (u32)std::min<int64_t>(c->core_long_opt, 0xffffffff) : 64 * G;
     const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_CORE_BLOCK), 1), LZX_CORE_SLICES);
     const u32 gb = (n + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK;
@@ -280,12 +206,10 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
             if (rounds == 1 && k == 0) core0 = queued;
             if (queued >= n) break;   // everything is queued: the last window has nobody left to push to
             const u32 wlen = queued - wbeg;
-            switch (G) {
-            case 4: launch_peel<4>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
-            case 8: launch_peel<8>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
-            case 16: launch_peel<16>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
-            default: launch_peel<32>(st, c, d_deg, d_layer, d_core, d_order, d_counters, wbeg, wlen, k, rounds, long_row); break;
-            }
+            lzx_with_lanes<32>(G, [&](auto g) {
+                hipLaunchKernelGGL(k_core_peel<g>, dim3(lzx_row_grid(wlen, LZX_CORE_BLOCK / g)), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx,
+                                   d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, rounds, long_row);
+            });
             LZX_HIP(hipGetLastError());
             if (c->max_degree > long_row) {
                 hipLaunchKernelGGL(k_core_peel_long, dim3((wlen + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK, slices), dim3(LZX_CORE_BLOCK), 0, st,
@@ -315,7 +239,7 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
         info->rounds = rounds;
         info->reserved_ = 0;
         info->peel_ms = peel_ms;
-        info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        info->loop_ms = lzx_ms_since(t0);
     }
     return LZX_OK;
 }

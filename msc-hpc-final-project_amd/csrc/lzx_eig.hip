@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 #include "lzx_test_hooks.h"
@@ -438,14 +439,9 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
     c->k_prep = 0;
 
     const u64 basis_bytes = (u64)(nw + m + 1) * c->ldq * sizeof(double);
-    const bool capped = c->eig_basis_cap_opt >= 0 && basis_bytes > (u64)c->eig_basis_cap_opt;
-    hipError_t e = capped ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void **>(&r.d_B), basis_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        r.d_B = nullptr;
-        LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the basis of (nw + m + 1) = %u columns needs %llu bytes of device memory: %s",
-                 fn, nw + m + 1, (unsigned long long)basis_bytes, hipGetErrorString(e));
-    }
+    char what[64];
+    std::snprintf(what, sizeof what, "the basis of (nw + m + 1) = %u columns", nw + m + 1);
+    LZX_TRY(lzx_alloc_state(fn, what, c->eig_basis_cap_opt, basis_bytes, basis_bytes, (void **)&r.d_B));
     r.G = lzx_cgs_grid(c);
     const u32 Jmax = nw + m + 1, ldy = (m + LZX_EIG_CT - 1) / LZX_EIG_CT * LZX_EIG_CT;
     const u64 scratch = (u64)Jmax * r.G + 2ull * Jmax + (u64)m * m + m + r.G + (u64)m * ldy + 16;

@@ -1,0 +1,113 @@
+// lzx_graph_call.h -- what the graph routines on the caller-order CSR (d_row_ptr / d_col_idx) share: lzx_components,
+// lzx_bfs_multi / lzx_betweenness_f64 (lzx_paths.hip), lzx_triangles and lzx_core_numbers.  Host side: the preconditions of such
+// a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
+// the choice of lanes per row.  Device side: the idioms of their kernels over ascending rows and wavefront-aggregated queues.
+#pragma once
+
+#include <type_traits>
+
+#include "lzx_internal.h"
+
+// one GPU, a graph, all of it on this handle; `what`: "<what the call does> on one GPU handle"
+inline int lzx_graph_call_check(const lzx_ctx *c, const char *fn, const char *what)
+{
+    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn);
+    if (c->comm_kind != 0 || c->world > 1)
+        LZX_FAIL(LZX_ERR_STATE, "%s: %s on one GPU handle; this handle is rank %d of a communicator of %d", fn, what, c->rank, c->world);
+    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
+    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn);
+    return LZX_OK;
+}
+
+// everything a graph call allocates: its end waits for the stream and gives it back, on every return path
+struct LzxGraphRun {
+    lzx_ctx *c;
+    void *arena = nullptr, *more[2] = {nullptr, nullptr};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    explicit LzxGraphRun(lzx_ctx *c_) : c(c_) {}
+    ~LzxGraphRun()
+    {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        for (void *p : {arena, more[0], more[1]})
+            if (p) (void)hipFree(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    LzxGraphRun(const LzxGraphRun &) = delete;
+    LzxGraphRun &operator=(const LzxGraphRun &) = delete;
+};
+
+// *out = alloc_bytes of device memory for a state of state_bytes (`what` names it), or the error: a state above cap (a test
+// shape *_state_bytes; < 0: none) counts as out of device memory (lzx_solve.hip)
+int lzx_alloc_state(const char *fn, const char *what, int64_t cap, u64 state_bytes, u64 alloc_bytes, void **out);
+
+// lanes per row: about half the mean row length, so that a typical row is two loads per lane; 4 .. max_g
+inline u32 lzx_lanes_per_row(u64 mean, u32 max_g)
+{
+    u32 G = 4;
+    while (G < max_g && 2 * G <= mean) G *= 2;
+    return G;
+}
+
+// f(std::integral_constant<u32, G>{}) for G = 4, 8, ... MAX_G (32 or 64; anything else counts as MAX_G): the launch of a
+// kernel template over the lanes per row.  Only the widths up to MAX_G are instantiated.
+template <u32 MAX_G, typename F>
+void lzx_with_lanes(u32 G, F f)
+{
+    if (G == 4) f(std::integral_constant<u32, 4>{});
+    else if (G == 8) f(std::integral_constant<u32, 8>{});
+    else if (G == 16) f(std::integral_constant<u32, 16>{});
+    else if (G == 32 || MAX_G == 32) f(std::integral_constant<u32, 32>{});
+    else if constexpr (MAX_G == 64) f(std::integral_constant<u32, 64>{});
+}
+// workgroups that take rows_per_block rows each
+inline u32 lzx_row_grid(u64 rows, u32 rows_per_block) { return (u32)((rows + rows_per_block - 1) / rows_per_block); }
+
+// ---- device ----
+// first position in the ascending list[0 .. len) whose entry is >= x
+__device__ __forceinline__ u32 lzx_lower_bound(const u32 *list, u32 len, u32 x)
+{
+    u32 lo = 0, hi = len;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (list[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// d_v: the entries of row v without the diagonal -- the row's length, minus one if a binary search finds v in it
+__device__ __forceinline__ u32 lzx_degree_no_diagonal(const u64 *row_ptr, const u32 *col_idx, u64 v)
+{
+    const u64 beg = row_ptr[v];
+    const u32 len = (u32)(row_ptr[v + 1] - beg);
+    const u32 at = lzx_lower_bound(col_idx + beg, len, (u32)v);
+    return len - ((at < len && col_idx[beg + at] == (u32)v) ? 1u : 0u);
+}
+
+// the calling lanes for which `take` holds get consecutive places behind *tail: one atomic per wavefront.  Every lane of the
+// wavefront must call it together.  Returns the lane's place (meaningless where !take).
+__device__ __forceinline__ u32 lzx_wave_append(bool take, u32 *tail)
+{
+    const ull m = __ballot(take);
+    if (m == 0) return 0;   // (the same for every lane)
+    const u32 lane = threadIdx.x & 63;
+    const int first = __builtin_ctzll(m);
+    u32 base = 0;
+    if (lane == (u32)first) base = atomicAdd(tail, (u32)__builtin_popcountll(m));
+    base = (u32)__shfl((int)base, first, 64);
+    return base + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+}
+
+// the prologue of a long-row kernel: the ids of the threads whose row is long are collected in s_rows (LDS, one place per
+// thread of the workgroup, in no particular order) and counted in *s_count (LDS).  Every thread of the workgroup must call it.
+// Returns the count.
+__device__ __forceinline__ u32 lzx_collect_long_rows(bool mine_is_long, u32 id, u32 *s_rows, u32 *s_count)
+{
+    if (threadIdx.x == 0) *s_count = 0;
+    __syncthreads();
+    if (mine_is_long) s_rows[atomicAdd(s_count, 1u)] = id;
+    __syncthreads();
+    return *s_count;
+}

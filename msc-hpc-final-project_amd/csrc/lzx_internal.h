@@ -15,6 +15,7 @@
 
 typedef uint32_t u32;
 typedef uint64_t u64;
+typedef unsigned long long ull;   // what the 64-bit atomics and shuffles take
 
 // ---- error plumbing -------------------------------------------------------------------------------
 void lzx_set_error(const char *fmt, ...);
@@ -460,9 +461,6 @@ inline double lzx_ms_since(std::chrono::steady_clock::time_point t)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
-// *out = alloc_bytes of device memory for a state of state_bytes (`what` describes it), or the error: a state above the test
-// shape solve_state_bytes counts as out of device memory
-int lzx_cg_alloc_state(lzx_ctx *c, const char *fn, const char *what, u64 state_bytes, u64 alloc_bytes, double **out);
 // the distinct values of v[0 .. n), ascending or descending; slot[i]: the place of v[i] among them
 std::vector<double> lzx_cg_distinct(const double *v, u32 n, bool descending, std::vector<u32> &slot);
 // From b (b . b = bb; a.pp: its partials): r = p = p_s = b and both parity states, then the loop -- the SpMV of p, k_lap_apply

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
@@ -128,8 +129,8 @@ extern "C" int lzx_pagerank_f64(lzx_handle h, const double *v, uint32_t nd, cons
     const u32 ncols = 2 + 2 * nu;
     const u64 state_bytes = (u64)ncols * c->ldq * sizeof(double);
     char what[64];
-    std::snprintf(what, sizeof what, "%u vectors (b, r, p, 2 per damping)", ncols);
-    LZX_TRY(lzx_cg_alloc_state(c, fn, what, state_bytes, state_bytes, &run.d_V));
+    std::snprintf(what, sizeof what, "the state of %u vectors (b, r, p, 2 per damping)", ncols);
+    LZX_TRY(lzx_alloc_state(fn, what, c->solve_cap_opt, state_bytes, state_bytes, (void **)&run.d_V));
     auto col = [&](u32 i) { return run.d_V + (size_t)i * c->ldq; };
     double *vb = col(0), *vr = col(1), *vp = col(2), *vz0 = col(3), *vZ = col(4), *vP = col(3 + nu);
 

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 #include "lzx_multi_shared.h"
@@ -189,22 +190,6 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_paths_unpack(const T *in, u
 
 // ==================================================================================================== host
 namespace {
-struct PathsRun {   // everything the call allocates: gone on every return path
-    lzx_ctx *c = nullptr;
-    void *arena = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~PathsRun()
-    {
-        if (c) {
-            (void)hipSetDevice(c->device);
-            (void)hipStreamSynchronize(c->stream);
-        }
-        if (arena) (void)hipFree(arena);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-
 struct PathsCall {
     const char *fn;
     uint32_t ns;
@@ -246,7 +231,7 @@ static int paths_level(lzx_ctx *c, const PathsState &s, u32 b, int32_t d)
 
 // one batch: sources first .. first + b - 1 of the call
 template <u32 B>
-static int paths_batch(lzx_ctx *c, const PathsCall &q, PathsRun &run, PathsState &s, u32 first, u32 b)
+static int paths_batch(lzx_ctx *c, const PathsCall &q, LzxGraphRun &run, PathsState &s, u32 first, u32 b)
 {
     const u64 n = c->n, nB = n * B;
     hipStream_t st = c->stream;
@@ -334,12 +319,8 @@ static int paths_run(lzx_handle h, const PathsCall &q)
     const char *fn = q.fn;
     // what needs no device
     if (q.ns == 0) LZX_FAIL(LZX_ERR_ARG, "%s: ns == 0", fn);
-    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn);
     lzx_ctx *c = h;
-    if (c->comm_kind != 0 || c->world > 1)
-        LZX_FAIL(LZX_ERR_STATE, "%s: the search runs on one GPU handle; this handle is rank %d of a communicator of %d", fn, c->rank, c->world);
-    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
-    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn);
+    LZX_TRY(lzx_graph_call_check(c, fn, "the search runs"));
     if (!q.sources && (u64)q.ns != c->n)
         LZX_FAIL(LZX_ERR_ARG, "%s: null sources mean every vertex: ns must be n = %llu, got %u", fn, (unsigned long long)c->n, q.ns);
     for (u32 i = 0; q.sources && i < q.ns; ++i)
@@ -355,20 +336,10 @@ static int paths_run(lzx_handle h, const PathsCall &q)
     const u64 b_dist = round16(sizeof(int32_t) * n * Bmax), b_vec = sizeof(double) * n * Bmax, b_bc = q.bc ? sizeof(double) * n : 0;
     const u64 b_part = sizeof(double) * (u64)m->n_parts * Bmax, b_prow = round16(sizeof(u32) * (u64)m->n_parts);
     const u64 bytes = b_dist + b_vec * (third ? 2 : 1) + b_bc + b_part + b_prow + sizeof(u32) * LZX_BFS_BATCH;
-    if (c->bfs_cap_opt >= 0 && bytes > (u64)c->bfs_cap_opt)
-        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u interleaved columns on %llu vertices needs %llu bytes of device memory", fn, Bmax,
-                 (unsigned long long)n, (unsigned long long)bytes);
-    PathsRun run;
-    run.c = c;
-    {
-        hipError_t e = hipMalloc(&run.arena, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            run.arena = nullptr;
-            LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the state of %u interleaved columns on %llu vertices needs %llu bytes of device memory: %s",
-                     fn, Bmax, (unsigned long long)n, (unsigned long long)bytes, hipGetErrorString(e));
-        }
-    }
+    LzxGraphRun run(c);
+    char what[80];
+    std::snprintf(what, sizeof what, "the state of %u interleaved columns on %llu vertices", Bmax, (ull)n);
+    LZX_TRY(lzx_alloc_state(fn, what, c->bfs_cap_opt, bytes, bytes, &run.arena));
     PathsState s{};
     char *p = static_cast<char *>(run.arena);
     s.dist = reinterpret_cast<int32_t *>(p); p += b_dist;
@@ -408,7 +379,7 @@ static int paths_run(lzx_handle h, const PathsCall &q)
         q.info->max_level = s.max_level;
         q.info->sweeps = s.sweeps;
         q.info->sweep_ms = s.sweep_ms;
-        q.info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        q.info->loop_ms = lzx_ms_since(t0);
     }
     return LZX_OK;
 }

@@ -11,6 +11,32 @@ __device__ __forceinline__ void block_partial(double s, double *sh, double *out)
     if (threadIdx.x == 0) out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// The integer statistics of the graph routines: every lane gets the wavefront's sum / maximum ...
+__device__ __forceinline__ ull wave_sum_u64(ull v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ ull wave_max_u64(ull v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const ull other = __shfl_xor(v, o, 64);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+// ... and one thread the largest of the four wavefronts' maxima s[0 .. 4) (LDS, behind a barrier)
+__device__ __forceinline__ ull block_max_u64(const ull *s)
+{
+    ull k = s[0];
+    for (u32 w = 1; w < 4; ++w) k = s[w] > k ? s[w] : k;
+    return k;
+}
+
 // Sum p[0..np) identically in every workgroup of a 256-thread launch. sh: >= 4 doubles of LDS.
 __device__ __forceinline__ double block_sum_fixed_256(const double *p, u32 np, double *sh)
 {

@@ -1,7 +1,7 @@
 // lzx_solve.hip -- (sigma_s I - A) x_s = b or (sigma_s I + L) x_s = b for up to 16 shifts at once by multi-shift conjugate
 // gradients (Frommer 2003; Jegerlehner): include/lzx.h, lzx_solve_shifted_f64; DESIGN.md section 13.  The loop and its two
 // kernels also run PageRank (lzx_pagerank.hip) in their degree-weighted form; the first host part
-// (state allocation, distinct values, lzx_cg_multishift) is declared in lzx_internal.h and serves lzx_solve_multi.hip too.
+// (distinct values, lzx_cg_multishift: lzx_internal.h) serves lzx_solve_multi.hip too, lzx_alloc_state every call with a state.
 //
 // One Krylov sequence: plain CG on the seed system S(sigma_0) (the smallest shift), every other shift s following it through
 // the scalars zeta_s, alpha_s, beta_s.  Its residual is zeta_{s,j} r_j, so no shift needs a matvec of its own.
@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
@@ -213,14 +214,14 @@ k_cg_resid(const double *__restrict__ b, const double *__restrict__ x, const dou
 }
 
 // ==================================================================================================== host: shared by the CG entry points
-int lzx_cg_alloc_state(lzx_ctx *c, const char *fn, const char *what, u64 state_bytes, u64 alloc_bytes, double **out)
+int lzx_alloc_state(const char *fn, const char *what, int64_t cap, u64 state_bytes, u64 alloc_bytes, void **out)
 {
-    const bool capped = c->solve_cap_opt >= 0 && state_bytes > (u64)c->solve_cap_opt;
-    const hipError_t e = capped ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void **>(out), alloc_bytes);
+    const bool capped = cap >= 0 && state_bytes > (u64)cap;
+    const hipError_t e = capped ? hipErrorOutOfMemory : hipMalloc(out, alloc_bytes);
     if (e == hipSuccess) return LZX_OK;
     (void)hipGetLastError();
     *out = nullptr;
-    LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: the state of %s needs %llu bytes of device memory: %s", fn, what,
+    LZX_FAIL(e == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: %s needs %llu bytes of device memory: %s", fn, what,
              (unsigned long long)state_bytes, hipGetErrorString(e));
 }
 
@@ -323,8 +324,8 @@ extern "C" int lzx_solve_shifted_f64(lzx_handle h, const double *b, uint32_t ns,
     const u32 ncols = 2 + 2 * nu + nw;
     const u64 state_bytes = (u64)ncols * c->ldq * sizeof(double);
     char what[80];
-    std::snprintf(what, sizeof what, "%u vectors (b, r, p, 2 per shift, %u deflation)", ncols, nw);
-    LZX_TRY(lzx_cg_alloc_state(c, fn, what, state_bytes, state_bytes, &run.d_V));
+    std::snprintf(what, sizeof what, "the state of %u vectors (b, r, p, 2 per shift, %u deflation)", ncols, nw);
+    LZX_TRY(lzx_alloc_state(fn, what, c->solve_cap_opt, state_bytes, state_bytes, (void **)&run.d_V));
     auto col = [&](u32 i) { return run.d_V + (size_t)i * c->ldq; };
     double *vb = col(0), *vr = col(1), *vp = col(2), *vx0 = col(3), *vX = col(4), *vP = col(3 + nu), *vW = col(2 + 2 * nu);
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 #include "lzx_multi_shared.h"
@@ -420,7 +421,7 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
     run.c = c;
     const u64 part_doubles = (u64)n_seg * B;
     const u64 state_bytes = ((5ull * B + nw) * n + 3 * part_doubles) * sizeof(double);
-    // (the cap again, ahead of lzx_cg_alloc_state's: before the work vectors are made, and this text ends without a runtime error)
+    // (the cap again, ahead of lzx_alloc_state's: before the work vectors are made, and this text ends without a runtime error)
     if (c->solve_cap_opt >= 0 && state_bytes > (u64)c->solve_cap_opt)
         LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of 5 x %u interleaved columns and %u deflation vectors needs %llu bytes of device memory", fn, B, nw,
                  (unsigned long long)state_bytes);
@@ -429,8 +430,8 @@ static int mcg_run(lzx_ctx *c, const McgCall &q, const char *fn)
     run.own_work = !(m->d_V && m->wB == B);
     LZX_TRY(lzx_multi_ensure_work(c, B, false));
     char what[80];
-    std::snprintf(what, sizeof what, "5 x %u interleaved columns and %u deflation vectors", B, nw);
-    LZX_TRY(lzx_cg_alloc_state(c, fn, what, state_bytes, sizeof(double) * (4 * nB + (u64)nw * n), &run.d_V));
+    std::snprintf(what, sizeof what, "the state of 5 x %u interleaved columns and %u deflation vectors", B, nw);
+    LZX_TRY(lzx_alloc_state(fn, what, c->solve_cap_opt, state_bytes, sizeof(double) * (4 * nB + (u64)nw * n), (void **)&run.d_V));
     double *vB = run.d_V, *vR = vB + nB, *vP = vR + nB, *vX = vP + nB, *vW = vX + nB;
 
     // scalars: [rr partials | pp partials | W partials | tmp | state x 2 | mid]

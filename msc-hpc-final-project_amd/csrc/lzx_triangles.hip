@@ -4,7 +4,7 @@
 //
 // Orientation.  d_v = the entries of row v without the diagonal.  Vertices are ranked by (d_v, v) and every edge that is not a
 // self loop is kept once, in the row of its lower-ranked end: the oriented CSR (64-bit row pointers, u32 columns).
-//   degrees    k_tri_degrees           one thread per row: the row's length, minus one if a binary search finds v in it
+//   degrees    k_tri_degrees           one thread per row: lzx_degree_no_diagonal (lzx_graph_call.h)
 //   out-counts k_tri_orient (count)    a group of G lanes per row counts the neighbours of higher rank; hipcub's exclusive scan
 //                                      turns the counts into the row pointers, in place
 //   fill       k_tri_orient (fill)     the same walk writes them: a ballot over the group orders the kept entries, so the
@@ -33,10 +33,9 @@
 #include <cstring>
 
 #include "lzx_internal.h"
+#include "lzx_graph_call.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
-
-typedef unsigned long long ull;
 
 static constexpr u32 LZX_TRI_BLOCK = 256;
 static constexpr u32 LZX_TRI_STAT_GRID = 1024;   // block partials of the statistics pass (at most)
@@ -44,26 +43,10 @@ static constexpr u32 LZX_TRI_LONG = 128;         // out-entries beyond which a r
 static constexpr u32 LZX_TRI_STAGE = 4096;       // entries of N+(a) staged in LDS by k_tri_count_long (at most)
 static constexpr u32 LZX_TRI_SLICES = 64;        // workgroups a long row's out-edges are dealt to (at most)
 
-// first position in the ascending list[0 .. len) whose entry is >= x
-__device__ __forceinline__ u32 tri_lower_bound(const u32 *list, u32 len, u32 x)
-{
-    u32 lo = 0, hi = len;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (list[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(LZX_TRI_BLOCK) k_tri_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 n)
 {
     const u64 v = (u64)blockIdx.x * LZX_TRI_BLOCK + threadIdx.x;
-    if (v >= n) return;
-    const u64 beg = row_ptr[v];
-    const u32 len = (u32)(row_ptr[v + 1] - beg);
-    const u32 at = tri_lower_bound(col_idx + beg, len, (u32)v);
-    deg[v] = len - ((at < len && col_idx[beg + at] == (u32)v) ? 1u : 0u);
+    if (v < n) deg[v] = lzx_degree_no_diagonal(row_ptr, col_idx, v);
 }
 
 // G lanes per row.  fill == nullptr: count[row] = the neighbours of higher rank (and count[n] = 0, kmax = the largest count);
@@ -136,7 +119,7 @@ k_tri_count(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list)
         u32 hits = 0;
         for (u32 j = sub; j < ks; j += G) {
             const u32 x = S[j];
-            const u32 at = tri_lower_bound(L, kl, x);
+            const u32 at = lzx_lower_bound(L, kl, x);
             if (at < kl && L[at] == x) {
                 ++hits;
                 atomicAdd(&tri[x], 1ull);
@@ -160,12 +143,8 @@ k_tri_count_long(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list,
     __shared__ u32 s_a[LZX_TRI_STAGE];     // N+(a)
     __shared__ u32 s_hit[LZX_TRI_STAGE];   // hits on s_a[j] as the triangle's highest rank
     __shared__ ull s_tot[LZX_TRI_BLOCK / 64];
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
     const u64 mine = (u64)blockIdx.x * LZX_TRI_BLOCK + threadIdx.x;
-    if (mine < n && orp[mine + 1] - orp[mine] > long_list) s_rows[atomicAdd(&s_count, 1u)] = (u32)mine;
-    __syncthreads();
-    const u32 count = s_count;
+    const u32 count = lzx_collect_long_rows(mine < n && orp[mine + 1] - orp[mine] > long_list, (u32)mine, s_rows, &s_count);
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr u32 W = LZX_TRI_BLOCK / 64;
     for (u32 r = 0; r < count; ++r) {
@@ -190,7 +169,7 @@ k_tri_count_long(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list,
             if (ka <= kb) {   // walk N+(a), search N+(b)
                 for (u32 j = lane; j < ka; j += 64) {
                     const u32 x = staged ? s_a[j] : A[j];
-                    const u32 at = tri_lower_bound(B, kb, x);
+                    const u32 at = lzx_lower_bound(B, kb, x);
                     if (at < kb && B[at] == x) {
                         ++hits;
                         if (staged) atomicAdd(&s_hit[j], 1u);
@@ -201,13 +180,13 @@ k_tri_count_long(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list,
                 for (u32 j = lane; j < kb; j += 64) {
                     const u32 x = B[j];
                     if (staged) {
-                        const u32 at = tri_lower_bound(s_a, ka, x);
+                        const u32 at = lzx_lower_bound(s_a, ka, x);
                         if (at < ka && s_a[at] == x) {
                             ++hits;
                             atomicAdd(&s_hit[at], 1u);
                         }
                     } else {
-                        const u32 at = tri_lower_bound(A, ka, x);
+                        const u32 at = lzx_lower_bound(A, ka, x);
                         if (at < ka && A[at] == x) {
                             ++hits;
                             atomicAdd(&tri[x], 1ull);
@@ -234,23 +213,6 @@ k_tri_count_long(const u64 *orp, const u32 *oci, ull *tri, u32 n, u32 long_list,
     }
 }
 
-__device__ __forceinline__ ull tri_wave_sum(ull v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ ull tri_wave_max(ull v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const ull other = __shfl_xor(v, o, 64);
-        v = other > v ? other : v;
-    }
-    return v;
-}
-
 // c_v, and block partials: sum c (fp64), sum t, sum d (d - 1) / 2, max t
 __global__ void __launch_bounds__(LZX_TRI_BLOCK)
 k_tri_stats(const ull *tri, const u32 *deg, u32 n, double *clus, double *part_c, ull *part_t, ull *part_w, ull *part_m)
@@ -270,9 +232,9 @@ k_tri_stats(const ull *tri, const u32 *deg, u32 n, double *clus, double *part_c,
         sm = t > sm ? t : sm;
     }
     sc = wave_sum(sc);
-    st = tri_wave_sum(st);
-    sw = tri_wave_sum(sw);
-    sm = tri_wave_max(sm);
+    st = wave_sum_u64(st);
+    sw = wave_sum_u64(sw);
+    sm = wave_max_u64(sm);
     if ((threadIdx.x & 63) == 0) {
         s_c[threadIdx.x >> 6] = sc;
         s_t[threadIdx.x >> 6] = st;
@@ -284,9 +246,7 @@ k_tri_stats(const ull *tri, const u32 *deg, u32 n, double *clus, double *part_c,
         part_c[blockIdx.x] = ((s_c[0] + s_c[1]) + s_c[2]) + s_c[3];
         part_t[blockIdx.x] = s_t[0] + s_t[1] + s_t[2] + s_t[3];
         part_w[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        ull mx = s_m[0];
-        for (u32 w = 1; w < LZX_TRI_BLOCK / 64; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
-        part_m[blockIdx.x] = mx;
+        part_m[blockIdx.x] = block_max_u64(s_m);
     }
 }
 
@@ -303,9 +263,9 @@ k_tri_close(const double *part_c, const ull *part_t, const ull *part_w, const ul
         sw += part_w[i];
         sm = part_m[i] > sm ? part_m[i] : sm;
     }
-    st = tri_wave_sum(st);
-    sw = tri_wave_sum(sw);
-    sm = tri_wave_max(sm);
+    st = wave_sum_u64(st);
+    sw = wave_sum_u64(sw);
+    sm = wave_max_u64(sm);
     if ((threadIdx.x & 63) == 0) {
         s_t[threadIdx.x >> 6] = st;
         s_w[threadIdx.x >> 6] = sw;
@@ -316,68 +276,22 @@ k_tri_close(const double *part_c, const ull *part_t, const ull *part_w, const ul
         out4[0] = (ull)__double_as_longlong(total / (double)n);
         out4[1] = s_t[0] + s_t[1] + s_t[2] + s_t[3];
         out4[2] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        ull mx = s_m[0];
-        for (u32 w = 1; w < LZX_VEC_BLOCK / 64; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
-        out4[3] = mx;
+        out4[3] = block_max_u64(s_m);
     }
-}
-
-namespace {
-struct TriRun {   // everything the call allocates: gone on every return path
-    lzx_ctx *c = nullptr;
-    void *arena = nullptr, *tmp = nullptr, *oci = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~TriRun()
-    {
-        if (c) {
-            (void)hipSetDevice(c->device);
-            (void)hipStreamSynchronize(c->stream);
-        }
-        if (arena) (void)hipFree(arena);
-        if (tmp) (void)hipFree(tmp);
-        if (oci) (void)hipFree(oci);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-}   // namespace
-
-template <u32 G>
-static void launch_orient(hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
-{
-    const u32 rows_per_block = LZX_TRI_BLOCK / G;
-    const u32 grid = (u32)((c->n + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(k_tri_orient<G>, dim3(grid), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg, (u32)c->n, count, orp, fill, kmax);
 }
 
 static void orient_pass(u32 G, hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
 {
-    switch (G) {
-    case 4: launch_orient<4>(st, c, deg, count, orp, fill, kmax); break;
-    case 8: launch_orient<8>(st, c, deg, count, orp, fill, kmax); break;
-    case 16: launch_orient<16>(st, c, deg, count, orp, fill, kmax); break;
-    case 32: launch_orient<32>(st, c, deg, count, orp, fill, kmax); break;
-    default: launch_orient<64>(st, c, deg, count, orp, fill, kmax); break;
-    }
-}
-
-template <u32 G>
-static void launch_count(hipStream_t st, u32 n, const u64 *orp, const u32 *oci, ull *tri, u32 long_list)
-{
-    const u32 rows_per_block = LZX_TRI_BLOCK / G;
-    const u32 grid = (u32)(((u64)n + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(k_tri_count<G>, dim3(grid), dim3(LZX_TRI_BLOCK), 0, st, orp, oci, tri, n, long_list);
+    lzx_with_lanes<64>(G, [&](auto g) {
+        hipLaunchKernelGGL(k_tri_orient<g>, dim3(lzx_row_grid(c->n, LZX_TRI_BLOCK / g)), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg,
+                           (u32)c->n, count, orp, fill, kmax);
+    });
 }
 
 extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lzx_triangles_info *info)
 {
     const char *fn_name = "lzx_triangles";
-    // what needs no device
-    if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn_name);
-    if (c->comm_kind != 0 || c->world > 1)
-        LZX_FAIL(LZX_ERR_STATE, "%s: triangles are counted on one GPU handle; this handle is rank %d of a communicator of %d", fn_name, c->rank, c->world);
-    if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn_name);
-    if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn_name);
+    LZX_TRY(lzx_graph_call_check(c, fn_name, "triangles are counted"));
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
 
@@ -387,24 +301,12 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     const u32 np = (u32)std::min<u64>(LZX_TRI_STAT_GRID, ((u64)n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK);
     const u64 bytes = sizeof(u64) * ((u64)n + 1) + sizeof(ull) * n + sizeof(double) * n + (u64)np * (sizeof(double) + 3 * sizeof(ull)) +
                       4 * sizeof(ull) + 2 * sizeof(u32) + sizeof(u32) * n_al;
-    if (c->tri_cap_opt >= 0 && bytes > (u64)c->tri_cap_opt)
-        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (row pointers, degrees, counts, coefficients, before the oriented columns) needs %llu bytes of device memory",
-                 fn_name, n, (unsigned long long)bytes);
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    TriRun run;
-    run.c = c;
-#define LZX_TRI_ALLOC(ptr, size, what)                                                                                                     \
-    do {                                                                                                                                   \
-        const hipError_t e_ = hipMalloc(&(ptr), (size));                                                                                   \
-        if (e_ != hipSuccess) {                                                                                                            \
-            (void)hipGetLastError();                                                                                                       \
-            (ptr) = nullptr;                                                                                                               \
-            LZX_FAIL(e_ == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP, "%s: %s of %u vertices needs %llu bytes of device memory: %s", \
-                     fn_name, what, n, (unsigned long long)(size), hipGetErrorString(e_));                                                 \
-        }                                                                                                                                  \
-    } while (0)
-    LZX_TRI_ALLOC(run.arena, bytes, "the state (row pointers, degrees, counts, coefficients)");
+    LzxGraphRun run(c);   // more[0]: the scan's scratch, more[1]: the oriented columns
+    char what[160];
+    std::snprintf(what, sizeof what, "the state of %u vertices (row pointers, degrees, counts, coefficients, before the oriented columns)", n);
+    LZX_TRY(lzx_alloc_state(fn_name, what, c->tri_cap_opt, bytes, bytes, &run.arena));
     u64 *d_orp = static_cast<u64 *>(run.arena);
     ull *d_tri = reinterpret_cast<ull *>(d_orp + n + 1);
     double *d_clus = reinterpret_cast<double *>(d_tri + n);
@@ -416,14 +318,13 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     size_t tmp_bytes = 0;
     LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_orp, d_orp, scan_len, st));
     tmp_bytes = std::max<size_t>(tmp_bytes, 16);
-    LZX_TRI_ALLOC(run.tmp, tmp_bytes, "the scan's scratch for the row pointers");
+    std::snprintf(what, sizeof what, "the scan's scratch for the row pointers of %u vertices", n);
+    LZX_TRY(lzx_alloc_state(fn_name, what, -1, tmp_bytes, tmp_bytes, &run.more[0]));
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // ---- the oriented copy ----
-    const u64 mean = c->nnz / std::max<u64>(c->n_active, 1);
-    u32 Go = 4;
-    while (Go < 64 && 2 * Go <= mean) Go *= 2;
+    const u32 Go = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 64);
     const u32 gb = (n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK;
     LZX_HIP(hipEventRecord(run.ev0, st));
     LZX_HIP(hipMemsetAsync(d_kmax, 0, 2 * sizeof(u32), st));
@@ -432,7 +333,7 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     LZX_HIP(hipGetLastError());
     orient_pass(Go, st, c, d_deg, d_orp, nullptr, nullptr, d_kmax);
     LZX_HIP(hipGetLastError());
-    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(run.tmp, tmp_bytes, d_orp, d_orp, scan_len, st));
+    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(run.more[0], tmp_bytes, d_orp, d_orp, scan_len, st));
     u64 m = 0;
     u32 kmax = 0;
     LZX_HIP(hipMemcpyAsync(&m, d_orp + n, sizeof(u64), hipMemcpyDeviceToHost, st));
@@ -441,12 +342,9 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     // the oriented columns: the scan's total, which is what the fill writes whatever was handed over ((nnz - self loops) / 2 of a
     // symmetric matrix)
     const u64 col_bytes = sizeof(u32) * std::max<u64>(m, 1);
-    if (c->tri_cap_opt >= 0 && bytes + col_bytes > (u64)c->tri_cap_opt)
-        LZX_FAIL(LZX_ERR_NOMEM, "%s: the state of %u vertices (an oriented copy of %llu entries, degrees, counts, coefficients) needs %llu bytes of device memory", fn_name,
-                 n, (unsigned long long)m, (unsigned long long)(bytes + col_bytes));
-    LZX_TRI_ALLOC(run.oci, col_bytes, "the oriented copy's columns");
-#undef LZX_TRI_ALLOC
-    u32 *d_oci = static_cast<u32 *>(run.oci);
+    std::snprintf(what, sizeof what, "the state of %u vertices (an oriented copy of %llu entries, degrees, counts, coefficients)", n, (ull)m);
+    LZX_TRY(lzx_alloc_state(fn_name, what, c->tri_cap_opt, bytes + col_bytes, col_bytes, &run.more[1]));
+    u32 *d_oci = static_cast<u32 *>(run.more[1]);
     if (m) {
         orient_pass(Go, st, c, d_deg, nullptr, d_orp, d_oci, nullptr);
         LZX_HIP(hipGetLastError());
@@ -457,19 +355,14 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     LZX_HIP(hipEventElapsedTime(&orient_ms, run.ev0, run.ev1));
 
     // ---- counting: lanes per row about half the mean oriented degree ----
-    const u64 mean_out = m / std::max<u64>(c->n_active, 1);
-    u32 G = 4;
-    while (G < 32 && 2 * G <= mean_out) G *= 2;
+    const u32 G = lzx_lanes_per_row(m / std::max<u64>(c->n_active, 1), 32);
     const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
     const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
     LZX_HIP(hipEventRecord(run.ev0, st));
     if (m) {
-        switch (G) {
-        case 4: launch_count<4>(st, n, d_orp, d_oci, d_tri, long_list); break;
-        case 8: launch_count<8>(st, n, d_orp, d_oci, d_tri, long_list); break;
-        case 16: launch_count<16>(st, n, d_orp, d_oci, d_tri, long_list); break;
-        default: launch_count<32>(st, n, d_orp, d_oci, d_tri, long_list); break;
-        }
+        lzx_with_lanes<32>(G, [&](auto g) {
+            hipLaunchKernelGGL(k_tri_count<g>, dim3(lzx_row_grid(n, LZX_TRI_BLOCK / g)), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n, long_list);
+        });
         LZX_HIP(hipGetLastError());
         if (kmax > long_list) {
             const u32 slices = std::min<u32>(std::max<u32>(kmax / 64, 1), LZX_TRI_SLICES);
@@ -504,7 +397,7 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
         info->avg_clustering = avg;
         info->orient_ms = orient_ms;
         info->count_ms = count_ms;
-        info->loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        info->loop_ms = lzx_ms_since(t0);
     }
     return LZX_OK;
 }
