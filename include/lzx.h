@@ -615,8 +615,8 @@ int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NU
  *             degrees, 8 n of counts, 8 n of coefficients, a few KiB of partials and the scan's scratch.
  *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
  *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  The checks that need no device come first.
- *   limits    one GPU handle; undirected, unweighted graphs; no per-edge support or k-truss, no sampling
- *             estimator.  A matrix that is not symmetric is not detected: the call stays within its memory (the columns are
+ *   limits    one GPU handle; undirected, unweighted graphs; no sampling estimator (the triangles per EDGE and the k-truss
+ *             are lzx_truss, below).  A matrix that is not symmetric is not detected: the call stays within its memory (the columns are
  *             sized by the count the fill repeats) and its counts mean nothing. */
 typedef struct lzx_triangles_info {
     uint64_t triangles;        /* T: triangles of the graph, each counted once */
@@ -666,8 +666,8 @@ int lzx_triangles(lzx_handle h, uint64_t *tri /* [n] or NULL */, double *cluster
  *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
  *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  LZX_ERR_LIMIT: more than n + 1 rounds (cannot happen).
  *             The checks that need no device come first.
- *   limits    one GPU handle; undirected, unweighted graphs; no k-truss or per-edge support; no degeneracy ordering (the
- *             order inside a round is not deterministic).  A matrix that is not symmetric is not detected: its numbers mean
+ *   limits    one GPU handle; undirected, unweighted graphs; no degeneracy ordering (the order inside a round is not
+ *             deterministic); cohesion by triangles instead of degrees -- per-edge support, the k-truss -- is lzx_truss, below.  A matrix that is not symmetric is not detected: its numbers mean
  *             nothing, but the call stays within its memory and ends -- the mark is taken by a compare-and-swap, so no vertex
  *             is queued twice even where a counter wraps. */
 typedef struct lzx_core_info {
@@ -681,6 +681,80 @@ typedef struct lzx_core_info {
 } lzx_core_info;
 int lzx_core_numbers(lzx_handle h, uint32_t *core /* [n] or NULL */, uint32_t *layer /* [n] or NULL */,
                      lzx_core_info *info /* or NULL */);
+
+/* ---- edge support and truss numbers -------------------------------------------------------------------
+ * lzx_truss: the truss decomposition of the handle's graph read as undirected and unweighted -- the edge sets networkx.k_truss
+ * returns, for every k at once -- peeled on the device over the caller-order CSR.
+ *   outputs   support(e) = the number of triangles through the undirected edge e.  A self loop is no edge and closes no
+ *             triangle: it changes nothing in any output.  Rounds are numbered from 1 and k_0 = 2.  Round r has
+ *             k_r = max(k_{r-1}, 2 + the smallest remaining support among the remaining edges) and removes, all at once, every
+ *             remaining edge whose remaining support is <= k_r - 2, where the remaining support counts the triangles whose
+ *             three edges all remain; each removed edge gets truss = k_r and layer = r.  So every edge has truss >= 2, and
+ *             {e : truss(e) >= k} is the edge set of networkx.k_truss(G, k).
+ *             support, truss and layer are PER STORED ENTRY of the caller-order CSR: entry e of lzx_get_graph_csr's col_idx gets
+ *             the value of its undirected edge, so both copies of an edge carry the same number and (truss, col_idx, row_ptr)
+ *             is the truss matrix; a diagonal entry gets 0 in all three.  vertex_truss[v] = the largest truss number among
+ *             v's edges, 0 where v has no edge other than a loop.  Every output may be NULL; only those asked for cross PCIe.
+ *             On a graph without an edge every per-entry output is 0, max_truss = 0 and rounds = levels = 0.
+ *   info      (or NULL) edges = m, the undirected edges that are not self loops; triangles = T = sum of the supports / 3;
+ *             max_support; max_truss = the last k; main_truss_edges = the edges whose truss number is max_truss; levels = the
+ *             distinct truss numbers that occur; rounds = the peeling rounds = the largest layer; the host clock of the call,
+ *             the device event time from the first launch to the end of the support count (orientation, edge ids, support)
+ *             and of the peeling loop (the host's reads included).  The host forms the integers from the boundaries of the
+ *             queue's windows and from block partials of the supports' sum and maximum.
+ *   method    (1) lzx_triangles' oriented copy: every edge once, in the row of its lower end by (d_v, v).  The EDGE ID of an edge
+ *             is its position in the oriented columns, m < 2^32 - 1 ids (more is LZX_ERR_LIMIT); src[e] is its oriented row.
+ *             (2) eid[entry], u32 [nnz] over the caller-order CSR: entry (u, v) binary-searches its higher-ranked end in the
+ *             oriented row of its lower-ranked end; a diagonal entry, and an entry whose search fails (only on a matrix that
+ *             is not symmetric), gets 0xffffffff, and every later use range-checks what it reads.  (3) Support: lzx_triangles'
+ *             counting walk, the same split at a list of more than 128 out-entries and the same LDS staging, with u32 counters
+ *             per edge: at a hit the walked index and the search result are the positions of the two far edges, one add each;
+ *             the out-edge gets its hits in one add.  (4) Push peeling over one queue of edge ids.  State, u32 [m] each: sup,
+ *             mark (0 = not yet removed, else the layer), truss, queue; every edge is appended exactly once, a round's
+ *             frontier is a window of the queue.  When the window is empty a level starts: one thread per edge, an unmarked
+ *             edge with sup <= s (s = k - 2) is marked and appended, the others contribute to a minimum; the host tries s + 1
+ *             first and sweeps again with the minimum only if nothing was appended.  A round peels its window: for a frontier
+ *             edge e1 = (u, v) the FULL rows of u and v are intersected (the shorter walked, the longer searched; w = u and
+ *             w = v skipped), a common neighbour w gives e2 = eid[w in row u], e3 = eid[w in row v].  The triangle is dead if
+ *             mark[e2] or mark[e3] is non-zero and < r.  Otherwise: both in the window (mark == r): nothing; exactly one in
+ *             the window, say e2: e3 is decremented only if e1 < e2 (edge ids); neither: both are decremented -- every dying
+ *             triangle takes exactly one from each of its edges that stays.  A decrement is old = atomicSub(&sup[x], 1); the one
+ *             lane that sees old == s + 1 takes the mark by atomicCAS(&mark[x], 0, r + 1), writes truss[x] = s + 2 and appends
+ *             x.  A mark of 0 and one of r + 1 decide alike and marks equal to r were written by the previous launch, so every
+ *             run marks the same edges in the same round.  A group of lanes (4 to 32, from the mean degree) handles each
+ *             frontier edge; edges whose SHORTER row has more than 64 times that many entries go to a second launch, a
+ *             workgroup per edge and slice, which runs only when the graph has such a row.  Appends and the minimum are
+ *             aggregated per wavefront.  The host reads one word per round and two per level start and stops when m edges are
+ *             queued; the last window is not peeled.  (5) One gather through eid per requested per-entry output, one row pass
+ *             for vertex_truss.  All atomics are 32-bit INTEGER vector atomics, in global memory and in LDS; there is no
+ *             floating point anywhere.  No kernel waits on another workgroup; every device loop is bounded by a row, list or
+ *             window length; every append is clamped to the queue's m entries.
+ *   bits      every output and every integer of info is canonical: any correct algorithm gives these bits.  The order inside
+ *             a window is not deterministic and is no output.
+ *   state     the call touches none: it voids no prepared or chunked decomposition and leaves the resident bases and the batch
+ *             state alone.  Everything it allocates is freed before it returns, on every path: for the vertices
+ *             8 (n + 1) + 4 n bytes, 16 KiB of partials and four words (12 n, roughly); then, once the scan has counted m,
+ *             24 m (oriented columns, src, sup, mark, truss, queue) + 4 nnz (eid) + 4 nnz (one staging buffer for the
+ *             per-entry outputs) -- in all 8 (n + 1) + 4 n + 16400 + 24 m + 8 nnz bytes -- and the scan's scratch.
+ *   errors    LZX_ERR_ARG: null handle.  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded
+ *             hand-over.  LZX_ERR_NOMEM: the message states the bytes.  LZX_ERR_LIMIT: 2^32 - 1 edges or more; more than m + 1
+ *             rounds (cannot happen on a symmetric matrix).  The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted graphs; no triangle listing, no truss hierarchy (connected components of
+ *             each k-truss).  A matrix that is not symmetric is not detected: its numbers mean nothing, but the call returns,
+ *             stays within its memory and leaves the handle answering -- the mark is taken by a compare-and-swap, so no edge is
+ *             queued twice even where a counter wraps. */
+typedef struct lzx_truss_info {
+    uint64_t edges;            /* m: undirected edges that are not self loops */
+    uint64_t triangles;        /* T = sum of the supports / 3 */
+    uint64_t main_truss_edges; /* edges whose truss number is max_truss */
+    uint32_t max_support, max_truss;
+    uint32_t levels;           /* distinct truss numbers that occur */
+    uint32_t rounds;           /* peeling rounds = the largest layer */
+    double   loop_ms, support_ms, peel_ms;  /* host clock of the call; device event time up to the end of the support count / of the peeling loop */
+} lzx_truss_info;
+int lzx_truss(lzx_handle h, uint32_t *support /* [nnz] or NULL */, uint32_t *truss /* [nnz] or NULL */,
+              uint32_t *layer /* [nnz] or NULL */, uint32_t *vertex_truss /* [n] or NULL */,
+              lzx_truss_info *info /* or NULL */);
 
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the

@@ -24,7 +24,8 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 # paths the product contains (what large graphs get by themselves), so tests that force them still run liblzx.so
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
-                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes")
+                 "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
+                 "truss_long_row", "truss_state_bytes")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -131,6 +132,15 @@ class LzxCoreInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
 
 
+class LzxTrussInfo(ctypes.Structure):
+    _fields_ = [("edges", ctypes.c_uint64), ("triangles", ctypes.c_uint64), ("main_truss_edges", ctypes.c_uint64),
+                ("max_support", ctypes.c_uint32), ("max_truss", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("support_ms", ctypes.c_double), ("peel_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -195,6 +205,7 @@ SYMBOLS = [
     ("lzx_betweenness_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _f64p, ctypes.POINTER(LzxBfsInfo)]),
     ("lzx_triangles", ctypes.c_int, [_h, _u64p, _f64p, ctypes.POINTER(LzxTrianglesInfo)]),
     ("lzx_core_numbers", ctypes.c_int, [_h, _u32p, _u32p, ctypes.POINTER(LzxCoreInfo)]),
+    ("lzx_truss", ctypes.c_int, [_h, _u32p, _u32p, _u32p, _u32p, ctypes.POINTER(LzxTrussInfo)]),
 ]
 
 _LIB = None
@@ -1071,6 +1082,72 @@ class Engine:
         if not keep.any():
             raise ValueError(f"k_shell: no vertex of this graph has core number {k} (the degeneracy is {top})")
         return self.induced(keep, **options)
+
+    # ---- edge support and truss numbers (include/lzx.h: lzx_truss) ----
+    def truss_raw(self, want_support: bool = True, want_truss: bool = True, want_layer: bool = True, want_vertex: bool = True):
+        """(support, truss, layer, vertex_truss, info) of lzx_truss.  support, truss and layer are uint32 arrays with one value per
+        stored entry of get_graph_csr()'s col_idx (both copies of an edge carry its number; a diagonal entry carries 0):
+        the triangles through the edge, the largest k such that the edge lies in networkx.k_truss(G, k), and the peeling round,
+        from 1, in which it is removed.  vertex_truss[v] (uint32, the caller's order) is the largest truss number among v's
+        edges.  Each is None when not wanted, and then it does not leave the device.  info = the lzx_truss_info fields (edges,
+        triangles, main_truss_edges, max_support, max_truss, levels, rounds, loop_ms, support_ms, peel_ms).  Self loops are
+        ignored."""
+        nnz = int(self.info()["nnz"]) if (want_support or want_truss or want_layer) else 0
+        outs = [np.zeros(max(nnz, 1), dtype=np.uint32) if want else None for want in (want_support, want_truss, want_layer)]
+        vertex = np.zeros(max(self.n, 1), dtype=np.uint32) if want_vertex else None
+        info = LzxTrussInfo()
+        _check(self.L.lzx_truss(self.h, *[None if o is None else _p(o, _u32p) for o in outs], None if vertex is None else _p(vertex, _u32p),
+                                ctypes.byref(info)), "lzx_truss", self.L)
+        support, truss, layer = [None if o is None else o[:nnz] for o in outs]
+        return support, truss, layer, None if vertex is None else vertex[:self.n], info.as_dict()
+
+    def _edge_matrix(self, values):
+        import scipy.sparse as sp
+        rp, ci = self.get_graph_csr()
+        return sp.csr_matrix((values, ci.astype(np.int64), rp.astype(np.int64)), shape=(self.n, self.n))
+
+    def edge_support(self):
+        """The triangles through every edge: a scipy CSR matrix (uint32) over the handle's pattern, symmetric; a diagonal entry
+        holds 0."""
+        return self._edge_matrix(self.truss_raw(want_truss=False, want_layer=False, want_vertex=False)[0])
+
+    def truss_number(self):
+        """The truss number of every edge -- the largest k such that the edge lies in networkx.k_truss(G, k), at least 2: a scipy
+        CSR matrix (uint32) over the handle's pattern, symmetric; a diagonal entry holds 0."""
+        return self._edge_matrix(self.truss_raw(want_support=False, want_layer=False, want_vertex=False)[1])
+
+    def max_truss(self):
+        """The largest truss number (0 for a graph without an edge).  No vector leaves the device."""
+        return int(self.truss_raw(False, False, False, False)[4]["max_truss"])
+
+    def k_truss(self, k=None, **options):
+        """networkx.k_truss: (engine on the k-truss, old_of_new) -- the edges of truss number >= k and the vertices that keep at
+        least one of them, renumbered in ascending old id; k=None selects the main truss (k = max_truss()).  A truss is not a
+        vertex-induced subgraph (an edge between two of its vertices may be missing from it), so unlike k_core this path is not
+        built on the device: the truss numbers come back per entry, the CSR is filtered on the host and handed to a new Engine
+        (this one's GPU; `options` as for Engine()) with set_graph_csr.  Self loops are dropped."""
+        _, truss, _, _, info = self.truss_raw(want_support=False, want_layer=False, want_vertex=False)
+        top = int(info["max_truss"])
+        k = top if k is None else int(k)
+        if top == 0:
+            raise ValueError("k_truss: this graph has no edge")
+        if k > top:
+            raise ValueError(f"k_truss: k = {k} is above the largest truss number {top} of this graph: the {k}-truss is empty")
+        rp, ci = self.get_graph_csr()
+        keep = truss >= max(k, 2)
+        rows = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(rp.astype(np.int64)))[keep]
+        counts = np.bincount(rows, minlength=self.n)
+        old = np.flatnonzero(counts).astype(np.uint32)
+        new_of_old = np.zeros(self.n, dtype=np.uint32)
+        new_of_old[old] = np.arange(len(old), dtype=np.uint32)
+        sub_rp = np.concatenate([[0], np.cumsum(counts[old])]).astype(np.uint64)
+        sub = Engine(self.device, **options)
+        try:
+            sub.set_graph_csr(sub_rp, new_of_old[ci[keep]])
+        except Exception:
+            sub.close()
+            raise
+        return sub, old
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

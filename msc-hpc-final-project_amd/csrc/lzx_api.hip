@@ -167,6 +167,10 @@ static const Option g_options[] = {
     // a state of more than this many bytes is out of device memory
     {"core_long_row", &lzx_ctx::core_long_opt, OPT_SHAPE},
     {"core_state_bytes", &lzx_ctx::core_cap_opt, OPT_SHAPE},
+    // lzx_truss: edges of the frontier whose shorter row has more than this many entries take the long-row launch (default 64 times the
+    // lanes per edge); a state of more than this many bytes is out of device memory
+    {"truss_long_row", &lzx_ctx::truss_long_opt, OPT_SHAPE},
+    {"truss_state_bytes", &lzx_ctx::truss_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

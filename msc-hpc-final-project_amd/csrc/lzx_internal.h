@@ -365,6 +365,8 @@ struct lzx_ctx {
     int64_t tri_long_opt = -1;         // test shape tri_long_list: out-entries beyond which lzx_triangles gives a row to its wide kernel (<= 0: LZX_TRI_LONG)
     int64_t tri_cap_opt = -1;          // test shape tri_state_bytes: lzx_triangles treats a state larger than this as out of device memory
     int64_t core_long_opt = -1;        // test shape core_long_row: entries beyond which lzx_core_numbers gives a row of the frontier to its long-row launch (<= 0: 64 lanes-per-row)
+    int64_t truss_long_opt = -1;       // test shape truss_long_row: entries of the shorter row beyond which lzx_truss gives an edge of the frontier to its long-row launch (<= 0: 64 lanes-per-edge)
+    int64_t truss_cap_opt = -1;        // test shape truss_state_bytes: lzx_truss treats a state larger than this as out of device memory
     int64_t core_cap_opt = -1;         // test shape core_state_bytes: lzx_core_numbers treats a state larger than this as out of device memory
 };
 

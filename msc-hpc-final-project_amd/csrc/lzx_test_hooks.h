@@ -22,7 +22,10 @@
 // takes a state larger than this many bytes as out of device memory), "core_long_row" (lzx_core_numbers: a row of the frontier with more than
 // this many entries is peeled by the long-row launch, a workgroup per row and slice of its entries; default 64 times the lanes per row,
 // 256 to 2048 from the mean degree), "core_state_bytes" (lzx_core_numbers takes a state larger than this many bytes as out of device
-// memory, before the device is touched).
+// memory, before the device is touched), "truss_long_row" (lzx_truss: an edge of the frontier whose shorter row has more than this many
+// entries is peeled by the long-row launch, a workgroup per edge and slice of that row; default 64 times the lanes per edge, 256 to 2048
+// from the mean degree; its wide support kernel splits at "tri_long_list"), "truss_state_bytes" (lzx_truss takes a state larger than this
+// many bytes as out of device memory, at either of its two allocations).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
