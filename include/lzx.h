@@ -310,6 +310,8 @@ int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, double *out);
  *             state are left alone; the eigensolver's basis is freed before the call returns.
  *   breakdown beta_j <= 2^-40 * g (g = d_max under A, 2 d_max under L) ends a cycle early: its Ritz pairs are exact, and the
  *             next cycle starts from a fresh probe (seed, index 1 + earlier breakdowns) orthogonalised against the basis.
+ *             A breakdown at which W and the cycle's columns span all of R^n (m + nw == n) leaves nothing to explore: the
+ *             call ends there with the exact pairs.
  *   repeated  a single-vector Krylov method finds one vector per eigenspace from one start vector: further copies of a
  *             repeated eigenvalue appear only through rounding or a breakdown restart.  W is the tool for getting them.
  *   determinism: the same graph, options and arguments give bit-identical evals, evecs, resid and counts.

@@ -234,6 +234,8 @@ def _load(path: str, mode: int) -> ctypes.CDLL:
     L.lzx_test_rank_row_sums.argtypes = [_h, _f64p, _u32p, _u64p]
     L.lzx_test_sym_eig.restype = ctypes.c_int          # the eigensolver's dense solver (csrc/lzx_test_hooks.h)
     L.lzx_test_sym_eig.argtypes = [ctypes.c_uint32, _f64p, _f64p, _f64p]
+    L.lzx_test_eig_ops.restype = ctypes.c_int          # the eigensolver's dense device kernels on a caller's basis
+    L.lzx_test_eig_ops.argtypes = [_h, ctypes.c_uint32, ctypes.c_uint32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
     return L
 
 
@@ -389,6 +391,22 @@ class Engine:
         ids = np.empty(gi["rows_local"], dtype=np.int64)
         ids[pos[mine].astype(np.int64) - lo] = mine
         return v[:gi["rows_local"]], ids
+
+    def eig_ops(self, Q, w, Y=None):
+        """test hook lzx_test_eig_ops: the eigensolver's Gram-Schmidt launches on the columns of Q (n, J) and w (n,), and with
+        Y (J, p) its restart rotation.  Returns (coef (J,) = h1 + h2, w_out (n,) unit, beta, R (p, n) = (Q Y)^T or None)."""
+        Qt = np.ascontiguousarray(np.asarray(Q, dtype=np.float64).T)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        J, n = Qt.shape
+        assert n == self.n and w.shape == (n,)
+        Yc = None if Y is None else np.ascontiguousarray(Y, dtype=np.float64)
+        assert Yc is None or (Yc.ndim == 2 and Yc.shape[0] == J)
+        p = 1 if Yc is None else Yc.shape[1]
+        coef, w_out, beta = np.zeros(J), np.zeros(n), ctypes.c_double()
+        R = None if Yc is None else np.zeros((p, n))
+        _check(self.L.lzx_test_eig_ops(self.h, J, p, _p(Qt, _f64p), _p(w, _f64p), None if Yc is None else _p(Yc, _f64p), _p(coef, _f64p),
+                                       _p(w_out, _f64p), ctypes.byref(beta), None if R is None else _p(R, _f64p)), "lzx_test_eig_ops", self.L)
+        return coef, w_out, float(beta.value), R
 
     def close(self):
         if self.h:

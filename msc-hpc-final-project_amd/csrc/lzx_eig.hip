@@ -20,7 +20,8 @@
 // (sym_eig below), the p wanted-most Ritz vectors are formed in place by k_eig_rotate (Q[:, 0:p] <- Q[:, 0:m] Y), q_m moves
 // to column p, and H restarts as diag(theta) with the coupling beta_{m-1} Y[m-1, i] in row p; the device's own projection
 // coefficients of step p supply the matching column.  A breakdown (beta_j <= 2^-40 * the Gershgorin bound) ends the cycle
-// early: its Ritz pairs are exact, and the next cycle starts from a fresh probe orthogonalised against what is kept.
+// early: its Ritz pairs are exact, and the next cycle starts from a fresh probe orthogonalised against what is kept -- unless
+// W and the cycle's columns already span R^n (m + nw == n), where the run ends.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -348,6 +349,31 @@ struct EigRun {
         if (lap) LZX_TRY(lzx_launch_lap_apply(c, c->d_v, x, nullptr, 0, c->n_loc_pad));
         return LZX_OK;
     }
+    // the basis of nw + m + 1 columns and the scratch behind it, both zeroed (c, nw, m set by the caller): the padding rows
+    // and tails of the basis stay 0 from here on
+    int alloc(const char *fn)
+    {
+        const u64 basis_bytes = (u64)(nw + m + 1) * c->ldq * sizeof(double);
+        char what[64];
+        std::snprintf(what, sizeof what, "the basis of (nw + m + 1) = %u columns", nw + m + 1);
+        LZX_TRY(lzx_alloc_state(fn, what, c->eig_basis_cap_opt, basis_bytes, basis_bytes, (void **)&d_B));
+        G = lzx_cgs_grid(c);
+        const u32 Jmax = nw + m + 1;
+        const u64 scratch = (u64)Jmax * G + 2ull * Jmax + (u64)m * m + m + G + (u64)m * ldy() + 16;
+        LZX_HIP(hipMalloc(reinterpret_cast<void **>(&d_s), sizeof(double) * scratch));
+        part = d_s;
+        h1 = part + (size_t)Jmax * G;
+        h2 = h1 + Jmax;
+        H = h2 + Jmax;
+        beta = H + (size_t)m * m;
+        npart = beta + m;
+        Y = npart + G;
+        tmp = Y + (size_t)m * ldy();
+        LZX_HIP(hipMemsetAsync(d_B, 0, basis_bytes, c->stream));
+        LZX_HIP(hipMemsetAsync(d_s, 0, sizeof(double) * scratch, c->stream));
+        return LZX_OK;
+    }
+    u32 ldy() const { return (m + LZX_EIG_CT - 1) / LZX_EIG_CT * LZX_EIG_CT; }   // row stride of Y
     LzxCgsScratch scratch() const { return LzxCgsScratch{G, part, h1, h2, npart}; }
     // w orthogonalised against columns [0, J) by CGS2, the norm partials of the result in npart; hsum: column of H
     int orth(double *w, u32 J, double *hsum) { return lzx_cgs2(c, d_B, J, w, scratch(), hsum, nw); }
@@ -438,29 +464,13 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
     // its alpha / beta and the batch state are not touched)
     c->k_prep = 0;
 
-    const u64 basis_bytes = (u64)(nw + m + 1) * c->ldq * sizeof(double);
-    char what[64];
-    std::snprintf(what, sizeof what, "the basis of (nw + m + 1) = %u columns", nw + m + 1);
-    LZX_TRY(lzx_alloc_state(fn, what, c->eig_basis_cap_opt, basis_bytes, basis_bytes, (void **)&r.d_B));
-    r.G = lzx_cgs_grid(c);
-    const u32 Jmax = nw + m + 1, ldy = (m + LZX_EIG_CT - 1) / LZX_EIG_CT * LZX_EIG_CT;
-    const u64 scratch = (u64)Jmax * r.G + 2ull * Jmax + (u64)m * m + m + r.G + (u64)m * ldy + 16;
-    LZX_HIP(hipMalloc(reinterpret_cast<void **>(&r.d_s), sizeof(double) * scratch));
-    r.part = r.d_s;
-    r.h1 = r.part + (size_t)Jmax * r.G;
-    r.h2 = r.h1 + Jmax;
-    r.H = r.h2 + Jmax;
-    r.beta = r.H + (size_t)m * m;
-    r.npart = r.beta + m;
-    r.Y = r.npart + r.G;
-    r.tmp = r.Y + (size_t)m * ldy;
+    LZX_TRY(r.alloc(fn));
+    const u32 ldy = r.ldy();
     for (u32 i = 0; i < 2 * m + 1; ++i) {
         hipEvent_t ev;
         LZX_HIP(hipEventCreate(&ev));
         r.ev.push_back(ev);
     }
-    LZX_HIP(hipMemsetAsync(r.d_B, 0, basis_bytes, c->stream));   // padding rows and tails stay 0 from here on
-    LZX_HIP(hipMemsetAsync(r.d_s, 0, sizeof(double) * scratch, c->stream));
 
     // deflation vectors: uploaded, orthonormalised in order on the device
     for (u32 t = 0; t < nw; ++t) {
@@ -529,6 +539,9 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
             if (res[i] <= tol * norm_est) ++conv;
         }
         const bool done = !brk && conv >= nev;
+        // a breakdown with W and the cycle's columns spanning all of R^n (m + nw == n at the latest): the Ritz pairs are every
+        // eigenpair of the complement of W, and a fresh probe could only break down again
+        if (brk && (u64)me + nw >= n) exhausted = true;
         if (done || restarts >= max_restarts || exhausted) {
             host_ms += lzx_ms_since(th0);
             break;
@@ -608,5 +621,58 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
     if (conv < nev)
         LZX_FAIL(LZX_ERR_LIMIT, "%s: %u of %u pairs converged after %u restarts (largest residual estimate %.3e, tolerance %.3e)", fn, conv, nev,
                  restarts, worst, tol * norm_est);
+    return LZX_OK;
+}
+
+// ==================================================================================================== test hook
+// (lzx_test_hooks.h) The dense launches above on a caller's basis: an EigRun with nw = 0 and m = J holds the J columns of Q and,
+// as its column J, w -- laid out, orthogonalised, scaled and rotated by the driver's own member functions.
+extern "C" int lzx_test_eig_ops(lzx_handle h, uint32_t J, uint32_t p, const double *Q, const double *w, const double *Y, double *coef,
+                                double *w_out, double *beta, double *R)
+{
+    static const char *fn = "lzx_test_eig_ops";
+    const u32 Jtop = LZX_EIG_MAX_W + LZX_EIG_MAX_M + 1;
+    if (J == 0 || J > Jtop) LZX_FAIL(LZX_ERR_ARG, "%s: J = %u columns (1 to %u)", fn, J, Jtop);
+    if (p == 0 || p > J) LZX_FAIL(LZX_ERR_ARG, "%s: p = %u output columns (1 to J = %u)", fn, p, J);
+    if (R && J > LZX_EIG_MAX_M) LZX_FAIL(LZX_ERR_ARG, "%s: the rotation takes at most %u columns (J = %u)", fn, LZX_EIG_MAX_M, J);
+    if (!Q) LZX_FAIL(LZX_ERR_ARG, "%s: null Q", fn);
+    if (!w) LZX_FAIL(LZX_ERR_ARG, "%s: null w", fn);
+    if (R && !Y) LZX_FAIL(LZX_ERR_ARG, "%s: R is wanted but Y is null", fn);
+    if (!h) LZX_FAIL(LZX_ERR_ARG, "%s: null handle (h)", fn);
+    lzx_ctx *c = h;
+    if (c->comm_kind != 0 || c->world > 1) LZX_FAIL(LZX_ERR_STATE, "%s: one GPU handle only", fn);
+    if (!c->d_row_ptr || !c->d_v) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
+    const u64 n = c->n;
+
+    EigRun r;
+    r.c = c;
+    r.nw = 0;
+    r.m = J;
+    LZX_HIP(hipSetDevice(c->device));
+    c->k_prep = 0;   // d_io is overwritten, as in lzx_eigsh_f64
+    LZX_TRY(r.alloc(fn));
+    for (u32 i = 0; i <= J; ++i) {
+        LZX_HIP(hipMemcpyAsync(c->d_io, i < J ? Q + (size_t)i * n : w, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        LZX_TRY(lzx_launch_permute_in(c, c->d_io, r.col(i), 1.0));
+    }
+    auto fetch = [&](u32 i, double *out) -> int {   // column i in the caller's order
+        LZX_TRY(lzx_launch_permute_out(c, r.col(i), c->d_io));
+        LZX_HIP(hipMemcpyAsync(out, c->d_io, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+        LZX_HIP(hipStreamSynchronize(c->stream));
+        return LZX_OK;
+    };
+    LZX_TRY(r.orth(r.col(J), J, r.H));
+    LZX_TRY(r.scale(r.col(J), r.col(J), r.beta, 0.0));
+    if (coef) LZX_HIP(hipMemcpyAsync(coef, r.H, sizeof(double) * J, hipMemcpyDeviceToHost, c->stream));
+    if (beta) LZX_HIP(hipMemcpyAsync(beta, r.beta, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LZX_HIP(hipStreamSynchronize(c->stream));
+    if (w_out) LZX_TRY(fetch(J, w_out));
+    if (R) {
+        const u32 ldy = r.ldy();
+        std::vector<double> Yh((size_t)J * ldy, 0.0);
+        for (u32 a = 0; a < J; ++a) std::copy(Y + (size_t)a * p, Y + (size_t)(a + 1) * p, Yh.begin() + (size_t)a * ldy);
+        LZX_TRY(r.rotate(0, J, Yh, ldy, p));
+        for (u32 i = 0; i < p; ++i) LZX_TRY(fetch(i, R + (size_t)i * n));
+    }
     return LZX_OK;
 }

@@ -63,3 +63,16 @@ int lzx_test_allreduce_latency(lzx_handle h, uint32_t reps, double *us_each);
 extern "C"
 #endif
 int lzx_test_sym_eig(uint32_t n, const double *A, double *w, double *V);
+// The eigensolver's dense device kernels on a caller's basis (lzx_eig.hip), through the launches lzx_eigsh_f64 itself uses.  The
+// handle holds a graph (n vertices; its layout is the basis's: stride ldq, padding rows 0); 1 <= J <= 137, 1 <= p <= J, and
+// J <= 128 when R is wanted.  Q: J columns of n doubles, w: n doubles, both in the caller's vertex order.  First the
+// Gram-Schmidt of one Lanczos step: w orthogonalised twice against the J columns (k_eig_proj, k_eig_close, k_eig_update) and
+// made unit (k_eig_scale): coef[c] = h1[c] + h2[c], what the solver stores as its column of H; *beta = the norm of what is
+// left of w; w_out = that divided by beta.  Then, with R, the restart's rotation (k_eig_rotate, in place, Y padded to rows of
+// a multiple of 8 as the driver pads it): R[i] = column i of Q Y for i < p, Y being J rows of p doubles.  coef, w_out, beta
+// and R may each be null.  Argument errors come back before the device is touched; voids a prepared decomposition.
+#ifdef __cplusplus
+extern "C"
+#endif
+int lzx_test_eig_ops(lzx_handle h, uint32_t J, uint32_t p, const double *Q, const double *w, const double *Y, double *coef,
+                     double *w_out, double *beta, double *R);

@@ -43,6 +43,31 @@ def test_argument_errors_without_gpu(pkg):
         assert "lzx_eigsh_f64" in msg and word in msg, (kw, msg)
 
 
+def test_eig_ops_hook_argument_errors_without_gpu(pkg):
+    """test hook lzx_test_eig_ops (csrc/lzx_test_hooks.h): every argument error comes back before a device is touched"""
+    L = pkg.lib()
+    buf = np.zeros(137 * 4)
+    P = buf.ctypes.data_as(_f64p)
+
+    def call(J=4, p=2, Q=P, w=P, Y=P, R=P, h=None):
+        return L.lzx_test_eig_ops(h, J, p, Q, w, Y, P, P, P, R)
+
+    cases = [(dict(J=0), "J = 0"),
+             (dict(J=138, p=1, R=None), "J = 138"),
+             (dict(p=0), "p = 0"),
+             (dict(J=4, p=5), "p = 5"),
+             (dict(J=129, p=1), "at most 128"),               # the rotation stages J columns in 64 KiB of LDS
+             (dict(Q=None), "null Q"),
+             (dict(w=None), "null w"),
+             (dict(Y=None), "Y is null"),
+             (dict(), "null handle"),
+             (dict(J=137, p=1, Y=None, R=None), "null handle")]   # the largest Gram-Schmidt shape: refused for the handle alone
+    for kw, word in cases:
+        assert call(**kw) == LZX_ERR_ARG, kw
+        msg = L.lzx_last_error().decode()
+        assert "lzx_test_eig_ops" in msg and word in msg, (kw, msg)
+
+
 def _sym_eig(L, A):
     n = A.shape[0]
     A = np.ascontiguousarray(A, dtype=np.float64)
