@@ -758,6 +758,146 @@ int lzx_truss(lzx_handle h, uint32_t *support /* [nnz] or NULL */, uint32_t *tru
               uint32_t *layer /* [nnz] or NULL */, uint32_t *vertex_truss /* [n] or NULL */,
               lzx_truss_info *info /* or NULL */);
 
+/* ---- greedy colouring, label-propagation communities, modularity ----------------------------------------
+ * Three calls on the handle's graph read as undirected and unweighted, each useful alone: a proper vertex colouring
+ * (networkx.coloring.greedy_color), the communities of semi-synchronous label propagation over its colour classes
+ * (networkx.community.label_propagation_communities) and Newman's modularity of any labelling (networkx.community.modularity).
+ * In all three d_v = the number of stored entries of row v NOT counting a diagonal entry, and a diagonal entry (self loop) is
+ * ignored everywhere.
+ *
+ * lzx_color
+ *   outputs   The vertices are put in one total order: v comes before u iff d_v > d_u, or the degrees are equal and
+ *             hash(v) < hash(u), or both are equal and v < u.  hash(v) is the probe hash above with p = 0:
+ *             key = seed + 0x9E3779B97F4A7C15 * (v + 1), then the three xor-shift-multiply steps, mod 2^64.  With
+ *             LZX_COLOR_TIES_BY_ID in flags the hash is left out: (d descending, id ascending).  color[v] = the smallest colour
+ *             that no neighbour EARLIER in the order has: exactly sequential greedy colouring in that order, and with the flag
+ *             networkx's default strategy largest_first on nodes 0 .. n-1.  An isolated vertex gets colour 0.  color may be NULL,
+ *             and then no n-vector crosses PCIe.
+ *   info      (or NULL) colors = the colours used (the largest + 1); rounds = the windows of the method below = the longest chain
+ *             v_1, v_2, ... of vertices each adjacent to and earlier than the next, which makes it canonical; largest_class = the
+ *             vertices of the most frequent colour; the host clock of the call and the device event time of the colouring (the
+ *             host's reads included).
+ *   method    Jones-Plassmann in push form, lzx_core_numbers' structure.  State, u32 [n] each: d, wait, colour, queue.  wait[v] =
+ *             the number of earlier neighbours of v, counted over the row by an init launch; the vertices with wait = 0 are
+ *             appended to the queue: window 1.  A round handles its window: (1) every window vertex takes the minimum excluded
+ *             colour over its earlier neighbours, all coloured by earlier launches; (2) for every later neighbour u,
+ *             old = atomicSub(&wait[u], 1), and the one lane that sees old == 1 appends u (aggregated per wavefront), so u is
+ *             coloured by the next launch and sees v's colour.  A group of lanes per row (4 to 32, from the mean degree) builds a
+ *             64-colour window mask across the group and, while the mask is full, moves the window up by 64 and walks the row
+ *             again: at most len / 64 + 1 walks.  Rows of more than 64 times that many entries go to a second launch, a
+ *             workgroup per row with an LDS bitmap.  An earlier neighbour has degree >= d_v, so a vertex has fewer than 2^16
+ *             earlier neighbours while nnz < 2^32: COLOURS ARE BELOW 2^16, and the bitmap's 8 KiB always suffice.  The host reads
+ *             two words per round (the queue's end, the colours) and stops when n vertices are queued.  All atomics are 32-bit
+ *             INTEGER vector atomics; no kernel waits on another workgroup; every device loop is bounded by a row length or a
+ *             window length; every append is clamped to n.
+ *             Ties by id can need n rounds -- a path numbered end to end does, and a ring around a star of 1 500 vertices takes
+ *             1 500 rounds by id and 8 hashed -- so hashed ties are the default everywhere else.
+ *   bits      color and every integer of info are canonical: any correct implementation of the definition gives them.
+ *   state     the call touches none of the handle's.  Everything it allocates (16 n + 12 min(n, 65536) + 64 bytes, n rounded up to
+ *             even) is freed before it returns, on every path.
+ *   errors    LZX_ERR_ARG: null handle, a flag bit other than LZX_COLOR_TIES_BY_ID.  LZX_ERR_STATE: no graph, a handle with a
+ *             communicator, a graph from a sharded hand-over.  LZX_ERR_NOMEM: the message states the bytes.  LZX_ERR_LIMIT: more
+ *             than n + 1 rounds, or vertices that still wait when a window comes back empty (only on a matrix that is not
+ *             symmetric).  The checks that need no device come first.
+ *   limits    colours below 2^16, which holds while nnz < 2^32 (see method); n rounds at the worst, which ties by id reach; and
+ *             the limits common to the three calls, below.
+ *
+ * lzx_label_propagation
+ *   outputs   Colour as lzx_color(seed, flags) does, and start from label[v] = v.  A sweep visits the colour classes in
+ *             ascending colour; every vertex v of the class that has at least one neighbour u != v is updated, the whole class at
+ *             once, from the current labels: H = the labels of greatest multiplicity among v's neighbours; the new label is H's
+ *             only member when |H| = 1, the old label when that is in H, max(H) otherwise (Prec-Max, Cordasco and Gargano) --
+ *             equivalently the label that maximises (multiplicity, label == old, label).  The call is done after the first sweep
+ *             that changes no label, and that sweep is counted.  labels[v] = the SMALLEST VERTEX ID of v's community, caller
+ *             order; may be NULL.  With LZX_COLOR_TIES_BY_ID the communities are networkx's label_propagation_communities',
+ *             set for set (networkx visits the classes in the order colours first appear, which is ascending).
+ *   info      (or NULL) n_communities; largest_size and largest_label (ties go to the smallest label), formed on the device;
+ *             sweeps; updates = the label changes over all sweeps; colors and color_rounds of the colouring; inner_entries,
+ *             entries, sum_degree_sq and modularity of the result, as lzx_modularity gives them; the host clock of the call, the
+ *             device event times of the colouring with the class layout and of the sweeps (the host's reads included).
+ *   method    The classes are laid out once by a counting sort of (colour, path): histogram, scan (on the host: three words per
+ *             colour), fill; the order inside a class is no output.  A class is one launch per path that has rows (two for the longest rows), the path
+ *             chosen by the row's length.  Rows of at most 128 entries: a group of lanes per row stages the neighbours' labels in
+ *             its LDS slice, every lane counts the equal labels for its own entries, and the packed key
+ *             count << 33 | (label == old) << 32 | label is max-reduced over the group.  Rows of at most 2 048: a workgroup per row
+ *             and an open-addressing table in LDS (4 096 slots of a u32 key and a u32 count, 32 KiB, which leaves five workgroups to a
+ *             compute unit): atomicCAS on the key slot, atomicAdd on the count, linear probing bounded by the slot count, never
+ *             more than half full, then the maximum of the same key over the slots.  Longer rows: the same insertion into a table of
+ *             pow2ceil(2 len) slots in global memory, at an offset from a scan over the long rows made once per call, by up to 64
+ *             workgroups that share the row's entries; a second launch, the workgroup that owns the table, takes the maximum and
+ *             clears the slots it read (the tables are zeroed once per call).  In both tables the lanes of a wavefront whose
+ *             labels agree with its first lane's, and then with the first of the rest, are inserted as one: late in a run most
+ *             neighbours of a hub carry one label.  Labels are updated in place: the vertices of a class share no edge.  Changed labels are
+ *             counted per wavefront into one word and the host reads one word per sweep.  The canonical labels are a 32-bit
+ *             atomicMin per vertex into a map, then a gather.  32-bit INTEGER vector atomics only, in LDS and in global memory,
+ *             and no floating point, up to the statistics (one 64-bit atomicMax) and the modularity pass; no kernel waits on
+ *             another workgroup; every loop is bounded by a row length, a table size or the sweep cap.
+ *   bits      labels and every integer of info are canonical: the new label is an arg-max under a total order, so it depends
+ *             neither on the path a row takes nor on any thread order.  modularity: see lzx_modularity.
+ *   state     the call touches none of the handle's.  Everything it allocates is freed before it returns, on every path:
+ *             16 n + 20 n' + 12 min(n, 65536) + 64 bytes for the vertices (n' = n rounded up to even, the third term rounded up to 8) and
+ *             8 pow2ceil(2 len) bytes for every row of more than 2 048 entries.
+ *   errors    as lzx_color, and LZX_ERR_ARG: max_sweeps == 0.  LZX_ERR_LIMIT: max_sweeps sweeps have run and the last one changed
+ *             a label -- labels and info ARE written, with the state after that sweep; a row of 2^30 entries or more.
+ *   limits    rows below 2^30 entries; one launch per colour class and path in every sweep, several hundred launches per sweep on
+ *             an R-MAT graph (merging the thin classes' launches is not done); and the common limits below.
+ *
+ * lzx_modularity
+ *   outputs   *q = Newman's modularity at resolution 1 of the labelling labels[v] < n (any labelling; label values need not be
+ *             members of their community).  D_c = the sum of d_v over the community, I_c = the stored off-diagonal entries with
+ *             both ends in c (twice the inner edges), M = the sum of the D_c (twice the edges):
+ *             q = the sum over the labels that occur, ascending, of (double)I_c / (double)M - ((double)D_c / (double)M)^2,
+ *             formed in that order in fp64 without contraction; q = 0 on a graph without an edge.
+ *   info      (or NULL) communities = the distinct labels; inner_entries = the sum of the I_c; entries = M; sum_degree_sq = the sum
+ *             of the D_c^2 mod 2^64 (exact while M < 2^32); the host clock of the call.
+ *   method    The integers are formed on the device: one launch counts, per row, the neighbours with the row's label (a group of
+ *             lanes per row, long rows a workgroup each); one launch adds d_v and that count to u64 [n] accumulators with 64-bit
+ *             integer atomics, one add per row at the most, the lanes of a wavefront whose labels agree combined first (one
+ *             community can hold most of the graph).  The accumulators cross PCIe (16 n bytes) and the host adds the terms.
+ *   bits      every integer is canonical, and q is bit-identical to the same loop in Python floats; it is within
+ *             (C + 4) 2^-52 of networkx.community.modularity, C the number of communities: every term lies in [-1, 1] and carries
+ *             at most four roundings.
+ *   state     the call touches none of the handle's; 28 n + 64 bytes (n rounded up to even in the u32 arrays), freed on every path.
+ *   errors    LZX_ERR_ARG: null handle, null labels or q, a label >= n (the message names its index and value).  LZX_ERR_STATE,
+ *             LZX_ERR_NOMEM: as above.  The labels are checked before the device is touched.
+ *   limits    resolution 1 only; the accumulators cross PCIe, 16 n bytes per call; and the common limits below.
+ *
+ *   limits    (all three) one GPU handle; undirected, unweighted graphs; no Louvain or Leiden, which need the weighted
+ *             aggregation a pattern-only CSR does not have; no asynchronous or seeded-random label propagation.  A matrix that is
+ *             not symmetric is not detected: its numbers mean nothing, but the calls return and stay within their memory --
+ *             appends are clamped, rounds and sweeps are capped, every label is a vertex id. */
+#define LZX_COLOR_TIES_BY_ID 1u
+typedef struct lzx_color_info {
+    uint32_t colors;         /* colours used */
+    uint32_t rounds;         /* windows = the longest chain of the order */
+    uint32_t largest_class;  /* vertices of the most frequent colour */
+    uint32_t reserved_;
+    double   loop_ms, color_ms;  /* host clock of the call; device event time of the colouring */
+} lzx_color_info;
+int lzx_color(lzx_handle h, uint64_t seed, uint32_t flags, uint32_t *color /* [n] or NULL */, lzx_color_info *info /* or NULL */);
+
+typedef struct lzx_communities_info {
+    uint64_t n_communities, largest_size;
+    uint64_t updates;        /* label changes over all sweeps */
+    uint64_t inner_entries, entries, sum_degree_sq;  /* lzx_modularity's integers of the result */
+    uint32_t largest_label;  /* of the largest community; ties go to the smallest label */
+    uint32_t sweeps;         /* the last one changed nothing, unless LZX_ERR_LIMIT */
+    uint32_t colors, color_rounds;
+    double   modularity;
+    double   loop_ms, color_ms, sweep_ms;  /* host clock of the call; device event time of the colouring / of the sweeps */
+} lzx_communities_info;
+int lzx_label_propagation(lzx_handle h, uint64_t seed, uint32_t flags, uint32_t max_sweeps, uint32_t *labels /* [n] or NULL */,
+                          lzx_communities_info *info /* or NULL */);
+
+typedef struct lzx_modularity_info {
+    uint64_t communities;    /* distinct labels */
+    uint64_t inner_entries;  /* sum of I_c */
+    uint64_t entries;        /* M = sum of D_c */
+    uint64_t sum_degree_sq;  /* sum of D_c^2 mod 2^64 */
+    double   loop_ms;
+} lzx_modularity_info;
+int lzx_modularity(lzx_handle h, const uint32_t *labels /* [n], values < n */, double *q, lzx_modularity_info *info /* or NULL */);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

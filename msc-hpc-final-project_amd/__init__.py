@@ -25,7 +25,9 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
                  "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
-                 "truss_long_row", "truss_state_bytes")
+                 "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes")
+
+LZX_COLOR_TIES_BY_ID = 1   # include/lzx.h: the colouring's order without the hash, (degree descending, id ascending)
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -141,6 +143,32 @@ class LzxTrussInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxColorInfo(ctypes.Structure):
+    _fields_ = [("colors", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("largest_class", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("color_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
+
+
+class LzxCommunitiesInfo(ctypes.Structure):
+    _fields_ = [("n_communities", ctypes.c_uint64), ("largest_size", ctypes.c_uint64), ("updates", ctypes.c_uint64),
+                ("inner_entries", ctypes.c_uint64), ("entries", ctypes.c_uint64), ("sum_degree_sq", ctypes.c_uint64),
+                ("largest_label", ctypes.c_uint32), ("sweeps", ctypes.c_uint32), ("colors", ctypes.c_uint32), ("color_rounds", ctypes.c_uint32),
+                ("modularity", ctypes.c_double), ("loop_ms", ctypes.c_double), ("color_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LzxModularityInfo(ctypes.Structure):
+    _fields_ = [("communities", ctypes.c_uint64), ("inner_entries", ctypes.c_uint64), ("entries", ctypes.c_uint64),
+                ("sum_degree_sq", ctypes.c_uint64), ("loop_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -206,6 +234,9 @@ SYMBOLS = [
     ("lzx_triangles", ctypes.c_int, [_h, _u64p, _f64p, ctypes.POINTER(LzxTrianglesInfo)]),
     ("lzx_core_numbers", ctypes.c_int, [_h, _u32p, _u32p, ctypes.POINTER(LzxCoreInfo)]),
     ("lzx_truss", ctypes.c_int, [_h, _u32p, _u32p, _u32p, _u32p, ctypes.POINTER(LzxTrussInfo)]),
+    ("lzx_color", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxColorInfo)]),
+    ("lzx_label_propagation", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxCommunitiesInfo)]),
+    ("lzx_modularity", ctypes.c_int, [_h, _u32p, _f64p, ctypes.POINTER(LzxModularityInfo)]),
 ]
 
 _LIB = None
@@ -1166,6 +1197,94 @@ class Engine:
             sub.close()
             raise
         return sub, old
+
+    # ---- colouring, label-propagation communities, modularity (include/lzx.h: lzx_color, lzx_label_propagation, lzx_modularity;
+    # DESIGN.md section 21) ----
+    def color_raw(self, seed: int = 0, ties_by_id: bool = False, want_colors: bool = True):
+        """(color, info) of lzx_color: color[v] = the colour of sequential greedy colouring in the order (degree descending, hash of
+        the id under `seed` ascending, id ascending) -- with ties_by_id the hash is left out and the colouring is
+        networkx.coloring.greedy_color(G)'s (uint32, the caller's order; None with want_colors=False, and then no n-vector leaves
+        the device); info = the lzx_color_info fields (colors, rounds, largest_class, loop_ms, color_ms).  Self loops are ignored.
+        Ties by id can take n rounds; the hashed order is the default for that reason."""
+        color = np.empty(self.n, dtype=np.uint32) if want_colors else None
+        info = LzxColorInfo()
+        _check(self.L.lzx_color(self.h, int(seed), LZX_COLOR_TIES_BY_ID if ties_by_id else 0, _p(color, _u32p) if want_colors else None,
+                                ctypes.byref(info)), "lzx_color", self.L)
+        return color, info.as_dict()
+
+    def greedy_color(self, seed: int = 0, ties_by_id: bool = False):
+        """networkx.coloring.greedy_color as a uint32 array in the caller's order (see color_raw)."""
+        return self.color_raw(seed, ties_by_id)[0]
+
+    def label_propagation_raw(self, seed: int = 0, ties_by_id: bool = False, max_sweeps: int = 1000, want_labels: bool = True):
+        """(labels, info) of lzx_label_propagation: semi-synchronous label propagation over the colour classes of
+        color_raw(seed, ties_by_id), Prec-Max ties; labels[v] = the smallest vertex id of v's community (uint32, the caller's order;
+        None with want_labels=False); info = the lzx_communities_info fields (n_communities, largest_size, largest_label, sweeps,
+        updates, colors, color_rounds, inner_entries, entries, sum_degree_sq, modularity, loop_ms, color_ms, sweep_ms).  With
+        ties_by_id the communities are networkx.community.label_propagation_communities(G)'s.  LzxError (-6) if max_sweeps
+        sweeps did not reach a fixed point."""
+        labels = np.empty(self.n, dtype=np.uint32) if want_labels else None
+        info = LzxCommunitiesInfo()
+        _check(self.L.lzx_label_propagation(self.h, int(seed), LZX_COLOR_TIES_BY_ID if ties_by_id else 0, int(max_sweeps),
+                                            _p(labels, _u32p) if want_labels else None, ctypes.byref(info)), "lzx_label_propagation", self.L)
+        return labels, info.as_dict()
+
+    def label_propagation_communities(self, seed: int = 0, ties_by_id: bool = False, max_sweeps: int = 1000):
+        """networkx.community.label_propagation_communities: a list of index arrays (int64, ascending), the largest community first
+        and communities of one size by their label (their smallest vertex)."""
+        labels = self.label_propagation_raw(seed, ties_by_id, max_sweeps)[0]
+        order = np.argsort(labels, kind="stable")
+        parts = np.split(order, np.flatnonzero(np.diff(labels[order])) + 1) if self.n else []
+        return sorted(parts, key=lambda part: (-len(part), int(part[0])))
+
+    def _labels_of(self, labels_or_communities, what):
+        if isinstance(labels_or_communities, np.ndarray) and labels_or_communities.ndim == 1 and len(labels_or_communities) == self.n:
+            labels = labels_or_communities
+        else:   # a list of vertex sets: every vertex in exactly one
+            labels = np.full(self.n, -1, dtype=np.int64)
+            for part in labels_or_communities:
+                part = np.asarray(sorted(part) if isinstance(part, (set, frozenset)) else part, dtype=np.int64)
+                if len(part) == 0:
+                    continue
+                if part.min() < 0 or part.max() >= self.n or (labels[part] != -1).any():
+                    raise ValueError(f"{what}: the communities must be disjoint sets of vertices 0 .. {self.n - 1}")
+                labels[part] = part.min()
+            if (labels < 0).any():
+                raise ValueError(f"{what}: vertex {int(np.flatnonzero(labels < 0)[0])} is in no community")
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError(f"{what}: labels must have shape ({self.n},), one per vertex, got {labels.shape}")
+        if len(labels) and (labels.min() < 0 or labels.max() > 0xffffffff):
+            raise ValueError(f"{what}: labels must be vertex ids 0 .. {self.n - 1}")
+        return np.ascontiguousarray(labels, dtype=np.uint32)
+
+    def modularity_raw(self, labels_or_communities):
+        """(q, info) of lzx_modularity: Newman's modularity at resolution 1 of a labelling (an array of n labels < n) or of a list
+        of disjoint vertex sets that cover the graph, as label_propagation_communities returns it; info = the lzx_modularity_info
+        fields (communities, inner_entries, entries, sum_degree_sq, loop_ms)."""
+        labels = self._labels_of(labels_or_communities, "modularity")
+        q = ctypes.c_double()
+        info = LzxModularityInfo()
+        _check(self.L.lzx_modularity(self.h, _p(labels, _u32p), ctypes.byref(q), ctypes.byref(info)), "lzx_modularity", self.L)
+        return q.value, info.as_dict()
+
+    def modularity(self, labels_or_communities):
+        """networkx.community.modularity(G, communities) as a float (see modularity_raw)."""
+        return self.modularity_raw(labels_or_communities)[0]
+
+    def community(self, labels, which=None, **options):
+        """induced(labels == which): (engine on one community, old_of_new), built on the device; which=None selects the largest
+        community, ties to the smallest label.  `options` as for induced()."""
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError(f"community: labels must have shape ({self.n},), one per vertex, got {labels.shape}")
+        if which is None:
+            values, counts = np.unique(labels, return_counts=True)
+            which = values[np.argmax(counts)]
+        keep = labels == which
+        if not keep.any():
+            raise ValueError(f"community: no vertex has the label {which}")
+        return self.induced(keep, **options)
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

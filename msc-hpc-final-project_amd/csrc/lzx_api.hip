@@ -171,6 +171,14 @@ static const Option g_options[] = {
     // lanes per edge); a state of more than this many bytes is out of device memory
     {"truss_long_row", &lzx_ctx::truss_long_opt, OPT_SHAPE},
     {"truss_state_bytes", &lzx_ctx::truss_cap_opt, OPT_SHAPE},
+    // lzx_color: rows with more than this many entries take the long-row launches (default 64 times the lanes per row).
+    // lzx_label_propagation: rows of at most lpa_group_row entries (default 128) are updated by a group of lanes, longer ones of at most
+    // lpa_table_row (default and at most half the slots of the LDS table) by a workgroup over that table, the rest over a table in global
+    // memory; a state of more than lpa_state_bytes is out of device memory
+    {"color_long_row", &lzx_ctx::color_long_opt, OPT_SHAPE},
+    {"lpa_group_row", &lzx_ctx::lpa_group_opt, OPT_SHAPE},
+    {"lpa_table_row", &lzx_ctx::lpa_table_opt, OPT_SHAPE},
+    {"lpa_state_bytes", &lzx_ctx::lpa_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

@@ -368,6 +368,10 @@ struct lzx_ctx {
     int64_t truss_long_opt = -1;       // test shape truss_long_row: entries of the shorter row beyond which lzx_truss gives an edge of the frontier to its long-row launch (<= 0: 64 lanes-per-edge)
     int64_t truss_cap_opt = -1;        // test shape truss_state_bytes: lzx_truss treats a state larger than this as out of device memory
     int64_t core_cap_opt = -1;         // test shape core_state_bytes: lzx_core_numbers treats a state larger than this as out of device memory
+    int64_t color_long_opt = -1;       // test shape color_long_row: entries beyond which lzx_color gives a row to its long-row launches (<= 0: 64 lanes-per-row)
+    int64_t lpa_group_opt = -1;        // test shape lpa_group_row: entries up to which lzx_label_propagation updates a row by a group of lanes (<= 0: 128)
+    int64_t lpa_table_opt = -1;        // test shape lpa_table_row: entries up to which it counts a longer row in the LDS table (<= 0 or above it: half its slots, 2048)
+    int64_t lpa_cap_opt = -1;          // test shape lpa_state_bytes: lzx_label_propagation treats a state larger than this as out of device memory
 };
 
 // ---- lzx_graph.hip ----

@@ -25,7 +25,13 @@
 // memory, before the device is touched), "truss_long_row" (lzx_truss: an edge of the frontier whose shorter row has more than this many
 // entries is peeled by the long-row launch, a workgroup per edge and slice of that row; default 64 times the lanes per edge, 256 to 2048
 // from the mean degree; its wide support kernel splits at "tri_long_list"), "truss_state_bytes" (lzx_truss takes a state larger than this
-// many bytes as out of device memory, at either of its two allocations).
+// many bytes as out of device memory, at either of its two allocations), "color_long_row" (lzx_color and the colouring of
+// lzx_label_propagation: a row with more than this many entries is counted and coloured by the long-row launches, a workgroup per row with
+// an LDS bitmap of colours; default 64 times the lanes per row), "lpa_group_row" (lzx_label_propagation: a row of at most this many entries
+// is updated by a group of lanes, which stages the first 128 labels in LDS and reads the rest of a longer row where it lies; default 128),
+// "lpa_table_row" (a longer row of at most this many entries is counted in the LDS table by a workgroup, the rest in a table in global
+// memory; default and at most 2048, half the LDS table's slots), "lpa_state_bytes" (lzx_label_propagation takes a state larger than this many
+// bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
