@@ -898,6 +898,75 @@ typedef struct lzx_modularity_info {
 } lzx_modularity_info;
 int lzx_modularity(lzx_handle h, const uint32_t *labels /* [n], values < n */, double *q, lzx_modularity_info *info /* or NULL */);
 
+/* ---- sweep cuts ----------------------------------------------------------------------------------------
+ * lzx_sweep_cut: what turns a score vector -- a Fiedler vector of lzx_eigsh_f64, a personalised lzx_pagerank_f64, a heat kernel
+ * e^(-tL) x -- into a set of vertices (Cheeger sweep; Andersen, Chung and Lang; Chung's heat-kernel PageRank): the vertices
+ * are ordered by score, cut(S_k) / min(vol S_k, vol of the rest) is evaluated for every prefix S_k of the order, and the best
+ * prefix is returned.  Up to 16 score vectors (columns) per call share one pass over the edges.  With an indicator score and
+ * k_min = k_max = |S| it gives networkx.cut_size, volume, conductance and edge_expansion of S.  The graph is read as undirected
+ * and unweighted; d_v = the number of stored entries of row v NOT counting a diagonal entry, M = the sum of the d_v, and a
+ * diagonal entry (self loop) changes no output.
+ *   inputs    scores: ns columns of n doubles, column c at scores + c * n, the caller's vertex order, host memory.
+ *   key       of vertex v in a column: s_v; with LZX_SWEEP_PER_DEGREE s_v / (double)d_v, one IEEE division, and a vertex with
+ *             d_v = 0 comes after all others whatever its score.  -0.0 counts as +0.0; +-inf are ordinary keys; a NaN score is
+ *             LZX_ERR_ARG (the message names the column and the index; checked before the device is touched).
+ *   order     descending key, ascending with LZX_SWEEP_ASCENDING; ties go by ascending vertex id in both directions.
+ *             order[c * n + i] = the vertex at position i of column c; pos is its inverse.  May be NULL.
+ *   profile   S_k = the first k vertices of the order.  vol[c * n + k - 1] = the sum of d over S_k.  b_v = the number of
+ *             neighbours u != v with pos[u] < pos[v], and cut[c * n + k - 1] = the sum of d_v - 2 b_v over S_k = the number
+ *             of edges that leave S_k; cut[n - 1] = 0 and vol[n - 1] = M.  Each may be NULL; only the outputs asked for cross
+ *             PCIe.
+ *   best      best[c]: the best prefix over k in [k_min, k_max]; k_min = 0 means 1 and k_max = 0 means n - 1.  den_k =
+ *             min(vol_k, M - vol_k) (conductance, the default) or min(k, n - k) with LZX_SWEEP_EXPANSION (edge expansion);
+ *             prefixes with den_k = 0 are left out.  The best k minimises cut_k / den_k, compared exactly: a is better than b
+ *             iff cut_a * den_b < cut_b * den_a in 64-bit integers; ties go to the smallest k.  value = (double)cut /
+ *             (double)den, one division.  With no admissible k (a graph without an edge, n = 1, a window of prefixes with
+ *             den = 0 only, k_min = n with k_max = 0): k = cut = vol = den = 0, value = +inf, and the call returns LZX_OK.
+ *   info      (or NULL) entries = M; ns and width = the columns of the call and B, the width they were padded to (1, 2, 4,
+ *             8 or 16); the host clock of the call and the device event times of the sorts (uploads, keys and positions
+ *             included), of the edge sweep, and of the scans with the reduction.
+ *   method    Per column: one launch maps the score to an order-preserving u64 key (complemented for descending order, all
+ *             ones for a vertex the per-degree rule puts last) beside the ids 0 .. n-1; hipcub's radix sort of the pairs is
+ *             stable, so ties keep their ascending ids; one launch writes pos, interleaved as u32 [n][B].  Then ONE pass over
+ *             the edges for all columns: a group of lanes per row (4 to 32, from the mean degree) loads, for every neighbour
+ *             u != v, the B positions of u as one line (16-byte loads where B >= 4), compares them with v's and counts in B
+ *             registers; the counts and d_v are summed over the group by shuffles and stored, d_v - 2 b_v (i64) and d_v (u64),
+ *             at place pos[v][c] of column c's arrays.  Rows of more than 64 times that many entries are listed (one
+ *             wavefront-aggregated append each; the list's order is no output) and go to a second launch, a workgroup per
+ *             row; both run only when such a row exists.  hipcub's inclusive sums over the two arrays give cut and vol; a
+ *             block-partial launch and a close launch apply the comparison above, and the host reads five words per column.
+ *             The sweep has no atomics and, after the key, nothing is floating-point; no kernel waits on another workgroup;
+ *             every loop is bounded by a row length, the list or the window.
+ *   bits      every output is an integer or one correctly rounded division of two integers: all of them are canonical, and
+ *             column c's outputs are bit-identical whatever else is in the batch and wherever c stands in it.
+ *   state     the call touches none of the handle's.  Everything it allocates is freed before it returns, on every path:
+ *             4 n B (rounded up to 16) + 16 n + 16 ns n + 24 ns g + 40 ns + 8 + 8 n' bytes (n' = n rounded up to even, g =
+ *             min(w / 256 + 1, 1024) blocks for a window of w + 1 prefixes), and behind it hipcub's temporary storage.
+ *   errors    LZX_ERR_ARG: null handle, scores or best; ns = 0; a flag bit other than the three; k_max > n; k_min > k_max
+ *             (k_min > n when k_max = 0); a NaN score.  LZX_ERR_LIMIT: ns > 16; nnz >= 2^32 (the products of the comparison
+ *             are below 2^63 because M < 2^32).  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a
+ *             sharded hand-over.  LZX_ERR_NOMEM: the message states the bytes.  The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted graphs; the columns of a call share flags and window; 16 ns n bytes of
+ *             profile state whether or not the profile is asked for.  A matrix that is not symmetric is not detected and its
+ *             numbers mean nothing, but the call returns and stays within its memory: every store goes to a place of the
+ *             order's permutation, and signed 64-bit arithmetic covers a negative running cut. */
+#define LZX_SWEEP_ASCENDING  1u
+#define LZX_SWEEP_PER_DEGREE 2u
+#define LZX_SWEEP_EXPANSION  4u
+typedef struct lzx_sweep_result {
+    uint64_t k;              /* vertices of the best prefix; 0: no admissible prefix */
+    uint64_t cut, vol, den;  /* of that prefix */
+    double   value;          /* (double)cut / (double)den; +inf with k = 0 */
+} lzx_sweep_result;
+typedef struct lzx_sweep_info {
+    uint64_t entries;        /* M */
+    uint32_t ns, width;      /* columns; the width B they were padded to */
+    double   loop_ms, sort_ms, sweep_ms, scan_ms;  /* host clock of the call; device event times of its three stages */
+} lzx_sweep_info;
+int lzx_sweep_cut(lzx_handle h, uint32_t ns, const double *scores /* [ns][n] */, uint32_t flags, uint64_t k_min, uint64_t k_max,
+                  uint32_t *order /* [ns][n] or NULL */, uint64_t *cut /* [ns][n] or NULL */, uint64_t *vol /* [ns][n] or NULL */,
+                  lzx_sweep_result *best /* [ns] */, lzx_sweep_info *info /* or NULL */);
+
 /* ---- measurement hook --------------------------------------------------------------------------
  * Runs `reps` back-to-back SpMVs of the current graph on a device-resident vector and returns the
  * average and minimum HIP-event time of one SpMV (all its kernels) in milliseconds.              */

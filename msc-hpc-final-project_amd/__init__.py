@@ -25,9 +25,13 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
                  "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
-                 "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes")
+                 "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes",
+                 "sweep_long_row", "sweep_state_bytes")
 
 LZX_COLOR_TIES_BY_ID = 1   # include/lzx.h: the colouring's order without the hash, (degree descending, id ascending)
+# include/lzx.h, the flags of lzx_sweep_cut: ascending keys; the key is score / degree; edge expansion instead of conductance
+LZX_SWEEP_ASCENDING, LZX_SWEEP_PER_DEGREE, LZX_SWEEP_EXPANSION = 1, 2, 4
+SWEEP_BATCH = 16           # score vectors per lzx_sweep_cut
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -169,6 +173,21 @@ class LzxModularityInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxSweepResult(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint64), ("cut", ctypes.c_uint64), ("vol", ctypes.c_uint64), ("den", ctypes.c_uint64), ("value", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LzxSweepInfo(ctypes.Structure):
+    _fields_ = [("entries", ctypes.c_uint64), ("ns", ctypes.c_uint32), ("width", ctypes.c_uint32), ("loop_ms", ctypes.c_double),
+                ("sort_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double), ("scan_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -237,6 +256,8 @@ SYMBOLS = [
     ("lzx_color", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxColorInfo)]),
     ("lzx_label_propagation", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxCommunitiesInfo)]),
     ("lzx_modularity", ctypes.c_int, [_h, _u32p, _f64p, ctypes.POINTER(LzxModularityInfo)]),
+    ("lzx_sweep_cut", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u32p, _u64p, _u64p,
+                                     ctypes.POINTER(LzxSweepResult), ctypes.POINTER(LzxSweepInfo)]),
 ]
 
 _LIB = None
@@ -1285,6 +1306,139 @@ class Engine:
         if not keep.any():
             raise ValueError(f"community: no vertex has the label {which}")
         return self.induced(keep, **options)
+
+    # ---- sweep cuts, spectral bisection, local clusters (include/lzx.h: lzx_sweep_cut) ----
+    def sweep_cut_raw(self, scores, ascending: bool = False, per_degree: bool = False, objective: str = "conductance", k_min: int = 0,
+                      k_max: int = 0, want_order: bool = True, want_profile: bool = False):
+        """(order, cut, vol, results, info) of lzx_sweep_cut for the score vectors `scores`, (n,) or (ns, n) with ns <= 16: the
+        vertices by descending score (ascending=True: ascending; per_degree=True: by score / degree, vertices without an edge
+        last), ties by ascending id; cut[c, k-1] and vol[c, k-1] of the first k vertices (uint64; None without want_profile, as
+        order is without want_order, and then they do not leave the device); results[c] = the lzx_sweep_result fields (k, cut,
+        vol, den, value) of the prefix with k_min <= k <= k_max (0: 1 and n - 1) of least conductance cut / min(vol, M - vol), or
+        least edge expansion cut / min(k, n - k) with objective="expansion" (k = 0 and value = inf when no prefix has a
+        denominator); info = the lzx_sweep_info fields.  The arrays always have the shape (ns, n)."""
+        if objective not in ("conductance", "expansion"):
+            raise ValueError(f"sweep_cut: objective must be 'conductance' or 'expansion', not {objective!r}")
+        S = np.ascontiguousarray(np.atleast_2d(np.asarray(scores, dtype=np.float64)))
+        if S.ndim != 2 or S.shape[1] != self.n:
+            raise ValueError(f"sweep_cut: scores must have shape ({self.n},) or (ns, {self.n}), got {np.shape(scores)}")
+        ns = S.shape[0]
+        flags = (LZX_SWEEP_ASCENDING if ascending else 0) | (LZX_SWEEP_PER_DEGREE if per_degree else 0) | \
+                (LZX_SWEEP_EXPANSION if objective == "expansion" else 0)
+        order = np.empty((ns, self.n), dtype=np.uint32) if want_order else None
+        cut = np.empty((ns, self.n), dtype=np.uint64) if want_profile else None
+        vol = np.empty((ns, self.n), dtype=np.uint64) if want_profile else None
+        best = (LzxSweepResult * max(ns, 1))()
+        info = LzxSweepInfo()
+        _check(self.L.lzx_sweep_cut(self.h, ns, _p(S, _f64p), flags, int(k_min), int(k_max), _p(order, _u32p) if want_order else None,
+                                    _p(cut, _u64p) if want_profile else None, _p(vol, _u64p) if want_profile else None, best, ctypes.byref(info)),
+               "lzx_sweep_cut", self.L)
+        return order, cut, vol, [best[c].as_dict() for c in range(ns)], info.as_dict()
+
+    def sweep_cut(self, score, **kw):
+        """The best prefix of the sweep over `score` (see sweep_cut_raw, whose keywords it takes): (members = the vertices of the
+        prefix as sorted ids (int64), value, result).  A 2-D score, (ns, n), gives a list of these, one per row."""
+        order, _, _, results, _ = self.sweep_cut_raw(score, want_order=True, want_profile=False, **kw)
+        out = [(np.sort(order[c, :r["k"]].astype(np.int64)), r["value"], r) for c, r in enumerate(results)]
+        return out if np.ndim(score) == 2 else out[0]
+
+    def _indicator(self, S, what):
+        S = np.asarray(S)
+        ind = np.zeros(self.n)
+        if S.dtype == np.bool_:
+            if S.shape != (self.n,):
+                raise ValueError(f"{what}: a mask must have shape ({self.n},), got {S.shape}")
+            ind[S] = 1.0
+        elif S.size:
+            idx = S.astype(np.int64).ravel()
+            if idx.min() < 0 or idx.max() >= self.n:
+                raise ValueError(f"{what}: the set must hold vertices 0 .. {self.n - 1}")
+            ind[idx] = 1.0
+        return ind, int(ind.sum())
+
+    def _set_sweep(self, S, what, objective="conductance"):
+        """the lzx_sweep_result of the set S against its complement: one sweep of S's indicator with k_min = k_max = |S|"""
+        ind, size = self._indicator(S, what)
+        if size == 0:   # (the prefix of no vertex: nothing to sweep)
+            return dict(k=0, cut=0, vol=0, den=0, value=float("inf"))
+        _, cut, vol, results, _ = self.sweep_cut_raw(ind, objective=objective, k_min=size, k_max=size, want_order=False, want_profile=True)
+        r = results[0]
+        if r["k"] == 0:   # a denominator of 0: the integers come from the profile
+            r = dict(k=size, cut=int(cut[0, size - 1]), vol=int(vol[0, size - 1]), den=0, value=float("inf"))
+        return r
+
+    def cut_size(self, S):
+        """networkx.cut_size(G, S): the edges between S (an index list or a boolean mask) and its complement."""
+        return int(self._set_sweep(S, "cut_size")["cut"])
+
+    def volume(self, S):
+        """networkx.volume(G, S): the sum of the degrees of S, self loops not counted."""
+        return int(self._set_sweep(S, "volume")["vol"])
+
+    def conductance(self, S):
+        """networkx.conductance(G, S) = cut_size / min(volume(S), volume(complement)); inf where networkx divides by zero."""
+        return float(self._set_sweep(S, "conductance")["value"])
+
+    def edge_expansion(self, S):
+        """networkx.edge_expansion(G, S) = cut_size / min(|S|, |complement|); inf where networkx divides by zero."""
+        return float(self._set_sweep(S, "edge_expansion", "expansion")["value"])
+
+    def spectral_bisection(self, tol: float = 1e-10, m: int = 0, max_restarts: int = 300, seed: int = 0, objective: str = "conductance"):
+        """The sweep cut of the Fiedler vector of a connected graph: (members, value, lambda2, info).  components() first (more
+        than one component: ValueError -- bisect largest_component() instead); then eigsh(1, "SA") of the Laplacian with the
+        constant vector deflated, and the sweep of its vector (sweep_cut).  info = eigsh's, with the sweep's result under "sweep".
+        The operator option is set to the Laplacian for the solve and put back afterwards, on exceptions too.  Like eigsh, and
+        like any change of the operator option, it voids a prepared chunked decomposition."""
+        _, cinfo = self.components(want_labels=False)
+        if cinfo["n_components"] != 1:
+            raise ValueError(f"spectral_bisection: the graph has {cinfo['n_components']} components; bisect one of them, e.g. "
+                             "largest_component()")
+        if self.n < 2:
+            raise ValueError("spectral_bisection: a graph of one vertex has no bisection")
+        previous = self.operator
+        self.set_option("operator", OP_LAPLACIAN)
+        try:
+            w, V, info = self.eigsh(1, "SA", m=m, tol=tol, max_restarts=max_restarts, seed=seed, deflate=np.full(self.n, 1.0 / np.sqrt(self.n)))
+        finally:
+            self.set_option("operator", previous)
+        members, value, result = self.sweep_cut(V[:, 0], objective=objective)
+        info["sweep"] = result
+        return members, value, float(w[0]), info
+
+    def local_cluster(self, seeds, method: str = "pagerank", alpha: float = 0.85, t: float = 1.0, k: int = 50, k_max: int = 0, tol: float = 1e-10):
+        """A low-conductance set around every seed vertex: a diffusion from the seed, then the sweep of diffusion / degree
+        (sweep_cut with per_degree=True and prefixes of at most k_max vertices, 0: n - 1).  method="pagerank": one
+        pagerank(alpha, personalization=e_seed, tol=tol) per seed (Andersen, Chung and Lang).  method="heat": the heat kernel
+        e^(-tL) e_seed by k Lanczos iterations (at most n), batched for up to 16 seeds (lanczos_multi and multout_multi under the
+        Laplacian; Chung's heat-kernel PageRank); it replaces the resident batch basis and voids a prepared chunked
+        decomposition, and the operator option is put back afterwards.  Up to 16 seeds share one sweep over the edges.  Returns
+        one (members, value, result) per seed, as sweep_cut does; a scalar seed returns one."""
+        if method not in ("pagerank", "heat"):
+            raise ValueError(f"local_cluster: method must be 'pagerank' or 'heat', not {method!r}")
+        ids = np.atleast_1d(np.asarray(seeds)).astype(np.int64)
+        if ids.ndim != 1 or len(ids) == 0 or ids.min() < 0 or ids.max() >= self.n:
+            raise ValueError(f"local_cluster: seeds must be vertices 0 .. {self.n - 1}")
+        out = []
+        for first in range(0, len(ids), SWEEP_BATCH):
+            batch = ids[first:first + SWEEP_BATCH]
+            X = np.zeros((len(batch), self.n))
+            X[np.arange(len(batch)), batch] = 1.0
+            out += self.sweep_cut(self._diffuse(X, method, alpha, t, k, tol), per_degree=True, k_max=k_max)
+        return out[0] if np.ndim(seeds) == 0 else out
+
+    def _diffuse(self, X, method, alpha, t, k, tol):
+        """the diffusion of local_cluster from the seed indicators X (b, n), b <= 16: personalised PageRank, or e^(-tL) X"""
+        if method == "pagerank":
+            return np.vstack([self.pagerank(alpha, personalization=x, tol=tol) for x in X])
+        k = max(1, min(int(k), self.n))
+        previous = self.operator
+        self.set_option("operator", OP_LAPLACIAN)
+        try:
+            a, b, _, xn, _, _ = self.lanczos_multi(X, k)
+            T = np.vstack([_expm_coefficients(a[c], b[c][:k - 1], xn[c], -t) for c in range(len(X))])
+            return self.multout_multi(T)
+        finally:
+            self.set_option("operator", previous)
 
     def bench_stream(self, nbytes: int = 1 << 30, reps: int = 5):
         rd, cp = ctypes.c_double(), ctypes.c_double()

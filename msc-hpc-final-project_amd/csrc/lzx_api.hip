@@ -179,6 +179,10 @@ static const Option g_options[] = {
     {"lpa_group_row", &lzx_ctx::lpa_group_opt, OPT_SHAPE},
     {"lpa_table_row", &lzx_ctx::lpa_table_opt, OPT_SHAPE},
     {"lpa_state_bytes", &lzx_ctx::lpa_cap_opt, OPT_SHAPE},
+    // lzx_sweep_cut: rows with more than this many entries take the long-row launch (default 64 times the lanes per row); a state of
+    // more than this many bytes is out of device memory
+    {"sweep_long_row", &lzx_ctx::sweep_long_opt, OPT_SHAPE},
+    {"sweep_state_bytes", &lzx_ctx::sweep_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

@@ -105,13 +105,6 @@ struct PredSameLabel {
     __device__ __forceinline__ bool operator()(u32 v, u32 u) const { return label[u] == label[v]; }
 };
 
-__device__ __forceinline__ u32 wave_sum_u32(u32 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u32)__shfl_xor((int)v, o, 64);
-    return v;
-}
-
 // The calling lanes for which `active` holds add one to bins[key] each, the lanes of one key with one atomic.  Every lane of the
 // wavefront must call it together.  Returns the lane's place in its bin: the count before the wavefront plus its rank among the
 // wavefront's lanes of the same key (meaningless where !active).
@@ -156,8 +149,7 @@ k_row_count(const u64 *row_ptr, const u32 *col_idx, P pred, u32 *out, u32 n, u32
         const u32 u = col_idx[beg + e];
         if (u != (u32)row && pred((u32)row, u)) ++cnt;
     }
-#pragma unroll
-    for (u32 o = G / 2; o > 0; o >>= 1) cnt += (u32)__shfl_xor((int)cnt, (int)o, 64);
+    cnt = lzx_group_sum_u32<G>(cnt);
     if (sub == 0 && mine) out[row] = cnt;
 }
 
@@ -179,7 +171,7 @@ k_row_count_long(const u64 *row_ptr, const u32 *col_idx, P pred, u32 *out, u32 n
             const u32 u = col_idx[e];
             if (u != v && pred(v, u)) ++cnt;
         }
-        cnt = wave_sum_u32(cnt);
+        cnt = lzx_wave_sum_u32(cnt);
         if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
         __syncthreads();
         if (threadIdx.x == 0) out[v] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);

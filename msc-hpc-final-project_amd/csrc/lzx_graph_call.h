@@ -1,6 +1,6 @@
 // lzx_graph_call.h -- what the graph routines on the caller-order CSR (d_row_ptr / d_col_idx) share: lzx_components,
 // lzx_bfs_multi / lzx_betweenness_f64 (lzx_paths.hip), lzx_triangles, lzx_core_numbers, lzx_truss and lzx_color /
-// lzx_label_propagation / lzx_modularity (lzx_communities.hip).  Host side: the preconditions of such
+// lzx_label_propagation / lzx_modularity (lzx_communities.hip) and lzx_sweep_cut (lzx_sweep.hip).  Host side: the preconditions of such
 // a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
 // the choice of lanes per row.  Device side: the idioms of their kernels over ascending rows and wavefront-aggregated queues.
 #pragma once
@@ -24,7 +24,7 @@ inline int lzx_graph_call_check(const lzx_ctx *c, const char *fn, const char *wh
 struct LzxGraphRun {
     lzx_ctx *c;
     void *arena = nullptr, *more[2] = {nullptr, nullptr};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     explicit LzxGraphRun(lzx_ctx *c_) : c(c_) {}
     ~LzxGraphRun()
     {
@@ -32,8 +32,8 @@ struct LzxGraphRun {
         (void)hipStreamSynchronize(c->stream);
         for (void *p : {arena, more[0], more[1]})
             if (p) (void)hipFree(p);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
+        for (hipEvent_t e : {ev0, ev1, ev2, ev3})
+            if (e) (void)hipEventDestroy(e);
     }
     LzxGraphRun(const LzxGraphRun &) = delete;
     LzxGraphRun &operator=(const LzxGraphRun &) = delete;
@@ -86,6 +86,16 @@ __device__ __forceinline__ u32 lzx_degree_no_diagonal(const u64 *row_ptr, const 
     const u32 at = lzx_lower_bound(col_idx + beg, len, (u32)v);
     return len - ((at < len && col_idx[beg + at] == (u32)v) ? 1u : 0u);
 }
+
+// a row's count summed over the G lanes that share the row (every lane gets the sum), and over the wavefront
+template <u32 G>
+__device__ __forceinline__ u32 lzx_group_sum_u32(u32 v)
+{
+#pragma unroll
+    for (u32 o = G / 2; o > 0; o >>= 1) v += (u32)__shfl_xor((int)v, (int)o, 64);
+    return v;
+}
+__device__ __forceinline__ u32 lzx_wave_sum_u32(u32 v) { return lzx_group_sum_u32<64>(v); }
 
 // the calling lanes for which `take` holds get consecutive places behind *tail: one atomic per wavefront.  Every lane of the
 // wavefront must call it together.  Returns the lane's place (meaningless where !take).

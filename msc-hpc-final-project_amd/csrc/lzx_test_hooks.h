@@ -31,7 +31,10 @@
 // is updated by a group of lanes, which stages the first 128 labels in LDS and reads the rest of a longer row where it lies; default 128),
 // "lpa_table_row" (a longer row of at most this many entries is counted in the LDS table by a workgroup, the rest in a table in global
 // memory; default and at most 2048, half the LDS table's slots), "lpa_state_bytes" (lzx_label_propagation takes a state larger than this many
-// bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables).
+// bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables), "sweep_long_row"
+// (lzx_sweep_cut: a row with more than this many entries is swept by the long-row launch, a workgroup per row; default 64 times the
+// lanes per row), "sweep_state_bytes" (lzx_sweep_cut takes a state larger than this many bytes as out of device memory, before the
+// device is touched).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
