@@ -996,7 +996,8 @@ int lzx_bench_stream(lzx_handle h, uint64_t bytes, uint32_t reps, double *read_g
  *                           sums stay fp64).  Off by default and NOT within the 1e-10 criterion: 6e-8 relative rounding per
  *                           entry and iteration ends near 1e-8 in the centrality vector (6.9e-9 measured on BASELINE C1;
  *                           the reference's own float runs end at 1.2e-6, parallel-final/output/single_double.txt:319)
- *                           -- SURVEY 8(f) N4
+ *                           -- SURVEY 8(f) N4.  Every rank multiplies the rounded vector in ALL entries, its own slice
+ *                           included, while the inner product and the norm use the unrounded local vector.
  *   "lazy_normalisation"    1: multiply (and, with several ranks, exchange) the unnormalised vector, so that alpha and
  *                           beta come out of one reduction per iteration (one 2-double all-reduce) and one vector kernel;
  *                           0: the reference's operation order.  Default: 1 with several ranks and in blocked mode, 0 on

@@ -229,7 +229,17 @@ def test_run_in_chunks_and_early_stop(pkg, oracle):
             a, b, Q = eng.lanczos_fetch(done, want_q=True)
             assert np.array_equal(a, a1[:done]) and np.array_equal(b, b1[:done - 1]) and np.array_equal(Q, Q1[:done]), (mode, done)
             t = np.random.default_rng(done).random(done)
-            assert np.allclose(eng.multout(t), t @ Q, rtol=1e-12, atol=1e-14) or mode.get("basis_fp32")
+            if not mode.get("basis_fp32"):
+                assert np.allclose(eng.multout(t), t @ Q, rtol=1e-12, atol=1e-14)
+            else:
+                # the fp32-stored basis: against the longdouble sum over the FETCHED (rounded) columns, entry by entry, at the
+                # bounds derived in test_gpu_fp32_forms._check_basis_fp32 -- rows with an edge: k fp64 products of widened
+                # values; rows without one: the factored form c_j f32(q_0[i]) t_j, one fp32 rounding from the fetched column
+                tl, Ql = t.astype(np.longdouble), Q.astype(np.longdouble)
+                S = np.abs(tl) @ np.abs(Ql)
+                bound = np.where(np.diff(rp.astype(np.int64)) > 0, (done + 4) * 2.0 ** -53 * S,
+                                 (2.0 ** -24 * (1 + 2.0 ** -20) + (done + 4) * 2.0 ** -53) * S + 2.0 ** -149 * float(np.abs(t[1:]) @ (1.0 / b)))
+                assert (np.abs(eng.multout(t).astype(np.longdouble) - tl @ Ql) <= bound).all(), (mode, done)
         with pytest.raises(pkg.LzxError):
             eng.lanczos_run_steps(1)                      # complete: nothing left
         eng.lanczos_prepare(x0, K)
@@ -305,7 +315,15 @@ def test_basis_stored_as_fp32(pkg, oracle):
             assert xn32 == xn and np.array_equal(a32, a64) and np.array_equal(b32, b64), (name, mode)
             scale = np.abs(Q64).max(axis=1, keepdims=True)
             assert np.abs(Q32 - Q64).max() <= 1e-7 * scale.max() and np.abs(Q32 - Q64).max() > 0
-            err = rel_inf(e32.multout(t), ref)
+            # ... and entry by entry (derivation: test_gpu_fp32_forms._check_basis_fp32): column 0 is q_0 rounded once; column
+            # j >= 1 is f32(u_j) divided by beta_{j-1} on the way out -- one fp32 rounding on rows with an edge, two on rows
+            # without one (k_iso_fill<float> multiplies the STORED q_0[i] by the scalar d_j and rounds the product)
+            assert np.array_equal(Q32[0], Q64[0].astype(np.float32).astype(np.float64)), (name, mode)
+            roundings = np.where(np.diff(rp.astype(np.int64)) > 0, 1.0, 2.0)
+            for j in range(1, k):
+                bound = roundings * 2.0 ** -24 * (1 + 2.0 ** -20) * np.abs(Q64[j]) + 2.0 ** -149 / b64[j - 1]
+                assert (np.abs(Q32[j] - Q64[j]) <= bound).all(), (name, mode, j, (np.abs(Q32[j] - Q64[j]) / bound).max())
+            err =rel_inf(e32.multout(t), ref)
             err_f = rel_inf(ans_factored, ref)
             err64 = rel_inf(e64.multout(t), ref)
             print(f"{name} {mode}: centrality vector vs oracle: fp32-stored basis {err:.2e} ({err_f:.2e} before the fetch), fp64 basis {err64:.2e}")
