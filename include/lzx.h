@@ -758,6 +758,88 @@ int lzx_truss(lzx_handle h, uint32_t *support /* [nnz] or NULL */, uint32_t *tru
               uint32_t *layer /* [nnz] or NULL */, uint32_t *vertex_truss /* [n] or NULL */,
               lzx_truss_info *info /* or NULL */);
 
+/* ---- similarity of two vertices: common neighbours, Jaccard, Adamic-Adar ---------------------------------
+ * lzx_similarity: how alike two vertices of the handle's graph are, read as undirected and unweighted -- what the functions of
+ * networkx.link_prediction return (common_neighbors, jaccard_coefficient, adamic_adar_index, resource_allocation_index) and the
+ * overlap and Sorensen coefficients next to them -- for a list of pairs or for every stored entry, on the device over the
+ * caller-order CSR.
+ *   outputs   N(x) = row x without a diagonal entry, d_x = |N(x)|, c = |N(u) n N(v)|: with u != v exactly
+ *             len(networkx.common_neighbors(G, u, v)) of the graph without self loops.  A self loop changes nothing in any
+ *             output.  common[p] = c, deg_u[p] = d_u, deg_v[p] = d_v.  values is [popcount(measures)][np], one row of np
+ *             doubles per flag of `measures`, in ascending order of the flags' bits:
+ *               LZX_SIM_JACCARD              c / (d_u + d_v - c), exactly 0.0 where the denominator is 0 (networkx's rule)
+ *               LZX_SIM_OVERLAP              c / min(d_u, d_v), 0.0 where the minimum is 0
+ *               LZX_SIM_SORENSEN             2 c / (d_u + d_v), 0.0 where the sum is 0
+ *               LZX_SIM_ADAMIC_ADAR          sum over w in N(u) n N(v) of 1 / log d_w
+ *               LZX_SIM_RESOURCE_ALLOCATION  sum over w in N(u) n N(v) of 1 / d_w
+ *             The first three are one correctly rounded fp64 division of two integers: networkx's bits.  A common neighbour of
+ *             two distinct vertices has d_w >= 2, so no term of the two sums is infinite; a sum over no term is exactly 0.0.
+ *             Every output may be NULL (values only with measures == 0); only those asked for cross PCIe.
+ *             PAIRS MODE (u and v given): np pairs (u[p], v[p]).  (u, v) and (v, u) give the same bits, and a pair's outputs
+ *             depend neither on what else is in the batch nor on its position in it.
+ *             EDGES MODE (u == v == NULL, np must equal nnz): one output per stored entry of lzx_get_graph_csr's col_idx, laid out
+ *             as lzx_truss lays out its vectors: entry e of row r gets the pair (r, col_idx[e]).  Both copies of an edge carry
+ *             identical bits -- the bits pairs mode gives that pair --, a diagonal entry carries 0 everywhere (deg_u and deg_v
+ *             included).  Each undirected edge is intersected once, from the entry with u < v; the mirror entry finds it by a
+ *             binary search of u in row v (and carries 0 where a matrix that is not symmetric has none).
+ *   info      (or NULL) pairs = np; walked = the sum of min(|row u|, |row v|), stored lengths, over the pairs intersected (in
+ *             edges mode every edge once); max_common = the largest c; short_pairs, long_pairs, sliced_pairs = the pairs
+ *             intersected on each of the three paths below (in edges mode they add up to the edges, not to np); lanes = the
+ *             lanes per short pair; the host clock of the call, the device event time of the preparation (degrees, tables,
+ *             the pair list of edges mode) and of everything from the classification to the last launch (the host's one read
+ *             in between included).
+ *   method    (1) Preparation: d_v by one thread per row (lzx_triangles' degree kernel) and, only for a sum that is asked for, one
+ *             fp64 table per sum: 1 / log d_v (0 where d_v < 2) and 1 / d_v (0 where d_v < 1).  A hit then costs one 8-byte
+ *             gather and no log runs in the walk.  (2) The walk: the shorter of the two stored rows is walked -- on a tie in
+ *             length the row of the smaller id, so both orders of a pair take the same path -- and the longer binary-searched;
+ *             u and v themselves are skipped; a lane's entries ascend, so each search starts at the place the previous one
+ *             ended.  (3) Three paths by s = the walked row's stored length.  SHORT, s <= 64 G: a group of G lanes per pair (4 to
+ *             32, from the graph's mean degree), lane i takes the entries i, i + G, ...  LONG, s above that: one workgroup of 256
+ *             per pair, thread i takes i, i + 256, ...  SLICED, s also above 16384: the walked row is cut into
+ *             min(64, ceil(s / 16384)) equal contiguous slices, one workgroup each, whose partial count and partial sums go to
+ *             a table that a closing launch adds in slice order -- two hubs of an R-MAT graph can each have millions of
+ *             entries, and one workgroup must not carry such a pair alone.  Long and sliced pairs are first counted, then
+ *             listed (a ballot and one atomic per wavefront).  (4) Sums: a lane adds its terms in ascending position; the lanes
+ *             of a group or wavefront close with a fixed shuffle tree; the four wavefronts of a workgroup are added in LDS as
+ *             (w0 + w1) + (w2 + w3); slices are added in ascending order.  Every one of these orders depends only on the two
+ *             row lengths and on G: that is what makes a pair's bits independent of the batch.  (5) One closing launch forms
+ *             the three ratios, copies the mirror entries of edges mode, gathers the degrees and takes the maximum of c.
+ *             There is no floating-point atomic anywhere; the integer atomics (the two list tails, the maximum) are 32-bit
+ *             vector atomics.  No kernel waits on another workgroup; every walk is bounded by a row length.  The long path stages
+ *             no pivots of the searched row in LDS.
+ *   bits      identical arguments give identical bits.  common, deg_u, deg_v and the three ratios are canonical: any correct
+ *             algorithm gives them.  The two sums depend on G -- the graph's mean degree -- and on the two row lengths only.
+ *   state     the call touches none: it voids no prepared or chunked decomposition and leaves the resident bases and the batch
+ *             state alone.  Everything it allocates is freed before it returns, on every path: 4 n of degrees, 8 n per sum
+ *             asked for, 8 np of pairs, 4 np of counts, 8 np per measure, 4 np per degree output, 16 KiB of partials; then,
+ *             once they are counted, 4 bytes per long or sliced pair and 1280 per sliced pair.
+ *   errors    LZX_ERR_ARG: null handle; an unknown bit in measures; measures without values; only one of u and v; np != nnz in
+ *             edges mode; u[p] >= n, v[p] >= n or u[p] == v[p] (the lists are the host's: both are checked before the device is
+ *             touched).  LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded hand-over.
+ *             LZX_ERR_LIMIT: np >= 2^32 - 1.  LZX_ERR_NOMEM: the message states the bytes.  np == 0 (after these checks) returns
+ *             LZX_OK and touches nothing but *info.  The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted graphs; no all-pairs at distance two, no top-k of a seed.  Cosine
+ *             similarity c / sqrt(d_u d_v) and preferential attachment d_u d_v are left to the caller, from common, deg_u and
+ *             deg_v: the rounding of the device's square root is not pinned here.  A matrix that is not symmetric is not
+ *             detected: the call stays within its memory and its numbers mean nothing. */
+#define LZX_SIM_JACCARD             1u
+#define LZX_SIM_OVERLAP             2u
+#define LZX_SIM_SORENSEN            4u
+#define LZX_SIM_ADAMIC_ADAR         8u
+#define LZX_SIM_RESOURCE_ALLOCATION 16u
+typedef struct lzx_similarity_info {
+    uint64_t pairs;            /* np */
+    uint64_t walked;           /* sum of min(|row u|, |row v|) over the pairs intersected */
+    uint64_t short_pairs, long_pairs, sliced_pairs;  /* pairs intersected on each path */
+    uint32_t max_common;       /* the largest c */
+    uint32_t lanes;            /* lanes per short pair */
+    double   loop_ms, prep_ms, count_ms;  /* host clock of the call; device event time of the preparation / of the classification, the walks and the closing launch */
+} lzx_similarity_info;
+int lzx_similarity(lzx_handle h, uint64_t np, const uint32_t *u, const uint32_t *v /* [np] each; both NULL: every stored entry */,
+                   uint32_t measures, uint32_t *common /* [np] or NULL */, uint32_t *deg_u /* [np] or NULL */,
+                   uint32_t *deg_v /* [np] or NULL */, double *values /* [popcount(measures)][np], or NULL with measures == 0 */,
+                   lzx_similarity_info *info /* or NULL */);
+
 /* ---- greedy colouring, label-propagation communities, modularity ----------------------------------------
  * Three calls on the handle's graph read as undirected and unweighted, each useful alone: a proper vertex colouring
  * (networkx.coloring.greedy_color), the communities of semi-synchronous label propagation over its colour classes

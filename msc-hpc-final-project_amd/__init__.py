@@ -26,12 +26,16 @@ SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
                  "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
                  "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes",
-                 "sweep_long_row", "sweep_state_bytes")
+                 "sweep_long_row", "sweep_state_bytes", "sim_long_pair", "sim_slice", "sim_state_bytes")
 
 LZX_COLOR_TIES_BY_ID = 1   # include/lzx.h: the colouring's order without the hash, (degree descending, id ascending)
 # include/lzx.h, the flags of lzx_sweep_cut: ascending keys; the key is score / degree; edge expansion instead of conductance
 LZX_SWEEP_ASCENDING, LZX_SWEEP_PER_DEGREE, LZX_SWEEP_EXPANSION = 1, 2, 4
 SWEEP_BATCH = 16           # score vectors per lzx_sweep_cut
+# include/lzx.h, the measures of lzx_similarity, in the order of their rows in `values`
+LZX_SIM_JACCARD, LZX_SIM_OVERLAP, LZX_SIM_SORENSEN, LZX_SIM_ADAMIC_ADAR, LZX_SIM_RESOURCE_ALLOCATION = 1, 2, 4, 8, 16
+SIM_MEASURES = {"jaccard": LZX_SIM_JACCARD, "overlap": LZX_SIM_OVERLAP, "sorensen": LZX_SIM_SORENSEN,
+                "adamic_adar": LZX_SIM_ADAMIC_ADAR, "resource_allocation": LZX_SIM_RESOURCE_ALLOCATION}
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -188,6 +192,15 @@ class LzxSweepInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxSimilarityInfo(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_uint64), ("walked", ctypes.c_uint64), ("short_pairs", ctypes.c_uint64), ("long_pairs", ctypes.c_uint64),
+                ("sliced_pairs", ctypes.c_uint64), ("max_common", ctypes.c_uint32), ("lanes", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("prep_ms", ctypes.c_double), ("count_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # every symbol include/lzx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lzx_create", ctypes.c_int, [_hp, ctypes.c_int]),
@@ -258,6 +271,8 @@ SYMBOLS = [
     ("lzx_modularity", ctypes.c_int, [_h, _u32p, _f64p, ctypes.POINTER(LzxModularityInfo)]),
     ("lzx_sweep_cut", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u32p, _u64p, _u64p,
                                      ctypes.POINTER(LzxSweepResult), ctypes.POINTER(LzxSweepInfo)]),
+    ("lzx_similarity", ctypes.c_int, [_h, ctypes.c_uint64, _u32p, _u32p, ctypes.c_uint32, _u32p, _u32p, _u32p, _f64p,
+                                      ctypes.POINTER(LzxSimilarityInfo)]),
 ]
 
 _LIB = None
@@ -1218,6 +1233,107 @@ class Engine:
             sub.close()
             raise
         return sub, old
+
+    # ---- similarity of two vertices (include/lzx.h: lzx_similarity) ----
+    def _pairs(self, pairs, what):
+        arr = np.asarray(pairs)
+        if arr.size == 0:
+            return np.zeros((0, 2), dtype=np.uint32)
+        if arr.ndim != 2 or arr.shape[1] != 2 or not np.issubdtype(arr.dtype, np.integer) or arr.min() < 0 or arr.max() >= self.n:
+            raise ValueError(f"{what}: pairs must be an (np, 2) array or a list of pairs of integer vertex ids in [0, {self.n})")
+        if (arr[:, 0] == arr[:, 1]).any():
+            raise ValueError(f"{what}: a vertex is not compared with itself")
+        return arr.astype(np.uint32)
+
+    def similarity_raw(self, pairs=None, measures=("jaccard", "overlap", "sorensen", "adamic_adar", "resource_allocation"),
+                       want_common: bool = True, want_degrees: bool = True):
+        """(common, deg_u, deg_v, values, info) of lzx_similarity for the pairs (u, v) of an (np, 2) array or a list of pairs, or,
+        with pairs=None, for every stored entry of get_graph_csr()'s col_idx (entry e of row r is the pair (r, col_idx[e]); both
+        copies of an edge carry the same bits, a diagonal entry carries 0).  common[p] = the common neighbours of the pair,
+        deg_u[p] and deg_v[p] the degrees of its ends, self loops not counted (uint32; None when not wanted, and then they do not
+        leave the device); values = {measure: float64 array} for the names in `measures`, out of "jaccard", "overlap",
+        "sorensen", "adamic_adar", "resource_allocation"; info = the lzx_similarity_info fields (pairs, walked, short_pairs,
+        long_pairs, sliced_pairs, max_common, lanes, loop_ms, prep_ms, count_ms)."""
+        names = [measures] if isinstance(measures, str) else list(measures)
+        unknown = [m for m in names if m not in SIM_MEASURES]
+        if unknown:
+            raise ValueError(f"similarity_raw: unknown measure {unknown[0]!r} (known: {', '.join(SIM_MEASURES)})")
+        bits = 0
+        for m in names:
+            bits |= SIM_MEASURES[m]
+        rows = [m for m in SIM_MEASURES if SIM_MEASURES[m] & bits]          # ascending bit order
+        if pairs is None:
+            count = int(self.info()["nnz"])
+            pu = pv = None
+        else:
+            pr = self._pairs(pairs, "similarity_raw")
+            count = len(pr)
+            pu = np.ascontiguousarray(pr[:, 0]) if count else np.zeros(1, dtype=np.uint32)
+            pv = np.ascontiguousarray(pr[:, 1]) if count else np.zeros(1, dtype=np.uint32)
+        room = max(count, 1)
+        common = np.zeros(room, dtype=np.uint32) if want_common else None
+        deg_u = np.zeros(room, dtype=np.uint32) if want_degrees else None
+        deg_v = np.zeros(room, dtype=np.uint32) if want_degrees else None
+        vals = np.zeros((max(len(rows), 1), room))
+        info = LzxSimilarityInfo()
+        opt = lambda a: None if a is None else _p(a, _u32p)   # noqa: E731
+        _check(self.L.lzx_similarity(self.h, count, opt(pu), opt(pv), bits, opt(common), opt(deg_u), opt(deg_v), _p(vals, _f64p) if rows else None,
+                                     ctypes.byref(info)), "lzx_similarity", self.L)
+        cut = lambda a: None if a is None else a[:count]      # noqa: E731
+        flat = vals.reshape(-1)
+        values = {m: flat[k * count:(k + 1) * count].copy() for k, m in enumerate(rows)}
+        return cut(common), cut(deg_u), cut(deg_v), values, info.as_dict()
+
+    def _similarity_value(self, pairs, measure):
+        return self.similarity_raw(pairs, measures=(measure,), want_common=False, want_degrees=False)[3][measure]
+
+    def common_neighbors_count(self, pairs):
+        """len(networkx.common_neighbors(G, u, v)) for every pair (uint32 array), self loops ignored."""
+        return self.similarity_raw(pairs, measures=(), want_degrees=False)[0]
+
+    def jaccard_coefficient(self, pairs):
+        """networkx.jaccard_coefficient: |N(u) n N(v)| / |N(u) u N(v)| for every pair, 0 where the union is empty (float64)."""
+        return self._similarity_value(pairs, "jaccard")
+
+    def overlap_coefficient(self, pairs):
+        """|N(u) n N(v)| / min(d_u, d_v) for every pair, 0 where the minimum is 0 (float64)."""
+        return self._similarity_value(pairs, "overlap")
+
+    def sorensen_coefficient(self, pairs):
+        """2 |N(u) n N(v)| / (d_u + d_v) for every pair, 0 where the sum is 0 (float64)."""
+        return self._similarity_value(pairs, "sorensen")
+
+    def adamic_adar_index(self, pairs):
+        """networkx.adamic_adar_index: the sum over the common neighbours w of 1 / log d_w, for every pair (float64)."""
+        return self._similarity_value(pairs, "adamic_adar")
+
+    def resource_allocation_index(self, pairs):
+        """networkx.resource_allocation_index: the sum over the common neighbours w of 1 / d_w, for every pair (float64)."""
+        return self._similarity_value(pairs, "resource_allocation")
+
+    def preferential_attachment(self, pairs):
+        """networkx.preferential_attachment: d_u d_v for every pair, formed here as int64 from the degrees the device returns."""
+        _, du, dv, _, _ = self.similarity_raw(pairs, measures=(), want_common=False)
+        return du.astype(np.int64) * dv.astype(np.int64)
+
+    def cosine_similarity(self, pairs):
+        """|N(u) n N(v)| / sqrt(d_u d_v) for every pair, 0 where a degree is 0 (float64).  Formed here in numpy from the counts
+        and degrees the device returns: the rounding of the device's square root is not pinned, numpy's is."""
+        c, du, dv, _, _ = self.similarity_raw(pairs, measures=())
+        prod = du.astype(np.float64) * dv.astype(np.float64)
+        out = np.zeros(len(c))
+        nz = prod > 0
+        out[nz] = c[nz] / np.sqrt(prod[nz])
+        return out
+
+    def edge_similarity(self, measure="jaccard"):
+        """One similarity per edge: a scipy CSR matrix over the handle's pattern, symmetric, a diagonal entry holding 0.  `measure`
+        is one of similarity_raw's names (float64), or "common_neighbors" (uint32: the matrix edge_support() returns)."""
+        if measure == "common_neighbors":
+            return self._edge_matrix(self.similarity_raw(None, measures=(), want_degrees=False)[0])
+        if measure not in SIM_MEASURES:
+            raise ValueError(f"edge_similarity: unknown measure {measure!r} (known: common_neighbors, {', '.join(SIM_MEASURES)})")
+        return self._edge_matrix(self._similarity_value(None, measure))
 
     # ---- colouring, label-propagation communities, modularity (include/lzx.h: lzx_color, lzx_label_propagation, lzx_modularity;
     # DESIGN.md section 21) ----

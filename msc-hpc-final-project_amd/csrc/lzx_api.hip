@@ -183,6 +183,12 @@ static const Option g_options[] = {
     // more than this many bytes is out of device memory
     {"sweep_long_row", &lzx_ctx::sweep_long_opt, OPT_SHAPE},
     {"sweep_state_bytes", &lzx_ctx::sweep_cap_opt, OPT_SHAPE},
+    // lzx_similarity: pairs whose shorter row has more than sim_long_pair entries (default 64 times the lanes per pair) get a workgroup
+    // each, and those of more than sim_slice as well (default 16384) one workgroup per slice of that many entries, 64 at the most; a
+    // state of more than sim_state_bytes is out of device memory
+    {"sim_long_pair", &lzx_ctx::sim_long_opt, OPT_SHAPE},
+    {"sim_slice", &lzx_ctx::sim_slice_opt, OPT_SHAPE},
+    {"sim_state_bytes", &lzx_ctx::sim_cap_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},

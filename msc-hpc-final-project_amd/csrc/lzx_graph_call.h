@@ -1,6 +1,6 @@
 // lzx_graph_call.h -- what the graph routines on the caller-order CSR (d_row_ptr / d_col_idx) share: lzx_components,
 // lzx_bfs_multi / lzx_betweenness_f64 (lzx_paths.hip), lzx_triangles, lzx_core_numbers, lzx_truss and lzx_color /
-// lzx_label_propagation / lzx_modularity (lzx_communities.hip) and lzx_sweep_cut (lzx_sweep.hip).  Host side: the preconditions of such
+// lzx_label_propagation / lzx_modularity (lzx_communities.hip), lzx_sweep_cut (lzx_sweep.hip) and lzx_similarity (lzx_similarity.hip).  Host side: the preconditions of such
 // a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
 // the choice of lanes per row.  Device side: the idioms of their kernels over ascending rows and wavefront-aggregated queues.
 #pragma once

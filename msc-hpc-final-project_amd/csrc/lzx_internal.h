@@ -374,6 +374,9 @@ struct lzx_ctx {
     int64_t lpa_cap_opt = -1;          // test shape lpa_state_bytes: lzx_label_propagation treats a state larger than this as out of device memory
     int64_t sweep_long_opt = -1;       // test shape sweep_long_row: entries beyond which lzx_sweep_cut gives a row to its long-row launch (<= 0: 64 lanes-per-row)
     int64_t sweep_cap_opt = -1;        // test shape sweep_state_bytes: lzx_sweep_cut treats a state larger than this as out of device memory
+    int64_t sim_long_opt = -1;         // test shape sim_long_pair: entries of the shorter row beyond which lzx_similarity gives a pair to a workgroup of its own (<= 0: 64 lanes-per-pair)
+    int64_t sim_slice_opt = -1;        // test shape sim_slice: entries per slice of the shorter row of a pair that several workgroups share (<= 0: LZX_SIM_SLICE)
+    int64_t sim_cap_opt = -1;          // test shape sim_state_bytes: lzx_similarity treats a state larger than this as out of device memory
 };
 
 // ---- lzx_graph.hip ----

@@ -34,7 +34,11 @@
 // bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables), "sweep_long_row"
 // (lzx_sweep_cut: a row with more than this many entries is swept by the long-row launch, a workgroup per row; default 64 times the
 // lanes per row), "sweep_state_bytes" (lzx_sweep_cut takes a state larger than this many bytes as out of device memory, before the
-// device is touched).
+// device is touched), "sim_long_pair" (lzx_similarity: a pair whose shorter row has more than this many entries is intersected by a
+// workgroup of its own instead of a group of lanes; default 64 times the lanes per pair), "sim_slice" (such a pair whose shorter row
+// also has more than this many entries is dealt to one workgroup per slice of that many entries, 64 at the most, whose partials a
+// closing launch adds in slice order; default 16384), "sim_state_bytes" (lzx_similarity takes a state larger than this many bytes as
+// out of device memory, at either of its two allocations).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"

@@ -66,7 +66,7 @@ k_tri_orient(const u64 *row_ptr, const u32 *col_idx, const u32 *deg, u32 n, u64 
     if ((threadIdx.x & 63) == 0 && mx) atomicMax(kmax, mx);
 }
 
-static void orient_pass(u32 G, hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
+static inline void orient_pass(u32 G, hipStream_t st, const lzx_ctx *c, const u32 *deg, u64 *count, const u64 *orp, u32 *fill, u32 *kmax)
 {
     lzx_with_lanes<64>(G, [&](auto g) {
         hipLaunchKernelGGL(k_tri_orient<g>, dim3(lzx_row_grid(c->n, LZX_TRI_BLOCK / g)), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, deg,
