@@ -309,7 +309,8 @@ int lzx_probe_diag_f64(lzx_handle h, const double *T, uint32_t k, double *out);
  *             lzx_lanczos_run_steps gets LZX_ERR_STATE.  The resident single-vector basis (lzx_multout_f64 on it) and the batch
  *             state are left alone; the eigensolver's basis is freed before the call returns.
  *   breakdown beta_j <= 2^-40 * g (g = d_max under A, 2 d_max under L) ends a cycle early: its Ritz pairs are exact, and the
- *             next cycle starts from a fresh probe (seed, index 1 + earlier breakdowns) orthogonalised against the basis.
+ *             next cycle starts from a fresh probe orthogonalised against the basis: the probes of `seed` are taken in order from
+ *             index 1, and one that lies in the span of W and the kept columns (three vertices: every second one can) is passed over.
  *             A breakdown at which W and the cycle's columns span all of R^n (m + nw == n) leaves nothing to explore: the
  *             call ends there with the exact pairs.
  *   repeated  a single-vector Krylov method finds one vector per eigenspace from one start vector: further copies of a

@@ -20,8 +20,9 @@
 // (sym_eig below), the p wanted-most Ritz vectors are formed in place by k_eig_rotate (Q[:, 0:p] <- Q[:, 0:m] Y), q_m moves
 // to column p, and H restarts as diag(theta) with the coupling beta_{m-1} Y[m-1, i] in row p; the device's own projection
 // coefficients of step p supply the matching column.  A breakdown (beta_j <= 2^-40 * the Gershgorin bound) ends the cycle
-// early: its Ritz pairs are exact, and the next cycle starts from a fresh probe orthogonalised against what is kept -- unless
-// W and the cycle's columns already span R^n (m + nw == n), where the run ends.
+// early: its Ritz pairs are exact, and the next cycle starts from a fresh probe orthogonalised against what is kept (the next
+// probe of the seed that does not lie in that span) -- unless W and the cycle's columns already span R^n (m + nw == n), where
+// the run ends.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -38,6 +39,7 @@ static constexpr u32 LZX_EIG_CT = 8;          // basis columns per tile of the p
 static constexpr u32 LZX_EIG_ROT_ROWS = 64;   // rows one workgroup of k_eig_rotate stages in LDS
 static constexpr u32 LZX_EIG_MAX_M = 128;
 static constexpr u32 LZX_EIG_MAX_W = 8;
+static constexpr u32 LZX_EIG_FRESH_TRIES = 64;   // probes tried for a fresh start before the span of the basis counts as all there is
 typedef double nt_double2 __attribute__((ext_vector_type(2)));   // what __builtin_nontemporal_load takes for a 16-byte load
 
 __device__ __forceinline__ double2 load_nt2(const double *p)
@@ -495,7 +497,8 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
     const double stop = ldexp(g, -40);
     std::vector<double> Hh((size_t)m * m, 0.0), Hd((size_t)m * m), bh(m), T, th(m), Yfull((size_t)m * m), Yr;
     std::vector<u32> ord(m);
-    u32 k = 0, restarts = 0, breaks = 0, matvecs = 0, me = m, conv = 0;
+    u32 k = 0, restarts = 0, matvecs = 0, me = m, conv = 0;
+    u64 fresh = 0;   // probes used for fresh starts so far (probe 0 was the first start vector)
     double norm_est = 0.0, host_ms = 0.0, worst = 0.0;
     std::vector<double> res(m, 0.0);
     bool exhausted = false;
@@ -565,9 +568,11 @@ extern "C" int lzx_eigsh_f64(lzx_handle h, uint32_t nev, int which, uint32_t m, 
         LZX_HIP(hipEventElapsedTime(&a, r.ev[0], r.ev[1]));
         r.orth_ms += a;
         if (brk) {
-            ++breaks;
+            // W and the kept columns do not span R^n here (me + nw < n), but one +-1 probe can lie in their span by accident: with
+            // three vertices and the columns (1, -1, 0), (0, 0, 1) every second one does, and taking that for "nothing new to
+            // explore" returned 0 as the largest eigenvalue of an edge beside an isolated vertex.  So the following probes are tried.
             double bx = 0.0;
-            LZX_TRY(r.start(nw + p, nullptr, seed, breaks, &bx));
+            for (u32 t = 0; t < LZX_EIG_FRESH_TRIES && !(bx > 0.0); ++t) LZX_TRY(r.start(nw + p, nullptr, seed, ++fresh, &bx));
             if (!(bx > 0.0)) exhausted = true;   // nothing new to explore: the next cycle is the last
         }
         LZX_HIP(hipMemsetAsync(r.beta, 0, sizeof(double) * m, c->stream));
