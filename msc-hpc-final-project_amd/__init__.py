@@ -440,7 +440,8 @@ class Engine:
             self.operator = int(value)
 
     def shape(self, name: str) -> int:
-        """what shape the blocked tables took (test hook lzx_test_get_shape): gather_items_dealt / _drawn, gather_workgroups"""
+        """what shape the blocked tables took (test hook lzx_test_get_shape): gather_items_dealt / _drawn, gather_workgroups,
+        finish_launched / _deferrable, row_bands, pb_runs, pb_steps, scatter_units, ... (csrc/lzx_test_hooks.h)"""
         v = ctypes.c_int64()
         _check(self.L.lzx_test_get_shape(self.h, name.encode(), ctypes.byref(v)), f"lzx_test_get_shape({name})", self.L)
         return int(v.value)

@@ -249,7 +249,7 @@ extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
 }
 
 // what shape the blocked tables took (test hook, beside lzx_test_set_shape): "gather_items_dealt", "gather_items_drawn",
-// "gather_workgroups"
+// "gather_workgroups", ..., and the counts of the table builder: "row_bands", "pb_runs", "pb_steps", "scatter_units" (0 when blocking is off)
 extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value)
 {
     if (!c || !name || !value) LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: bad argument");
@@ -261,6 +261,10 @@ extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value
     else if (!strcmp(name, "start_vector_was_constant")) *value = c->x0_was_constant ? 1 : 0;
     else if (!strcmp(name, "finish_deferrable")) *value = c->pb && c->pb_defer_ok ? 1 : 0;
     else if (!strcmp(name, "finish_launched")) *value = c->pb && c->pb_finish_grid ? 1 : 0;
+    else if (!strcmp(name, "row_bands")) *value = c->pb ? c->pb_nr : 0;
+    else if (!strcmp(name, "pb_runs")) *value = c->pb ? c->pb_nruns : 0;
+    else if (!strcmp(name, "pb_steps")) *value = c->pb ? c->pbr_steps : 0;
+    else if (!strcmp(name, "scatter_units")) *value = c->pb ? c->pb_units : 0;
     else if (!strncmp(name, "placement_us_", 13) && name[13] >= '0' && name[13] <= '7' && !name[14]) *value = (int64_t)(c->place_ms[name[13] - '0'] * 1e3f);
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: unknown shape '%s'", name);
     return LZX_OK;

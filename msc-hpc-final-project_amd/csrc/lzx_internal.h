@@ -233,6 +233,7 @@ struct lzx_ctx {
     u64 pb_entries = 0;
     u32 pb_nr = 0;                     // row bands of LZX_PB_RB local rows
     u32 pb_units = 0;                  // scatter work units
+    u32 pb_nruns = 0;                  // (row band, column band) runs (reporting only: lzx_test_get_shape "pb_runs")
     uint16_t *d_pb_lcol = nullptr;     // [pb_entries] scatter order: column within its band
     u32 *d_pb_dst = nullptr;           // [pb_entries] scatter order: slot in d_pb_val (gather order)
     uint16_t *d_pb_lrow = nullptr;     // [pb_entries] gather order: slot in the band's y tile (row * rep + replica)

@@ -1250,6 +1250,7 @@ void lzx_pb_release(lzx_ctx *c)
     c->pb_entries = c->pb_values = c->pbr_entries = 0;
     c->pb_units = c->pb_units0 = c->pb_nr = c->pb_gather_grid = c->pb_n_items = c->pb_n_static = c->pb_n_dyn = c->pb_n_multi = c->pb_finish_grid = 0;
     c->pbr_steps = 0;
+    c->pb_nruns = 0;
 }
 
 // block partials of alpha the blocked passes leave
@@ -1543,7 +1544,7 @@ int pb_prepare_impl(lzx_ctx *c, const u32 *d_code, const u32 *d_old_of_local, co
     LZX_TRY(ar.get(&d_step_base, (u64)nsteps + 1));
     hipLaunchKernelGGL(k_pb_fill16, GRID(len + 8), d_prow, len + 8, (uint16_t)0xffffu);        // padding: no row
     hipLaunchKernelGGL(k_pb_fill16, GRID(len + 8), d_plcol, len + 8, (uint16_t)c->pb_cb);     // padding: the zero behind the staged band
-    hipLaunchKernelGGL(k_pb_fill16, GRID(nquads + 2), d_qcband, nquads + 2, (uint16_t)0xffffu);   // quads outside plain runs: no band
+    hipLaunchKernelGGL(k_pb_fill16, GRID(nquads + 2), d_qcband, nquads + 2, (uint16_t)0xffffu);   // quads without an entry of a plain run in their first slot (reduced runs' values, what run_align adds behind a plain run's last quad): no band
     if (nsteps) {
         hipLaunchKernelGGL(k_pbr_step_base, GRID(nsteps), d_step_run, d_estart, d_step_excl, d_vpos, nsteps, d_step_base);
         hipLaunchKernelGGL(k_pbr_rows, dim3(nsteps), dim3(64), 0, st, reinterpret_cast<const uint4 *>(d_rcode),
@@ -1913,6 +1914,7 @@ int pb_prepare_impl(lzx_ctx *c, const u32 *d_code, const u32 *d_old_of_local, co
     c->pbr_entries = red_entries;
     c->pb_values = len;
     c->pb_nr = nr;
+    c->pb_nruns = nruns;
     constexpr u32 waves_per_wg = LZX_PB_GATHER_BLOCK / 64;
     (void)waves_per_wg;
     // k_pb_finish: the rows of multi-item bands, then (only when some split row is covered by no gather item) a thread per split row

@@ -50,7 +50,9 @@ int lzx_test_set_shape(lzx_handle h, const char *name, int64_t value);
 // the gather pass), "gather_workgroups", "placement_tried" / "placement_kept" / "placement_us_<i>" (option placement_trials: candidates of
 // the value stream timed at the last hand-over, the one kept, the SpMV time of candidate i in microseconds), "start_vector_was_constant"
 // (the last prepared x0 was filled on the device instead of uploaded), "finish_launched" / "finish_deferrable" (the graph's blocked SpMV has a
-// k_pb_finish launch / the lazy loop may leave it out)
+// k_pb_finish launch / the lazy loop may leave it out), "row_bands" / "pb_runs" / "pb_steps" / "scatter_units" (what the builder of the
+// blocked tables counted: row bands, (row band, column band) runs, 512-entry steps of the reduced runs, scatter work units; read-only,
+// 0 when blocking is off -- tests/pb_model.py restates the rules they follow)
 #ifdef __cplusplus
 extern "C"
 #endif
