@@ -441,7 +441,9 @@ class Engine:
 
     def shape(self, name: str) -> int:
         """what shape the blocked tables took (test hook lzx_test_get_shape): gather_items_dealt / _drawn, gather_workgroups,
-        finish_launched / _deferrable, row_bands, pb_runs, pb_steps, scatter_units, ... (csrc/lzx_test_hooks.h)"""
+        finish_launched / _deferrable, row_bands, pb_runs, pb_steps, scatter_units, ...; and the body and split rows of either mode:
+        split_rows, split_items, body_slices, slices_wide / _w8 / _w4 / _w0, staged_workgroups, split_entries, body_entries,
+        staged_x_stride, live_rows (csrc/lzx_test_hooks.h)"""
         v = ctypes.c_int64()
         _check(self.L.lzx_test_get_shape(self.h, name.encode(), ctypes.byref(v)), f"lzx_test_get_shape({name})", self.L)
         return int(v.value)

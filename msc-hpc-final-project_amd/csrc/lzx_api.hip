@@ -249,7 +249,9 @@ extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
 }
 
 // what shape the blocked tables took (test hook, beside lzx_test_set_shape): "gather_items_dealt", "gather_items_drawn",
-// "gather_workgroups", ..., and the counts of the table builder: "row_bands", "pb_runs", "pb_steps", "scatter_units" (0 when blocking is off)
+// "gather_workgroups", ..., and the counts of the table builder: "row_bands", "pb_runs", "pb_steps", "scatter_units" (0 when blocking is off),
+// and of the builder of the body and the split rows: "split_rows", "split_items", "body_slices", "slices_wide" / "_w8" / "_w4" / "_w0",
+// "staged_workgroups", "split_entries", "body_entries", "staged_x_stride", "live_rows" (csrc/lzx_test_hooks.h)
 extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value)
 {
     if (!c || !name || !value) LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: bad argument");
@@ -265,6 +267,19 @@ extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value
     else if (!strcmp(name, "pb_runs")) *value = c->pb ? c->pb_nruns : 0;
     else if (!strcmp(name, "pb_steps")) *value = c->pb ? c->pbr_steps : 0;
     else if (!strcmp(name, "scatter_units")) *value = c->pb ? c->pb_units : 0;
+    // what lzx_graph_prepare counted for the sliced-ELL body and the split rows (steps 3 to 5; plain and blocked mode alike)
+    else if (!strcmp(name, "split_rows")) *value = c->n_long64;
+    else if (!strcmp(name, "split_items")) *value = c->n_items;
+    else if (!strcmp(name, "body_slices")) *value = c->n_slices;
+    else if (!strcmp(name, "slices_wide")) *value = c->ns_wide;
+    else if (!strcmp(name, "slices_w8")) *value = c->ns_w8;
+    else if (!strcmp(name, "slices_w4")) *value = c->ns_w4;
+    else if (!strcmp(name, "slices_w0")) *value = (int64_t)c->h_slice_w0.size();
+    else if (!strcmp(name, "staged_workgroups")) *value = c->spmv_grid;
+    else if (!strcmp(name, "split_entries")) *value = (int64_t)c->long_elems;
+    else if (!strcmp(name, "body_entries")) *value = (int64_t)c->sell_elems;
+    else if (!strcmp(name, "staged_x_stride")) *value = c->xs0;
+    else if (!strcmp(name, "live_rows")) *value = c->rows_live;
     else if (!strncmp(name, "placement_us_", 13) && name[13] >= '0' && name[13] <= '7' && !name[14]) *value = (int64_t)(c->place_ms[name[13] - '0'] * 1e3f);
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: unknown shape '%s'", name);
     return LZX_OK;

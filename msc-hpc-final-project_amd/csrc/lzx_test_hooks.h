@@ -5,7 +5,8 @@
 // "pb_dyn_share" (per cent of the gather pass left to its dynamic tail; 0 = every item dealt by the host), "pb_gather_grid" (at most this many gather workgroups),
 // "pb_gather_nt" (the gather pass's stream loads non-temporal 1 / cached 0, whatever the stream's size),
 // "pb_group" / "pb_group_force" (small row bands gathered one wavefront each), "narrow_slices", "tie_sort", "long_row",
-// "item_len", "exchange_at_world_1" (a 1-rank RCCL communicator runs the several-rank loop, collectives included),
+// "item_len", "spmv_wgs" (at most this many workgroups of k_spmv, and staged-columns workgroups of the blocked SpMV's shared launch; never
+// more than the default rule's ceiling of workgroups per CU and of one wavefront per slice or item), "exchange_at_world_1" (a 1-rank RCCL communicator runs the several-rank loop, collectives included),
 // "pb_carry_scan" (reduced steps: a row that spans lanes summed by the fixed-order cross-lane scan 1 / through LDS carry slots 0),
 // "isolated_rows" (0: rows without an edge updated elementwise instead of as one scalar recurrence), "unnormalised_basis" (0: the
 // resident basis holds q_j instead of u_j), "fuse_staged" (0: staged-columns kernel in a launch of its own; 1: behind the
@@ -52,7 +53,15 @@ int lzx_test_set_shape(lzx_handle h, const char *name, int64_t value);
 // (the last prepared x0 was filled on the device instead of uploaded), "finish_launched" / "finish_deferrable" (the graph's blocked SpMV has a
 // k_pb_finish launch / the lazy loop may leave it out), "row_bands" / "pb_runs" / "pb_steps" / "scatter_units" (what the builder of the
 // blocked tables counted: row bands, (row band, column band) runs, 512-entry steps of the reduced runs, scatter work units; read-only,
-// 0 when blocking is off -- tests/pb_model.py restates the rules they follow)
+// 0 when blocking is off -- tests/pb_model.py restates the rules they follow); and what lzx_graph_prepare (steps 3 to 5) counted for
+// the other half of the SpMV, the sliced-ELL body and the split rows that spmv_body takes, in plain and in blocked mode (read-only;
+// tests/sell_model.py restates the rules they follow): "split_rows" (rows handled as split rows: through the last row over the
+// threshold, rounded up to whole slices, at most the padded rows), "split_items" (work items of those rows), "body_slices" (64-row
+// slices behind them), "slices_wide" / "slices_w8" / "slices_w4" / "slices_w0" (slices the general loop takes, and those of 8, 4 and
+// 0 codes per row that the class loops take; without classes slices_wide == body_slices and the rest is 0), "staged_workgroups"
+// (workgroups of k_spmv, or staged-columns workgroups of the shared launch), "split_entries" / "body_entries" (padded codes in the two
+// tables; info's sell_padded is their sum), "staged_x_stride" (slice stride of chunk 0 of the exchange layout: the staged value of
+// degree rank r is read at (r % world) * stride + r / world), "live_rows" (this rank's rows with an edge, rounded up to whole slices)
 #ifdef __cplusplus
 extern "C"
 #endif
