@@ -443,7 +443,8 @@ class Engine:
         """what shape the blocked tables took (test hook lzx_test_get_shape): gather_items_dealt / _drawn, gather_workgroups,
         finish_launched / _deferrable, row_bands, pb_runs, pb_steps, scatter_units, ...; and the body and split rows of either mode:
         split_rows, split_items, body_slices, slices_wide / _w8 / _w4 / _w0, staged_workgroups, split_entries, body_entries,
-        staged_x_stride, live_rows (csrc/lzx_test_hooks.h)"""
+        staged_x_stride, live_rows; and the batched path's work list, 0 until its first call on the graph: multi_chunk,
+        multi_work_items, multi_split_rows, multi_chunk_slots, multi_row_segments, multi_vector_grid (csrc/lzx_test_hooks.h)"""
         v = ctypes.c_int64()
         _check(self.L.lzx_test_get_shape(self.h, name.encode(), ctypes.byref(v)), f"lzx_test_get_shape({name})", self.L)
         return int(v.value)

@@ -280,6 +280,9 @@ extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value
     else if (!strcmp(name, "body_entries")) *value = (int64_t)c->sell_elems;
     else if (!strcmp(name, "staged_x_stride")) *value = c->xs0;
     else if (!strcmp(name, "live_rows")) *value = c->rows_live;
+    // the batched path's work list (lzx_multi.hip): "multi_chunk", "multi_work_items", "multi_split_rows", "multi_chunk_slots",
+    // "multi_row_segments", "multi_vector_grid"
+    else if (lzx_multi_shape(c, name, value)) {}
     else if (!strncmp(name, "placement_us_", 13) && name[13] >= '0' && name[13] <= '7' && !name[14]) *value = (int64_t)(c->place_ms[name[13] - '0'] * 1e3f);
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: unknown shape '%s'", name);
     return LZX_OK;

@@ -387,6 +387,8 @@ int lzx_graph_prepare(lzx_ctx *c);   // builds this rank's share from d_row_ptr/
 // ---- lzx_multi.hip ----
 // with_tables: the per-graph work list goes too (a new graph, lzx_destroy); otherwise only the batch basis and work vectors
 void lzx_multi_free(lzx_ctx *c, bool with_tables);
+// the "multi_*" names of lzx_test_get_shape (csrc/lzx_test_hooks.h): false when `name` is none of them; 0 until the tables exist
+bool lzx_multi_shape(const lzx_ctx *c, const char *name, int64_t *value);
 
 // ---- lzx_eig.hip: classical Gram-Schmidt twice against the columns of a block Q (stride ldq, zero tails), shared by the
 // eigensolver and the shifted solver (lzx_solve.hip) ----

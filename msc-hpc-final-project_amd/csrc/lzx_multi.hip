@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "lzx_internal.h"
@@ -340,6 +341,23 @@ int lzx_multi_build_tables(lzx_ctx *c)
     LZX_HIP(hipMemcpy(m->d_run_split, run_split.data(), sizeof(u32) * run_split.size(), hipMemcpyHostToDevice));
     m->chunk = L;
     return LZX_OK;
+}
+
+// What the builder above counted, read-only, for lzx_test_get_shape (tests/multi_model.py restates the rules): every name is 0
+// until the tables exist, that is until the first batched call on the graph.
+bool lzx_multi_shape(const lzx_ctx *c, const char *name, int64_t *value)
+{
+    const lzx_multi_state *m = c->multi;
+    const bool built = m && m->d_wl;
+    if (!strcmp(name, "multi_chunk")) *value = built ? m->chunk : 0;
+    else if (!strcmp(name, "multi_work_items")) *value = built ? (int64_t)m->n_wl : 0;
+    else if (!strcmp(name, "multi_split_rows")) *value = built ? m->n_split : 0;
+    else if (!strcmp(name, "multi_chunk_slots")) *value = built ? m->n_parts : 0;
+    else if (!strcmp(name, "multi_row_segments")) *value = built ? m->n_seg : 0;
+    // the grid of k_multi_update and of k_multi_alpha's launch
+    else if (!strcmp(name, "multi_vector_grid")) *value = built ? std::min<u32>(std::max<u32>(m->n_seg, 1), (u32)c->cu_count * 4) : 0;
+    else return false;
+    return true;
 }
 
 // the work vectors of width B; need_x: the second one too (packing, unpacking -- a probe run starts on the device without it)

@@ -61,7 +61,15 @@ int lzx_test_set_shape(lzx_handle h, const char *name, int64_t value);
 // 0 codes per row that the class loops take; without classes slices_wide == body_slices and the rest is 0), "staged_workgroups"
 // (workgroups of k_spmv, or staged-columns workgroups of the shared launch), "split_entries" / "body_entries" (padded codes in the two
 // tables; info's sell_padded is their sum), "staged_x_stride" (slice stride of chunk 0 of the exchange layout: the staged value of
-// degree rank r is read at (r % world) * stride + r / world), "live_rows" (this rank's rows with an edge, rounded up to whole slices)
+// degree rank r is read at (r % world) * stride + r / world), "live_rows" (this rank's rows with an edge, rounded up to whole slices);
+// and what lzx_multi_build_tables counted for the batched path's work list (read-only; each reads 0 until the tables exist, that is
+// until the first batched call on the graph -- lzx_spmm_f64, lzx_lanczos_multi_f64, the probe entries, lzx_solve_multi_f64,
+// lzx_bfs_multi, lzx_betweenness_f64; tests/multi_model.py restates the rules they follow): "multi_chunk" (the L the list was built
+// with: multi_row_chunk, or 2048), "multi_work_items" (entries of the work list, one per unsplit row and per chunk of a split row,
+// padded to a multiple of 32), "multi_split_rows" (rows of more than L entries), "multi_chunk_slots" (their chunks: one slot of
+// chunk totals each), "multi_row_segments" (2048-row segments, one partial per column each: ceil(n / 2048)), "multi_vector_grid"
+// (min(max(multi_row_segments, 1), 4 x compute units): the workgroups of k_multi_update and of k_multi_alpha's launch, which
+// stride over the row segments)
 #ifdef __cplusplus
 extern "C"
 #endif
