@@ -26,7 +26,7 @@ SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
                  "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
                  "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes",
-                 "sweep_long_row", "sweep_state_bytes", "sim_long_pair", "sim_slice", "sim_state_bytes")
+                 "sweep_long_row", "sweep_state_bytes", "sim_long_pair", "sim_slice", "sim_state_bytes", "graph_lanes")
 
 LZX_COLOR_TIES_BY_ID = 1   # include/lzx.h: the colouring's order without the hash, (degree descending, id ascending)
 # include/lzx.h, the flags of lzx_sweep_cut: ascending keys; the key is score / degree; edge expansion instead of conductance

@@ -189,6 +189,9 @@ static const Option g_options[] = {
     {"sim_long_pair", &lzx_ctx::sim_long_opt, OPT_SHAPE},
     {"sim_slice", &lzx_ctx::sim_slice_opt, OPT_SHAPE},
     {"sim_state_bytes", &lzx_ctx::sim_cap_opt, OPT_SHAPE},
+    // every graph routine on the caller-order CSR: the lanes per row of its kernel templates, in place of the rule of
+    // lzx_lanes_per_row (lzx_graph_call.h) and capped at each call site's widest kernel; range-checked
+    {"graph_lanes", &lzx_ctx::graph_lanes_opt, OPT_SHAPE},
 #ifdef LZX_DEBUG_KNOBS
     {"wgs_per_cu", &lzx_ctx::wgs_per_cu_opt, OPT_KNOB},
     {"nt_index_loads", &lzx_ctx::nt_opt, OPT_KNOB},
@@ -244,6 +247,8 @@ extern "C" int lzx_test_set_shape(lzx_handle c, const char *name, int64_t value)
     if (c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "shapes must be set before the graph is handed over");
     const Option *o = find_option(name, OPT_SHAPE);
     if (!o) LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: unknown shape '%s'", name);
+    if (o->field == &lzx_ctx::graph_lanes_opt && value != -1 && value != 0 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64)
+        LZX_FAIL(LZX_ERR_ARG, "lzx_test_set_shape: graph_lanes must be 4, 8, 16, 32 or 64 (0, or -1 as every unset shape: the rule), got %lld", (long long)value);
     store_option(c, *o, value);
     return LZX_OK;
 }
@@ -283,6 +288,9 @@ extern "C" int lzx_test_get_shape(lzx_handle c, const char *name, int64_t *value
     // the batched path's work list (lzx_multi.hip): "multi_chunk", "multi_work_items", "multi_split_rows", "multi_chunk_slots",
     // "multi_row_segments", "multi_vector_grid"
     else if (lzx_multi_shape(c, name, value)) {}
+    // the lanes per row the last graph call ran (lzx_lanes_per_row, lzx_graph_call.h)
+    else if (!strcmp(name, "graph_lanes_rows")) *value = c->lanes_rows_ran;
+    else if (!strcmp(name, "graph_lanes_oriented")) *value = c->lanes_oriented_ran;
     else if (!strncmp(name, "placement_us_", 13) && name[13] >= '0' && name[13] <= '7' && !name[14]) *value = (int64_t)(c->place_ms[name[13] - '0'] * 1e3f);
     else LZX_FAIL(LZX_ERR_ARG, "lzx_test_get_shape: unknown shape '%s'", name);
     return LZX_OK;

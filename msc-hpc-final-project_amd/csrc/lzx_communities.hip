@@ -621,7 +621,7 @@ struct ColorResult {
 inline u64 even(u64 x) { return (x + 1) & ~1ull; }
 inline u64 class_bins(u32 n) { return even(3 * (u64)std::min<u32>(n, LZX_COLOR_CAP)); }
 inline u32 vertex_grid(u32 n) { return (n + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK; }
-inline u32 lanes_of(const lzx_ctx *c) { return lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32); }
+inline u32 lanes_of(lzx_ctx *c) { return lzx_lanes_per_row(c, c->nnz, 32); }
 
 // out[v] = the entries of row v that satisfy pred: both launches
 template <typename P>

@@ -194,7 +194,7 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // lanes per row: about half the mean degree of the rows that have an edge, so that a typical row is two loads per lane
-    const u32 G = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, c->nnz, 32);
     const u32 long_row = 64 * G;
     const u32 gb = (n + LZX_CC_BLOCK - 1) / LZX_CC_BLOCK;
 

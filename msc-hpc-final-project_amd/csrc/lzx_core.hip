@@ -167,7 +167,7 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
 
     // lanes per row of the window: about half the mean degree of the rows that have an edge.  Rows of more than 64 G entries
     // (256 ... 2048: more than 64 trips of a group) go to the long-row launch.
-    const u32 G = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, c->nnz, 32);
     const u32 long_row = c->core_long_opt > 0 ? (u32)std::min<int64_t>(c->core_long_opt, 0xffffffff) : 64 * G;
     const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_CORE_BLOCK), 1), LZX_CORE_SLICES);
     const u32 gb = (n + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK;

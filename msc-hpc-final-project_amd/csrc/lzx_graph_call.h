@@ -5,18 +5,21 @@
 // the choice of lanes per row.  Device side: the idioms of their kernels over ascending rows and wavefront-aggregated queues.
 #pragma once
 
+#include <algorithm>
 #include <type_traits>
 
 #include "lzx_internal.h"
 
-// one GPU, a graph, all of it on this handle; `what`: "<what the call does> on one GPU handle"
-inline int lzx_graph_call_check(const lzx_ctx *c, const char *fn, const char *what)
+// one GPU, a graph, all of it on this handle; `what`: "<what the call does> on one GPU handle".  A call that passes starts with
+// no lanes per row on record (lzx_lanes_per_row)
+inline int lzx_graph_call_check(lzx_ctx *c, const char *fn, const char *what)
 {
     if (!c) LZX_FAIL(LZX_ERR_ARG, "%s: null handle", fn);
     if (c->comm_kind != 0 || c->world > 1)
         LZX_FAIL(LZX_ERR_STATE, "%s: %s on one GPU handle; this handle is rank %d of a communicator of %d", fn, what, c->rank, c->world);
     if (!c->d_row_ptr) LZX_FAIL(LZX_ERR_STATE, "%s: no graph has been handed over", fn);
     if (c->sharded) LZX_FAIL(LZX_ERR_STATE, "%s: the graph came through the sharded hand-over -- no rank holds all of it", fn);
+    c->lanes_rows_ran = c->lanes_oriented_ran = 0;
     return LZX_OK;
 }
 
@@ -43,11 +46,22 @@ struct LzxGraphRun {
 // shape *_state_bytes; < 0: none) counts as out of device memory (lzx_solve.hip)
 int lzx_alloc_state(const char *fn, const char *what, int64_t cap, u64 state_bytes, u64 alloc_bytes, void **out);
 
-// lanes per row: about half the mean row length, so that a typical row is two loads per lane; 4 .. max_g
-inline u32 lzx_lanes_per_row(u64 mean, u32 max_g)
+// what a launch over G lanes per row walks: the caller-order rows, or the rows of the oriented copy (lzx_tri_orient.h)
+enum LzxLanesOver { LZX_OVER_ROWS, LZX_OVER_ORIENTED };
+
+// lanes per row of a graph call's launches over `entries` entries in the rows that have an edge: about half the mean row length,
+// so that a typical row is two loads per lane; 4 .. max_g, the widest instantiation of the kernels it is for.  The test shape
+// graph_lanes takes the rule's place (capped at max_g as well).  What it returns goes on record for lzx_test_get_shape
+// (graph_lanes_rows / graph_lanes_oriented): the widest of a call where its launches differ -- lzx_truss peels over
+// min(that, 32) lanes per edge.
+inline u32 lzx_lanes_per_row(lzx_ctx *c, u64 entries, u32 max_g, LzxLanesOver over = LZX_OVER_ROWS)
 {
+    const u64 mean = entries / std::max<u64>(c->n_active, 1);
     u32 G = 4;
     while (G < max_g && 2 * G <= mean) G *= 2;
+    if (c->graph_lanes_opt > 0) G = (u32)std::min<int64_t>(c->graph_lanes_opt, max_g);
+    u32 &ran = over == LZX_OVER_ORIENTED ? c->lanes_oriented_ran : c->lanes_rows_ran;
+    ran = std::max(ran, G);
     return G;
 }
 

@@ -378,6 +378,9 @@ struct lzx_ctx {
     int64_t sim_long_opt = -1;         // test shape sim_long_pair: entries of the shorter row beyond which lzx_similarity gives a pair to a workgroup of its own (<= 0: 64 lanes-per-pair)
     int64_t sim_slice_opt = -1;        // test shape sim_slice: entries per slice of the shorter row of a pair that several workgroups share (<= 0: LZX_SIM_SLICE)
     int64_t sim_cap_opt = -1;          // test shape sim_state_bytes: lzx_similarity treats a state larger than this as out of device memory
+    int64_t graph_lanes_opt = -1;      // test shape graph_lanes: 4 | 8 | 16 | 32 | 64 takes the place of the rule of lzx_lanes_per_row in every graph routine, capped at the call site's widest kernel (<= 0: the rule)
+    u32 lanes_rows_ran = 0;            // lzx_test_get_shape graph_lanes_rows: lanes per row of the last graph call's launches over caller-order rows (0: none yet)
+    u32 lanes_oriented_ran = 0;        // ... graph_lanes_oriented: of its launches over the oriented copy (0: the call has none)
 };
 
 // ---- lzx_graph.hip ----

@@ -410,7 +410,7 @@ extern "C" int lzx_similarity(lzx_handle c, uint64_t np64, const uint32_t *u, co
     for (hipEvent_t *e : {&run.ev0, &run.ev1, &run.ev2, &run.ev3}) LZX_HIP(hipEventCreate(e));
 
     // ---- preparation ----
-    const u32 G = lzx_lanes_per_row(nnz / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, nnz, 32);
     const u32 gb = (n + LZX_SIM_BLOCK - 1) / LZX_SIM_BLOCK;
     const u32 gp = (u32)(((u64)np + LZX_SIM_BLOCK - 1) / LZX_SIM_BLOCK);
     LZX_HIP(hipEventRecord(run.ev0, st));

@@ -383,7 +383,7 @@ extern "C" int lzx_sweep_cut(lzx_handle c, uint32_t ns, const double *scores, ui
     LZX_HIP(hipEventRecord(run.ev1, st));
 
     // ---- the edge sweep ----
-    const u32 G = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, c->nnz, 32);
     const u32 long_row = c->sweep_long_opt > 0 ? (u32)std::min<int64_t>(c->sweep_long_opt, 0xffffffff) : 64 * G;
     const bool long_rows = c->max_degree > long_row;
     if (long_rows) {

@@ -39,7 +39,12 @@
 // workgroup of its own instead of a group of lanes; default 64 times the lanes per pair), "sim_slice" (such a pair whose shorter row
 // also has more than this many entries is dealt to one workgroup per slice of that many entries, 64 at the most, whose partials a
 // closing launch adds in slice order; default 16384), "sim_state_bytes" (lzx_similarity takes a state larger than this many bytes as
-// out of device memory, at either of its two allocations).
+// out of device memory, at either of its two allocations), "graph_lanes" (lzx_components, lzx_triangles, lzx_core_numbers, lzx_truss,
+// lzx_color, lzx_label_propagation, lzx_modularity, lzx_sweep_cut and lzx_similarity: 4 | 8 | 16 | 32 | 64 lanes per row in every kernel
+// template they launch, in place of the rule on the mean row length and capped at the widest instantiation of each launch -- 64 for the
+// orientation pass and lzx_truss's per-row passes, 32 elsewhere; 0, or -1 like every unset shape: the rule; any other value is refused
+// with LZX_ERR_ARG.  The defaults of "core_long_row", "truss_long_row", "color_long_row", "sweep_long_row", "sim_long_pair" and
+// lzx_components's split, 64 times the lanes, follow the forced width).
 #pragma once
 #include <stdint.h>
 #include "lzx.h"
@@ -69,7 +74,10 @@ int lzx_test_set_shape(lzx_handle h, const char *name, int64_t value);
 // padded to a multiple of 32), "multi_split_rows" (rows of more than L entries), "multi_chunk_slots" (their chunks: one slot of
 // chunk totals each), "multi_row_segments" (2048-row segments, one partial per column each: ceil(n / 2048)), "multi_vector_grid"
 // (min(max(multi_row_segments, 1), 4 x compute units): the workgroups of k_multi_update and of k_multi_alpha's launch, which
-// stride over the row segments)
+// stride over the row segments); and the lanes per row the last graph call on the handle ran (read-only; 0 before the first):
+// "graph_lanes_rows" (of its launches over the caller-order rows; where they differ the widest -- lzx_truss peels over min(that, 32)
+// lanes per edge), "graph_lanes_oriented" (of its launches over the oriented copy: the counting kernel of lzx_triangles, the support
+// kernel of lzx_truss; 0 for a call without an oriented copy or without an edge in it)
 #ifdef __cplusplus
 extern "C"
 #endif

@@ -265,7 +265,7 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // ---- the oriented copy ----
-    const u32 Go = lzx_lanes_per_row(c->nnz / std::max<u64>(c->n_active, 1), 64);
+    const u32 Go = lzx_lanes_per_row(c, c->nnz, 64);
     const u32 gb = (n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK;
     LZX_HIP(hipEventRecord(run.ev0, st));
     LZX_HIP(hipMemsetAsync(d_kmax, 0, 2 * sizeof(u32), st));
@@ -296,7 +296,7 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     LZX_HIP(hipEventElapsedTime(&orient_ms, run.ev0, run.ev1));
 
     // ---- counting: lanes per row about half the mean oriented degree ----
-    const u32 G = lzx_lanes_per_row(m / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, m, 32, LZX_OVER_ORIENTED);
     const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
     const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
     LZX_HIP(hipEventRecord(run.ev0, st));

@@ -452,7 +452,7 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // ---- the oriented copy: lzx_triangles' ----
-    const u32 Go = lzx_lanes_per_row(nnz / std::max<u64>(c->n_active, 1), 64);
+    const u32 Go = lzx_lanes_per_row(c, nnz, 64);
     const u32 gb = (n + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK;
     LZX_HIP(hipEventRecord(run.ev0, st));
     LZX_HIP(hipMemsetAsync(d_words, 0, 4 * sizeof(u32), st));
@@ -499,7 +499,7 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     // ---- support: lanes per row about half the mean oriented degree, the split of lzx_triangles at a long list ----
     u64 sup_sum = 0, sup_max = 0;
     if (m) {
-        const u32 G = lzx_lanes_per_row(m / std::max<u64>(c->n_active, 1), 32);
+        const u32 G = lzx_lanes_per_row(c, m, 32, LZX_OVER_ORIENTED);
         const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
         const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
         lzx_with_lanes<32>(G, [&](auto g) {
@@ -539,7 +539,7 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
 
     // ---- the peel.  Lanes per edge: about half the mean row length.  Edges whose shorter row has more than 64 G entries go to the
     // long-row launch, which runs only when the graph has such a row ----
-    const u32 G = lzx_lanes_per_row(nnz / std::max<u64>(c->n_active, 1), 32);
+    const u32 G = lzx_lanes_per_row(c, nnz, 32);
     const u32 long_row = c->truss_long_opt > 0 ? (u32)std::min<int64_t>(c->truss_long_opt, 0xffffffff) : 64 * G;
     const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_TRUSS_BLOCK), 1), LZX_TRUSS_SLICES);
     TrussPeel p = {c->d_row_ptr, c->d_col_idx, d_eid, d_src, d_oci, d_sup, d_mark, d_truss, d_queue, d_counters, m, 0, 0, 0, 0, long_row};
