@@ -565,8 +565,46 @@ int lzx_set_graph_induced(lzx_handle dst, lzx_handle src, const uint8_t *keep /*
  *             (lzx_betweenness_f64), a source >= n (the message names its index and value).  LZX_ERR_STATE: no graph, a handle
  *             with a communicator, a graph from a sharded hand-over over several ranks.  LZX_ERR_NOMEM: the message states the
  *             bytes.  The checks that need no device come first.
- *   limits    one GPU handle; unweighted, undirected graphs; no edge betweenness, no endpoints; no push / direction-optimising
- *             search (a small frontier still costs a sweep over the unreached rows). */
+ *   limits    one GPU handle; unweighted, undirected graphs; no push / direction-optimising
+ *             search (a small frontier still costs a sweep over the unreached rows).
+ *
+ * lzx_brandes_f64: the same Brandes pass with its two other outputs, networkx's edge_betweenness_centrality and
+ * betweenness_centrality(endpoints=True).  bc and ebc may each be NULL, not both.
+ *   ebc       one value per stored entry of the caller-order CSR, in the positions of lzx_get_graph_csr's col_idx.  For the entry
+ *             e = (u, w): ebc[e] = the sum over the sources s, in the caller's order, of c_s(u, w), with
+ *             c_s(u, w) = sigma_s[u] * g_s[w] if dist_s[u] >= 0 and dist_s[w] = dist_s[u] + 1, sigma_s[w] * g_s[u] if
+ *             dist_s[w] >= 0 and dist_s[u] = dist_s[w] + 1, and +0 otherwise (an edge inside one level, an unreached endpoint, a
+ *             diagonal entry); g = (1 + delta) / sigma as above.  Each non-zero term is one rounded product, networkx's
+ *             c = sigma[v] * coeff.  Raw: no 1/2, no normalisation; with every vertex a source it is twice networkx's
+ *             unnormalised edge betweenness.  Both copies of an edge carry the same bits (they form the same product), a diagonal
+ *             entry carries 0, a source listed twice counts twice.
+ *   bc        flags = 0: lzx_betweenness_f64's bc, bit for bit, whether ebc is asked for or not.  With LZX_BRANDES_ENDPOINTS:
+ *             bc[v] = bc_plain[v] + (double)cnt[v], one addition after the last batch, where the 64-bit integer cnt[v] counts, on
+ *             the device, + 1 for every source s != v that reaches v (networkx's delta[w] + 1) and + reached_s - 1 every time v is
+ *             itself a source (networkx's betweenness[s] += len(S) - 1).  The flag does not change ebc.
+ *   method    the forward pass of lzx_betweenness_f64.  When ebc is wanted the backward pass keeps sigma: g goes to the third
+ *             [n][B] array as above, delta to a fourth one, and only when bc is wanted too (without ebc the call runs
+ *             lzx_betweenness_f64's kernels).  After the last backward level of a batch one edge pass walks the caller-order rows,
+ *             4 .. 32 lanes per row by the rule of the other graph routines (G lanes; a row of more than 64 G entries gets a whole
+ *             workgroup); every stored entry belongs to one lane, which does
+ *             x = ebc[e]; x += c_c(u, w) for the columns c = 0, 1, ... of the batch in ascending order; ebc[e] = x.  The lane
+ *             keeps its row's dist / sigma / g in registers, reads the neighbour's dist line, and fetches a sigma or g word of the
+ *             neighbour only for a column that meets one of the two conditions.  g of a source (level 0 has no sweep) and of an
+ *             unreached vertex is never formed and never read: the dist tests stand in front of every read.  No floating-point
+ *             atomic, no search for the mirror entry.
+ *   bits      identical arguments give identical bits, for every number of lanes per row.  ebc of a call with sources
+ *             (s_1 ... s_m) equals, bit for bit, ((ebc(s_1) + ebc(s_2)) + ...) of m single-source calls added left to right,
+ *             wherever the batch boundaries fall: bc's contract.
+ *   state     as lzx_betweenness_f64: nothing of the handle's other state is voided or changed; only the batched path's work list
+ *             may be added.  The call's arena holds lzx_betweenness_f64's bytes (dist, sigma, g, the split rows' totals, and
+ *             bc[n] when bc is wanted), + 8 B n for delta when bc and ebc are both wanted, + 8 nnz for ebc (zeroed at the start),
+ *             + 8 n for cnt with the flag: one allocation under the cap of the test shape bfs_state_bytes, freed on every path.
+ *   info      (or NULL) as lzx_bfs_info, and edge_ms: the device event time of the per-batch edge passes alone (sweeps does not
+ *             count them).
+ *   errors    LZX_ERR_ARG: null handle, ns == 0, bc and ebc both NULL, an unknown flag bit, LZX_BRANDES_ENDPOINTS with null bc,
+ *             null sources with ns != n, a source >= n (the message names its index and value).  LZX_ERR_STATE and LZX_ERR_NOMEM
+ *             as for lzx_betweenness_f64.  The checks that need no device come first.
+ *   limits    as above; both triangles of ebc are always returned. */
 typedef struct lzx_bfs_info {
     uint32_t ns, batches;      /* sources, batches of <= 16 */
     uint32_t max_level;        /* largest eccentricity among the sources */
@@ -582,6 +620,18 @@ int lzx_bfs_multi(lzx_handle h, uint32_t ns, const uint32_t *sources,
 int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NULL: every vertex, ns must equal n */,
                         double *bc /* [n], caller order: sum over the sources s of Brandes' dependency delta_s(v), v != s */,
                         lzx_bfs_info *info /* or NULL */);
+#define LZX_BRANDES_ENDPOINTS 1
+typedef struct lzx_brandes_info {
+    uint32_t ns, batches;      /* as lzx_bfs_info */
+    uint32_t max_level;
+    uint32_t sweeps;
+    double   loop_ms, sweep_ms;
+    double   edge_ms;          /* device event time of the per-batch edge passes alone */
+} lzx_brandes_info;
+int lzx_brandes_f64(lzx_handle h, uint32_t ns, const uint32_t *sources /* NULL: every vertex, ns must equal n */,
+                    uint32_t flags /* 0 or LZX_BRANDES_ENDPOINTS */, double *bc /* [n] or NULL */,
+                    double *ebc /* [nnz] or NULL: one value per stored entry of lzx_get_graph_csr's col_idx */,
+                    lzx_brandes_info *info /* or NULL */);
 
 /* ---- triangles and clustering ---------------------------------------------------------------------
  * lzx_triangles: the local structure of the handle's graph read as undirected and unweighted -- what networkx.triangles,

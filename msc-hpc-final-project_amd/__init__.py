@@ -28,6 +28,7 @@ SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_
                  "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes",
                  "sweep_long_row", "sweep_state_bytes", "sim_long_pair", "sim_slice", "sim_state_bytes", "graph_lanes")
 
+LZX_BRANDES_ENDPOINTS = 1  # include/lzx.h: lzx_brandes_f64's flag, bc counts the endpoints of every path too
 LZX_COLOR_TIES_BY_ID = 1   # include/lzx.h: the colouring's order without the hash, (degree descending, id ascending)
 # include/lzx.h, the flags of lzx_sweep_cut: ascending keys; the key is score / degree; edge expansion instead of conductance
 LZX_SWEEP_ASCENDING, LZX_SWEEP_PER_DEGREE, LZX_SWEEP_EXPANSION = 1, 2, 4
@@ -120,6 +121,14 @@ class LzxComponentsInfo(ctypes.Structure):
 class LzxBfsInfo(ctypes.Structure):
     _fields_ = [("ns", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("max_level", ctypes.c_uint32), ("sweeps", ctypes.c_uint32),
                 ("loop_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LzxBrandesInfo(ctypes.Structure):
+    _fields_ = [("ns", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("max_level", ctypes.c_uint32), ("sweeps", ctypes.c_uint32),
+                ("loop_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double), ("edge_ms", ctypes.c_double)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -263,6 +272,7 @@ SYMBOLS = [
     ("lzx_set_graph_induced", ctypes.c_int, [_h, _h, _u8p, _u32p, _u64p]),
     ("lzx_bfs_multi", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _i32p, _f64p, _u64p, _u64p, _f64p, _u32p, ctypes.POINTER(LzxBfsInfo)]),
     ("lzx_betweenness_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, _f64p, ctypes.POINTER(LzxBfsInfo)]),
+    ("lzx_brandes_f64", ctypes.c_int, [_h, ctypes.c_uint32, _u32p, ctypes.c_uint32, _f64p, _f64p, ctypes.POINTER(LzxBrandesInfo)]),
     ("lzx_triangles", ctypes.c_int, [_h, _u64p, _f64p, ctypes.POINTER(LzxTrianglesInfo)]),
     ("lzx_core_numbers", ctypes.c_int, [_h, _u32p, _u32p, ctypes.POINTER(LzxCoreInfo)]),
     ("lzx_truss", ctypes.c_int, [_h, _u32p, _u32p, _u32p, _u32p, ctypes.POINTER(LzxTrussInfo)]),
@@ -998,7 +1008,7 @@ class Engine:
             W[i, members] = 1.0 / np.sqrt(np.count_nonzero(members))
         return W
 
-    # ---- path-based centralities (include/lzx.h: lzx_bfs_multi, lzx_betweenness_f64) ----
+    # ---- path-based centralities (include/lzx.h: lzx_bfs_multi, lzx_betweenness_f64, lzx_brandes_f64; DESIGN.md sections 17, 24) ----
     def _sources(self, sources, what):
         """(uint32 array or None for every vertex, ns)"""
         if sources is None:
@@ -1054,22 +1064,66 @@ class Engine:
                "lzx_betweenness_f64", self.L)
         return bc, info.as_dict()
 
-    def betweenness(self, k=None, sources=None, normalized: bool = True, seed: int = 0):
-        """Betweenness centrality as networkx.betweenness_centrality defines it on an undirected graph without endpoints.
-        sources=None, k=None: exact; k: k distinct sources sampled with numpy.random.default_rng(seed); explicit `sources` are
-        scaled as a sample of len(sources).  Scaling (networkx 3.4's _rescale): 1 / ((n - 1)(n - 2)) when normalised and n > 2,
-        0.5 when not, both times n / k when sampling."""
+    def brandes_raw(self, sources=None, want_bc: bool = True, want_edges: bool = True, endpoints: bool = False):
+        """(bc, ebc, info) of lzx_brandes_f64, unscaled: bc (n,) the sum over the sources (None: every vertex) of Brandes'
+        dependencies -- with endpoints=True plus the endpoints' count --, ebc one value per stored entry of get_graph_csr()'s
+        col_idx (both copies of an edge carry its number; a diagonal entry carries 0).  Each is None when not wanted, and then
+        it does not leave the device.  info = the lzx_brandes_info fields."""
+        src, ns = self._sources(sources, "brandes")
+        bc = np.empty(max(self.n, 1)) if want_bc else None
+        nnz = int(self.info()["nnz"]) if want_edges else 0
+        ebc = np.zeros(max(nnz, 1)) if want_edges else None
+        info = LzxBrandesInfo()
+        _check(self.L.lzx_brandes_f64(self.h, ns, None if src is None else _p(src, _u32p), LZX_BRANDES_ENDPOINTS if endpoints else 0,
+                                      None if bc is None else _p(bc, _f64p), None if ebc is None else _p(ebc, _f64p), ctypes.byref(info)),
+               "lzx_brandes_f64", self.L)
+        return None if bc is None else bc[:self.n], None if ebc is None else ebc[:nnz], info.as_dict()
+
+    def _sampled_sources(self, what, k, sources, seed):
+        """the sources of a sampled centrality: `sources`, or k distinct ones drawn with numpy.random.default_rng(seed)"""
         n = self.n
         if sources is not None and k is not None:
-            raise ValueError("betweenness: give k or sources, not both")
+            raise ValueError(f"{what}: give k or sources, not both")
         if k is not None:
             if not 1 <= k <= n:
-                raise ValueError(f"betweenness: k must lie in [1, {n}]")
+                raise ValueError(f"{what}: k must lie in [1, {n}]")
             sources = np.random.default_rng(seed).choice(n, size=k, replace=False)
-        bc, _ = self.betweenness_raw(sources)
+        return sources
+
+    def edge_betweenness(self, k=None, sources=None, normalized: bool = True, seed: int = 0):
+        """Edge betweenness centrality as networkx.edge_betweenness_centrality defines it on an undirected graph: a scipy CSR
+        matrix (float64) over the handle's pattern, symmetric; a diagonal entry holds 0.  k and sources as in betweenness.
+        Scaling (networkx 3.4's _rescale_e): 1 / (n (n - 1)) when normalised and n > 1, 0.5 when not, both times n / k when
+        sampling."""
+        n = self.n
+        sources = self._sampled_sources("edge_betweenness", k, sources, seed)
+        ebc = self.brandes_raw(sources, want_bc=False)[1]
         ks = None if sources is None else len(np.atleast_1d(sources))
         if normalized:
-            scale = 1.0 / ((n - 1) * (n - 2)) if n > 2 else None
+            scale = 1.0 / (n * (n - 1)) if n > 1 else None
+        else:
+            scale = 0.5
+        if scale is not None:
+            if ks is not None:
+                scale = scale * n / ks
+            ebc = ebc * scale
+        return self._edge_matrix(ebc)
+
+    def betweenness(self, k=None, sources=None, normalized: bool = True, seed: int = 0, endpoints: bool = False):
+        """Betweenness centrality as networkx.betweenness_centrality defines it on an undirected graph, without endpoints or
+        (endpoints=True, through lzx_brandes_f64) with them.
+        sources=None, k=None: exact; k: k distinct sources sampled with numpy.random.default_rng(seed); explicit `sources` are
+        scaled as a sample of len(sources).  Scaling (networkx 3.4's _rescale): 1 / ((n - 1)(n - 2)) when normalised and n > 2
+        -- with endpoints 1 / (n (n - 1)) when n >= 2 --, 0.5 when not, both times n / k when sampling."""
+        n = self.n
+        sources = self._sampled_sources("betweenness", k, sources, seed)
+        bc = self.brandes_raw(sources, want_edges=False, endpoints=True)[0] if endpoints else self.betweenness_raw(sources)[0]
+        ks = None if sources is None else len(np.atleast_1d(sources))
+        if normalized:
+            if endpoints:
+                scale = 1.0 / (n * (n - 1)) if n >= 2 else None
+            else:
+                scale = 1.0 / ((n - 1) * (n - 2)) if n > 2 else None
         else:
             scale = 0.5
         if scale is not None:

@@ -1,5 +1,5 @@
 // lzx_paths.hip -- path-based centralities on the device: breadth-first search from many sources at once, and Brandes'
-// betweenness on top of it (include/lzx.h: lzx_bfs_multi, lzx_betweenness_f64).
+// betweenness on top of it (include/lzx.h: lzx_bfs_multi, lzx_betweenness_f64, lzx_brandes_f64; DESIGN.md sections 17 and 24).
 //
 // Up to 16 sources share every sweep over the edges: the per-vertex state is laid out [n][B] (B = the batch width padded to
 // 2, 4, 8 or 16) like the batched path's vectors, and the sweeps walk the batched path's work list (lzx_multi_shared.h: whole
@@ -25,6 +25,11 @@
 // k_paths_split.  Those shapes depend on the graph alone, there is no floating-point atomic, and the only racing accesses are
 // the forward pass's dist words, whose two possible values (-1, d) both fail the reader's test: results are the same bits in
 // every run and for every composition of the batch.
+//
+// lzx_brandes_f64 adds edge betweenness and the endpoints to the same pass.  With ebc wanted the backward pass keeps sigma
+// (delta goes to a fourth [n][B] array, and only when bc is wanted too), and after the last backward level of a batch one edge
+// pass (k_paths_edges) adds, per stored entry of the caller-order CSR, sigma * g over the batch's columns in ascending order.  The
+// endpoints are a 64-bit count per vertex (k_paths_endpoints), added to bc once, after the last batch.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -61,15 +66,20 @@ __global__ void k_paths_part_rows(const u32 *split_row, const u32 *split_first, 
     for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) part_row[p] = row;
 }
 
+// the three forms of a level: the forward search, the backward recurrence that puts delta in sigma's place (lzx_betweenness_f64),
+// and the one that keeps sigma for the edge pass (lzx_brandes_f64): delta goes to a fourth array, and only if bc is wanted
+enum : int { PATHS_FORWARD = 0, PATHS_BACK = 1, PATHS_BACK_KEEP = 2 };
+
 // what a complete row sum s does to (row, column) i; forward: 1 if the vertex was reached at this level
-template <bool BACK>
-__device__ __forceinline__ u32 paths_epilogue(u64 i, double s, int32_t d, int32_t *dist, double *sigma, double *g)
+template <int MODE>
+__device__ __forceinline__ u32 paths_epilogue(u64 i, double s, int32_t d, int32_t *dist, double *sigma, double *g, double *delta_out)
 {
-    if (BACK) {
+    if (MODE != PATHS_FORWARD) {
         const double sg = sigma[i];
         const double delta = sg * s;
         g[i] = (1.0 + delta) / sg;
-        sigma[i] = delta;
+        if (MODE == PATHS_BACK) sigma[i] = delta;
+        else if (delta_out) delta_out[i] = delta;
         return 0;
     }
     if (!(s > 0.0)) return 0;
@@ -90,11 +100,12 @@ __device__ __forceinline__ void paths_count(u32 v, u32 *reached)
 
 // One level of either pass over the work list: lane (segment, column) of a wavefront.  want_row / want: -1 / d - 1 forward,
 // d / d + 1 backward.  A chunk of a split row leaves its total in part (closed by k_paths_split).
-template <u32 B, bool BACK>
+template <u32 B, int MODE>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK)
 k_paths_sweep(const uint4 *__restrict__ wl, u64 n_waves, const u32 *__restrict__ col, const u32 *__restrict__ part_row, int32_t *dist,
-              double *sigma, double *g, double *part, u32 b, int32_t d, u32 *reached)
+              double *sigma, double *g, double *part, u32 b, int32_t d, u32 *reached, double *delta_out)
 {
+    constexpr bool BACK = MODE != PATHS_FORWARD;
     constexpr u32 G = 64 / B;
     const u64 w = (u64)blockIdx.x * (LZX_MULTI_BLOCK / 64) + (threadIdx.x >> 6);
     if (w >= n_waves) return;   // (the whole wavefront)
@@ -132,17 +143,18 @@ k_paths_sweep(const uint4 *__restrict__ wl, u64 n_waves, const u32 *__restrict__
             if (dist[o] == want) acc += X[o];
         }
         if (chunk) part[(u64)slot * B + c] = acc;
-        else newly = paths_epilogue<BACK>(at, acc, d, dist, sigma, g);
+        else newly = paths_epilogue<MODE>(at, acc, d, dist, sigma, g, delta_out);
     }
     if (!BACK) paths_count<B>(newly, reached);
 }
 
 // split rows: the chunk totals added in chunk order, then the same epilogue; thread (split row, column)
-template <u32 B, bool BACK>
+template <u32 B, int MODE>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK)
 k_paths_split(const double *part, const u32 *__restrict__ split_row, const u32 *__restrict__ split_first, u32 n_split, int32_t *dist,
-              double *sigma, double *g, u32 b, int32_t d, u32 *reached)
+              double *sigma, double *g, u32 b, int32_t d, u32 *reached, double *delta_out)
 {
+    constexpr bool BACK = MODE != PATHS_FORWARD;
     const u64 i = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
     const u64 ks = i / B;
     const u32 c = (u32)(i % B);
@@ -152,7 +164,7 @@ k_paths_split(const double *part, const u32 *__restrict__ split_row, const u32 *
         if (dist[at] == (BACK ? d : -1)) {
             double acc = 0.0;
             for (u32 p = split_first[ks]; p < split_first[ks + 1]; ++p) acc += part[(u64)p * B + c];
-            newly = paths_epilogue<BACK>(at, acc, d, dist, sigma, g);
+            newly = paths_epilogue<MODE>(at, acc, d, dist, sigma, g, delta_out);
         }
     }
     if (!BACK) paths_count<B>(newly, reached);
@@ -178,6 +190,145 @@ __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_paths_accumulate(const int3
     bc[r] = x;
 }
 
+// the endpoints' count of one batch: cnt[v] += 1 per column whose source reaches v from elsewhere, and reached - 1 per column
+// whose source v is (dist = 0 holds at the source alone)
+struct PathsReached { u64 v[LZX_BFS_BATCH]; };
+
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_paths_endpoints(const int32_t *__restrict__ dist, u64 n, u32 b, PathsReached reached, long long *cnt)
+{
+    const u64 r = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (r >= n) return;
+    long long x = cnt[r];
+#pragma unroll
+    for (u32 c = 0; c < B; ++c) {
+        const int32_t lv = dist[r * B + c];
+        if (c < b && lv > 0) x += 1;
+        else if (c < b && lv == 0) x += (long long)reached.v[c] - 1;
+    }
+    cnt[r] = x;
+}
+
+// bc[v] = bc[v] + (double)cnt[v]: the one addition of the endpoints, after the last batch
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_paths_add_endpoints(const long long *__restrict__ cnt, u64 n, double *bc)
+{
+    const u64 r = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    if (r < n) bc[r] = bc[r] + (double)cnt[r];
+}
+
+// The edge pass of one batch, after its last backward level: ebc[e] += c_c(u, w) for the columns c = 0, 1, ... in ascending
+// order, for every stored entry e = (u, w) of the caller-order CSR.  c_c(u, w) = sigma[u][c] * g[w][c] where w lies one level
+// below u, sigma[w][c] * g[u][c] where it lies one level above, +0 otherwise (x + 0 = x: such a column is skipped, and an entry
+// without a column is not written).  G lanes per row, 256 / G rows per workgroup, and a whole workgroup for a row of more than
+// 64 G entries; a lane keeps its row's B-wide dist / sigma / g in registers, reads the neighbour's dist line per entry, and of
+// its sigma / g lines only the one word per column a term needs.  g of a source and of an unreached vertex is never formed: the
+// dist tests stand in front of every use of a g.  Every entry belongs to one lane: no atomic, and a sum that depends on the
+// entry's own terms alone.
+// the B levels of one vertex, a line of 4 B bytes aligned to its size, in 16-byte loads
+template <u32 B>
+__device__ __forceinline__ void paths_load_levels(const int32_t *__restrict__ line, int32_t (&lv)[B])
+{
+    if constexpr (B == 2) {
+        const int2 t = *reinterpret_cast<const int2 *>(line);
+        lv[0] = t.x;
+        lv[1] = t.y;
+    } else {
+#pragma unroll
+        for (u32 k = 0; k < B / 4; ++k) {
+            const int4 t = reinterpret_cast<const int4 *>(line)[k];
+            lv[4 * k] = t.x;
+            lv[4 * k + 1] = t.y;
+            lv[4 * k + 2] = t.z;
+            lv[4 * k + 3] = t.w;
+        }
+    }
+}
+
+// One lane's share of row `row`: the entries first, first + step, ... < end
+template <u32 B>
+__device__ __forceinline__ void paths_edges_of_row(u64 row, u64 first, u64 end, u32 step, const u32 *__restrict__ col, const int32_t *__restrict__ dist,
+                                                   const double *__restrict__ sigma, const double *__restrict__ g, u32 b, double *ebc)
+{
+    if (first >= end) return;
+    int32_t du[B];
+    u32 seen = 0;
+    paths_load_levels<B>(dist + row * B, du);
+#pragma unroll
+    for (u32 c = 0; c < B; ++c)
+        if (c < b && du[c] >= 0) seen |= 1u << c;
+    if (!seen) return;   // no source of the batch reaches this row: all of its terms are +0
+    double su[B], gu[B];
+#pragma unroll
+    for (u32 c = 0; c < B; ++c) {
+        su[c] = sigma[row * B + c];
+        gu[c] = g[row * B + c];
+    }
+    for (u64 e = first; e < end; e += step) {
+        const u64 w = (u64)col[e] * B;
+        int32_t dw[B];
+        paths_load_levels<B>(dist + w, dw);
+        u32 down = 0, up = 0;
+#pragma unroll
+        for (u32 c = 0; c < B; ++c) {
+            if (c < b && du[c] >= 0 && dw[c] == du[c] + 1) down |= 1u << c;
+            if (c < b && dw[c] >= 0 && du[c] == dw[c] + 1) up |= 1u << c;
+        }
+        if (!(down | up)) continue;
+        double x = ebc[e];
+        // the neighbour's words of up to eight columns in flight, then their terms added in column order: a load inside the
+        // chain of additions would wait for the one before it
+        constexpr u32 CH = B < 8 ? B : 8;
+#pragma unroll
+        for (u32 c0 = 0; c0 < B; c0 += CH) {
+            double v[CH];
+#pragma unroll
+            for (u32 k = 0; k < CH; ++k) {
+                const u32 c = c0 + k;
+                const double *from = ((down >> c) & 1u) ? g : sigma;
+                v[k] = (((down | up) >> c) & 1u) ? from[w + c] : 0.0;
+            }
+#pragma unroll
+            for (u32 k = 0; k < CH; ++k) {
+                const u32 c = c0 + k;
+                const double mine = ((down >> c) & 1u) ? su[c] : gu[c];   // sigma[u] * g[w] or sigma[w] * g[u]: one product either way
+                if (((down | up) >> c) & 1u) x += mine * v[k];
+            }
+        }
+        ebc[e] = x;
+    }
+}
+
+// rows of at most long_row entries: G lanes per row, 256 / G rows per workgroup
+template <u32 B, u32 G>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_paths_edges(const u64 *__restrict__ row_ptr, const u32 *__restrict__ col, const int32_t *__restrict__ dist, const double *__restrict__ sigma,
+              const double *__restrict__ g, u64 n, u32 b, u32 long_row, double *ebc)
+{
+    const u64 row = (u64)blockIdx.x * (LZX_MULTI_BLOCK / G) + threadIdx.x / G;
+    if (row >= n) return;
+    const u64 beg = row_ptr[row], end = row_ptr[row + 1];
+    if (end - beg > long_row) return;   // k_paths_edges_long's
+    paths_edges_of_row<B>(row, beg + (threadIdx.x & (G - 1)), end, G, col, dist, sigma, g, b, ebc);
+}
+
+// rows of more than long_row entries among the 256 rows of blockIdx.x: gridDim.y workgroups per row, which take its entries in
+// turns of 256 (the hubs of an R-MAT graph sit side by side at the low ids: one workgroup for all of them is the whole pass's tail)
+template <u32 B>
+__global__ void __launch_bounds__(LZX_MULTI_BLOCK)
+k_paths_edges_long(const u64 *__restrict__ row_ptr, const u32 *__restrict__ col, const int32_t *__restrict__ dist, const double *__restrict__ sigma,
+                   const double *__restrict__ g, u64 n, u32 b, u32 long_row, double *ebc)
+{
+    __shared__ u32 s_rows[LZX_MULTI_BLOCK];
+    __shared__ u32 s_count;
+    const u64 mine = (u64)blockIdx.x * LZX_MULTI_BLOCK + threadIdx.x;
+    const u32 count = lzx_collect_long_rows(mine < n && row_ptr[mine + 1] - row_ptr[mine] > long_row, (u32)mine, s_rows, &s_count);
+    for (u32 r = 0; r < count; ++r) {
+        const u64 row = s_rows[r];
+        paths_edges_of_row<B>(row, row_ptr[row] + (u64)blockIdx.y * LZX_MULTI_BLOCK + threadIdx.x, row_ptr[row + 1], LZX_MULTI_BLOCK * gridDim.y, col,
+                              dist, sigma, g, b, ebc);
+    }
+}
+
 // in [n][B] -> out [b][n]
 template <u32 B, typename T>
 __global__ void __launch_bounds__(LZX_MULTI_BLOCK) k_paths_unpack(const T *in, u32 b, u64 n, T *out)
@@ -199,32 +350,38 @@ struct PathsCall {
     uint64_t *reached, *sum_dist;
     double *harmonic;
     uint32_t *ecc;
-    double *bc;                // non-null: the backward pass runs
+    double *bc;                // non-null (or ebc): the backward pass runs
     lzx_bfs_info *info;
+    double *ebc = nullptr;     // lzx_brandes_f64: the edge pass runs, and the backward pass keeps sigma
+    bool endpoints = false;
+    lzx_brandes_info *binfo = nullptr;
 };
 
 struct PathsState {
     int32_t *dist;
     double *sigma, *third, *bc, *part;
     u32 *part_row, *reached;
+    double *delta, *ebc;       // the fourth [n][B] array (bc and ebc both wanted), ebc [nnz]
+    long long *cnt;            // [n], the endpoints' count
+    u32 lanes = 0;             // lanes per row of the edge pass
     u32 max_level = 0, sweeps = 0;
-    double sweep_ms = 0.0;
+    double sweep_ms = 0.0, edge_ms = 0.0;
 };
 
 u64 round16(u64 bytes) { return (bytes + 15) & ~15ull; }
 }   // namespace
 
-template <u32 B, bool BACK>
+template <u32 B, int MODE>
 static int paths_level(lzx_ctx *c, const PathsState &s, u32 b, int32_t d)
 {
     const lzx_multi_state *m = c->multi;
     const u64 n_waves = m->n_wl / (64 / B);
     if (n_waves)
-        hipLaunchKernelGGL((k_paths_sweep<B, BACK>), dim3((u32)((n_waves + 3) / 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_wl, n_waves,
-                           c->d_col_idx, s.part_row, s.dist, s.sigma, s.third, s.part, b, d, s.reached);
+        hipLaunchKernelGGL((k_paths_sweep<B, MODE>), dim3((u32)((n_waves + 3) / 4)), dim3(LZX_MULTI_BLOCK), 0, c->stream, m->d_wl, n_waves,
+                           c->d_col_idx, s.part_row, s.dist, s.sigma, s.third, s.part, b, d, s.reached, s.delta);
     if (m->n_split)
-        hipLaunchKernelGGL((k_paths_split<B, BACK>), dim3(grid_of((u64)m->n_split * B)), dim3(LZX_MULTI_BLOCK), 0, c->stream, s.part,
-                           m->d_split_row, m->d_split_first, m->n_split, s.dist, s.sigma, s.third, b, d, s.reached);
+        hipLaunchKernelGGL((k_paths_split<B, MODE>), dim3(grid_of((u64)m->n_split * B)), dim3(LZX_MULTI_BLOCK), 0, c->stream, s.part,
+                           m->d_split_row, m->d_split_first, m->n_split, s.dist, s.sigma, s.third, b, d, s.reached, s.delta);
     LZX_HIP(hipGetLastError());
     return LZX_OK;
 }
@@ -251,7 +408,7 @@ static int paths_batch(lzx_ctx *c, const PathsCall &q, LzxGraphRun &run, PathsSt
     for (u32 d = 1;; ++d) {
         if ((u64)d > n) LZX_FAIL(LZX_ERR_LIMIT, "%s: the search is still growing at level %u on %llu vertices", q.fn, d, (unsigned long long)n);
         LZX_HIP(hipEventRecord(run.ev0, st));
-        LZX_TRY((paths_level<B, false>(c, s, b, (int32_t)d)));
+        LZX_TRY((paths_level<B, PATHS_FORWARD>(c, s, b, (int32_t)d)));
         LZX_HIP(hipEventRecord(run.ev1, st));
         u32 now[LZX_BFS_BATCH] = {};
         LZX_HIP(hipMemcpyAsync(now, s.reached, sizeof(u32) * B, hipMemcpyDeviceToHost, st));
@@ -295,21 +452,51 @@ static int paths_batch(lzx_ctx *c, const PathsCall &q, LzxGraphRun &run, PathsSt
         LZX_HIP(hipMemcpyAsync(q.paths + (u64)first * n, s.third, sizeof(double) * b * n, hipMemcpyDeviceToHost, st));
     }
     if (q.dist || q.paths) LZX_HIP(hipStreamSynchronize(st));
-    if (!q.bc) return LZX_OK;
+    if (!q.bc && !q.ebc) return LZX_OK;
 
     // backward: nothing for the host to read between the levels
+    const bool keep = q.ebc != nullptr;
     LZX_HIP(hipEventRecord(run.ev0, st));
     for (u32 d = top; d >= 1; --d) {
-        LZX_TRY((paths_level<B, true>(c, s, b, (int32_t)d)));
+        if (keep) LZX_TRY((paths_level<B, PATHS_BACK_KEEP>(c, s, b, (int32_t)d)));
+        else LZX_TRY((paths_level<B, PATHS_BACK>(c, s, b, (int32_t)d)));
         ++s.sweeps;
     }
     LZX_HIP(hipEventRecord(run.ev1, st));
-    hipLaunchKernelGGL(k_paths_accumulate<B>, dim3(grid_of(n)), blk, 0, st, s.dist, s.sigma, n, b, s.bc);
-    LZX_HIP(hipGetLastError());
+    if (q.bc) {   // (a row the backward pass never wrote has dist <= 0 and is not read)
+        hipLaunchKernelGGL(k_paths_accumulate<B>, dim3(grid_of(n)), blk, 0, st, s.dist, keep ? s.delta : s.sigma, n, b, s.bc);
+        LZX_HIP(hipGetLastError());
+    }
+    if (q.endpoints) {
+        PathsReached r{};
+        for (u32 col = 0; col < b; ++col) r.v[col] = cnt[col];
+        hipLaunchKernelGGL(k_paths_endpoints<B>, dim3(grid_of(n)), blk, 0, st, s.dist, n, b, r, s.cnt);
+        LZX_HIP(hipGetLastError());
+    }
+    if (keep) {
+        LZX_HIP(hipEventRecord(run.ev2, st));
+        const u32 long_row = 64 * s.lanes;
+        lzx_with_lanes<32>(s.lanes, [&](auto g) {
+            hipLaunchKernelGGL((k_paths_edges<B, g>), dim3(lzx_row_grid(n, LZX_MULTI_BLOCK / g)), blk, 0, st, c->d_row_ptr, c->d_col_idx, s.dist,
+                               s.sigma, s.third, n, b, long_row, s.ebc);
+        });
+        LZX_HIP(hipGetLastError());
+        if (c->max_degree > long_row) {
+            const u32 shares = (u32)std::min<u64>((c->max_degree + 2047) / 2048, 32);   // workgroups per long row
+            hipLaunchKernelGGL(k_paths_edges_long<B>, dim3(grid_of(n), shares), blk, 0, st, c->d_row_ptr, c->d_col_idx, s.dist, s.sigma, s.third, n, b,
+                               long_row, s.ebc);
+            LZX_HIP(hipGetLastError());
+        }
+        LZX_HIP(hipEventRecord(run.ev3, st));
+    }
     LZX_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
     LZX_HIP(hipEventElapsedTime(&ms, run.ev0, run.ev1));
     s.sweep_ms += ms;
+    if (keep) {
+        LZX_HIP(hipEventElapsedTime(&ms, run.ev2, run.ev3));
+        s.edge_ms += ms;
+    }
     return LZX_OK;
 }
 
@@ -332,10 +519,11 @@ static int paths_run(lzx_handle h, const PathsCall &q)
     const lzx_multi_state *m = c->multi;
     const u64 n = c->n;
     const u32 Bmax = lzx_multi_pad_width(std::min<u32>(q.ns, LZX_BFS_BATCH));
-    const bool third = q.bc || q.dist || q.paths;
+    const bool third = q.bc || q.ebc || q.dist || q.paths, fourth = q.bc && q.ebc;
     const u64 b_dist = round16(sizeof(int32_t) * n * Bmax), b_vec = sizeof(double) * n * Bmax, b_bc = q.bc ? sizeof(double) * n : 0;
     const u64 b_part = sizeof(double) * (u64)m->n_parts * Bmax, b_prow = round16(sizeof(u32) * (u64)m->n_parts);
-    const u64 bytes = b_dist + b_vec * (third ? 2 : 1) + b_bc + b_part + b_prow + sizeof(u32) * LZX_BFS_BATCH;
+    const u64 b_ebc = q.ebc ? sizeof(double) * c->nnz : 0, b_cnt = q.endpoints ? sizeof(long long) * n : 0;
+    const u64 bytes = b_dist + b_vec * (1 + (third ? 1 : 0) + (fourth ? 1 : 0)) + b_bc + b_ebc + b_cnt + b_part + b_prow + sizeof(u32) * LZX_BFS_BATCH;
     LzxGraphRun run(c);
     char what[80];
     std::snprintf(what, sizeof what, "the state of %u interleaved columns on %llu vertices", Bmax, (ull)n);
@@ -345,12 +533,22 @@ static int paths_run(lzx_handle h, const PathsCall &q)
     s.dist = reinterpret_cast<int32_t *>(p); p += b_dist;
     s.sigma = reinterpret_cast<double *>(p); p += b_vec;
     s.third = third ? reinterpret_cast<double *>(p) : nullptr; p += third ? b_vec : 0;
+    s.delta = fourth ? reinterpret_cast<double *>(p) : nullptr; p += fourth ? b_vec : 0;
     s.bc = q.bc ? reinterpret_cast<double *>(p) : nullptr; p += b_bc;
+    s.ebc = q.ebc ? reinterpret_cast<double *>(p) : nullptr; p += b_ebc;
+    s.cnt = q.endpoints ? reinterpret_cast<long long *>(p) : nullptr; p += b_cnt;
     s.part = reinterpret_cast<double *>(p); p += b_part;
     s.part_row = reinterpret_cast<u32 *>(p); p += b_prow;
     s.reached = reinterpret_cast<u32 *>(p);
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
+    if (q.ebc) {
+        LZX_HIP(hipEventCreate(&run.ev2));
+        LZX_HIP(hipEventCreate(&run.ev3));
+        s.lanes = lzx_lanes_per_row(c, c->nnz, 32);
+        if (b_ebc) LZX_HIP(hipMemsetAsync(s.ebc, 0, b_ebc, c->stream));
+    }
+    if (q.endpoints) LZX_HIP(hipMemsetAsync(s.cnt, 0, b_cnt, c->stream));
     if (m->n_split) {
         hipLaunchKernelGGL(k_paths_part_rows, dim3((m->n_split + 255) / 256), dim3(256), 0, c->stream, m->d_split_row, m->d_split_first, m->n_split, s.part_row);
         LZX_HIP(hipGetLastError());
@@ -369,9 +567,21 @@ static int paths_run(lzx_handle h, const PathsCall &q)
         }
         LZX_TRY(rc);
     }
-    if (q.bc) {
-        LZX_HIP(hipMemcpyAsync(q.bc, s.bc, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-        LZX_HIP(hipStreamSynchronize(c->stream));
+    if (q.endpoints) {
+        hipLaunchKernelGGL(k_paths_add_endpoints, dim3(grid_of(n)), dim3(LZX_MULTI_BLOCK), 0, c->stream, s.cnt, n, s.bc);
+        LZX_HIP(hipGetLastError());
+    }
+    if (q.bc) LZX_HIP(hipMemcpyAsync(q.bc, s.bc, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    if (b_ebc) LZX_HIP(hipMemcpyAsync(q.ebc, s.ebc, b_ebc, hipMemcpyDeviceToHost, c->stream));
+    if (q.bc || b_ebc) LZX_HIP(hipStreamSynchronize(c->stream));
+    if (q.binfo) {
+        q.binfo->ns = q.ns;
+        q.binfo->batches = batches;
+        q.binfo->max_level = s.max_level;
+        q.binfo->sweeps = s.sweeps;
+        q.binfo->sweep_ms = s.sweep_ms;
+        q.binfo->edge_ms = s.edge_ms;
+        q.binfo->loop_ms = lzx_ms_since(t0);
     }
     if (q.info) {
         q.info->ns = q.ns;
@@ -397,4 +607,18 @@ extern "C" int lzx_betweenness_f64(lzx_handle h, uint32_t ns, const uint32_t *so
     static const char *fn = "lzx_betweenness_f64";
     if (ns > 0 && !bc) LZX_FAIL(LZX_ERR_ARG, "%s: null bc", fn);
     return paths_run(h, PathsCall{fn, ns, sources, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bc, info});
+}
+
+extern "C" int lzx_brandes_f64(lzx_handle h, uint32_t ns, const uint32_t *sources, uint32_t flags, double *bc, double *ebc, lzx_brandes_info *info)
+{
+    static const char *fn = "lzx_brandes_f64";
+    if (ns == 0) LZX_FAIL(LZX_ERR_ARG, "%s: ns == 0", fn);
+    if (!bc && !ebc) LZX_FAIL(LZX_ERR_ARG, "%s: null bc and null ebc: nothing is asked for", fn);
+    if (flags & ~(uint32_t)LZX_BRANDES_ENDPOINTS) LZX_FAIL(LZX_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~(uint32_t)LZX_BRANDES_ENDPOINTS);
+    if ((flags & LZX_BRANDES_ENDPOINTS) && !bc) LZX_FAIL(LZX_ERR_ARG, "%s: LZX_BRANDES_ENDPOINTS with null bc: the endpoints count into bc", fn);
+    PathsCall q{fn, ns, sources, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bc, nullptr};
+    q.ebc = ebc;
+    q.endpoints = (flags & LZX_BRANDES_ENDPOINTS) != 0;
+    q.binfo = info;
+    return paths_run(h, q);
 }
