@@ -648,7 +648,7 @@ int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 
     const u32 n = (u32)c->n;
     hipStream_t st = c->stream;
     const u32 G = lanes_of(c);
-    const u32 long_row = c->color_long_opt > 0 ? (u32)std::min<int64_t>(c->color_long_opt, 0xffffffff) : 64 * G;
+    const u32 long_row = lzx_shape_or(c->color_long_opt, 64 * G);
     const u32 gb = vertex_grid(n);
     const ColorOrder order{s.d, seed, flags & LZX_COLOR_TIES_BY_ID};
 

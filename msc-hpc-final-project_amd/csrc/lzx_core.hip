@@ -5,16 +5,17 @@
 // k_r = max(k_{r-1}, the smallest remaining degree of a remaining vertex) and removes, all at once, every remaining vertex whose
 // remaining degree is <= k_r: core[v] = k_r, layer[v] = r.
 //
-// Push peeling.  deg[v] is the remaining degree, layer[v] != 0 marks a vertex that is removed or queued for removal, and `order`
-// is one queue in which every vertex is placed exactly once over the whole call, so that each round's frontier is a window
-// [beg, end) of it and what a launch appends behind `end` is the next window.
+// Push peeling: the loop, the level start and the push of lzx_peel.h, which lzx_truss.hip shares, over vertices.  deg[v] is the
+// remaining degree, layer[v] != 0 marks a vertex that is removed or queued for removal, and `order` is one queue in which every
+// vertex is placed exactly once over the whole call, so that each round's frontier is a window [beg, end) of it and what a
+// launch appends behind `end` is the next window.
 //   degrees      k_core_degrees       one thread per row: lzx_degree_no_diagonal (lzx_graph_call.h), and layer = 0, the queue empty
-//   level start  k_core_level         one thread per vertex, when the frontier is empty: an unmarked vertex with deg <= k is
-//                                     marked (layer = r, core = k) and appended, the others contribute to a minimum.  The host
-//                                     tries k + 1 first -- after a level is peeled out every remaining degree is at least that --
-//                                     and only if nothing was appended repeats the sweep with the minimum it got back.
+//   level start  k_peel_level         (lzx_peel.h) one thread per vertex, when the frontier is empty: an unmarked vertex with
+//                                     deg <= k is marked (layer = r, core = k) and appended, the others contribute to a minimum.
+//                                     The host tries k + 1 first -- after a level is peeled out every remaining degree is at least
+//                                     that -- and only if nothing was appended repeats the sweep with the minimum it got back.
 //   peel         k_core_peel<G>       G lanes per row of the window; for every neighbour u != v that is not marked,
-//                                     old = atomicSub(&deg[u], 1), and the one lane that sees old == k + 1 marks u
+//                                     lzx_peel_push: old = atomicSub(&deg[u], 1), and the one lane that sees old == k + 1 marks u
 //                                     (layer = r + 1, core = k) and appends it
 //                k_core_peel_long     the window's rows of more than long_row entries: a workgroup per (row, slice of its entries)
 // Appends are aggregated per wavefront (lzx_wave_append: a ballot, one atomic add on the queue's end, a broadcast), and so is the
@@ -40,10 +41,9 @@
 
 #include "lzx_internal.h"
 #include "lzx_graph_call.h"
+#include "lzx_peel.h"
 
 static constexpr u32 LZX_CORE_BLOCK = 256;
-static constexpr u32 LZX_CORE_SLICES = 64;   // workgroups a long row's entries are dealt to (at most)
-static constexpr u32 LZX_CORE_NONE = 0xffffffffu;
 
 __global__ void __launch_bounds__(LZX_CORE_BLOCK)
 k_core_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *counters, u32 n)
@@ -53,44 +53,6 @@ k_core_degrees(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32
     if (v >= n) return;
     deg[v] = lzx_degree_no_diagonal(row_ptr, col_idx, v);
     layer[v] = 0;
-}
-
-// counters[0] = the queue's end, counters[1] = the minimum (LZX_CORE_NONE before the launch)
-__global__ void __launch_bounds__(LZX_CORE_BLOCK)
-k_core_level(const u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *counters, u32 n, u32 k, u32 r)
-{
-    const u64 v = (u64)blockIdx.x * LZX_CORE_BLOCK + threadIdx.x;
-    bool take = false;
-    u32 m = LZX_CORE_NONE;
-    if (v < n && layer[v] == 0) {
-        const u32 d = deg[v];
-        if (d <= k) take = true;
-        else m = d;
-    }
-    const u32 at = lzx_wave_append(take, &counters[0]);
-    if (take) {
-        layer[v] = r;
-        core[v] = k;
-        if (at < n) order[at] = (u32)v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = min(m, (u32)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0 && m != LZX_CORE_NONE) atomicMin(&counters[1], m);
-}
-
-// one neighbour u of a window's vertex (have: this lane holds one, it is not the vertex itself): the decrement, the mark, the append
-__device__ __forceinline__ void core_push(bool have, u32 u, u32 *deg, u32 *layer, u32 *core, u32 *order, u32 *tail, u32 n, u32 k, u32 r)
-{
-    bool take = false;
-    if (have && layer[u] == 0) {
-        const u32 old = atomicSub(&deg[u], 1u);
-        if (old == k + 1) take = atomicCAS(&layer[u], 0u, r + 1) == 0u;
-    }
-    const u32 at = lzx_wave_append(take, tail);
-    if (take) {
-        core[u] = k;
-        if (at < n) order[at] = u;
-    }
 }
 
 // rows of the window order[wbeg .. wbeg + wlen) with at most long_row entries: G lanes per row, 256 / G rows per workgroup
@@ -116,7 +78,7 @@ k_core_peel(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u32 *c
         const u32 e = t * G + sub;
         u32 u = v;
         if (e < len) u = col_idx[beg + e];
-        core_push(u != v, u, deg, layer, core, order, &counters[0], n, k, r);
+        lzx_peel_push(u != v && layer[u] == 0, u, deg, layer, core, order, &counters[0], n, k, k, r);
     }
 }
 
@@ -139,7 +101,7 @@ k_core_peel_long(const u64 *row_ptr, const u32 *col_idx, u32 *deg, u32 *layer, u
             const u64 e = e0 + threadIdx.x;
             u32 u = v;
             if (e < end) u = col_idx[e];
-            core_push(u != v, u, deg, layer, core, order, &counters[0], n, k, r);
+            lzx_peel_push(u != v && layer[u] == 0, u, deg, layer, core, order, &counters[0], n, k, k, r);
         }
     }
 }
@@ -168,63 +130,36 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
     // lanes per row of the window: about half the mean degree of the rows that have an edge.  Rows of more than 64 G entries
     // (256 ... 2048: more than 64 trips of a group) go to the long-row launch.
     const u32 G = lzx_lanes_per_row(c, c->nnz, 32);
-    const u32 long_row = c->core_long_opt > 0 ? (u32)std::min<int64_t>(c->core_long_opt, 0xffffffff) : 64 * G;
-    const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_CORE_BLOCK), 1), LZX_CORE_SLICES);
+    const u32 long_row = lzx_shape_or(c->core_long_opt, 64 * G);
+    const u32 slices = lzx_peel_slices(c->max_degree, LZX_CORE_BLOCK);
     const u32 gb = (n + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK;
 
     LZX_HIP(hipEventRecord(run.ev0, st));
     hipLaunchKernelGGL(k_core_degrees, dim3(gb), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, d_layer, d_counters, n);
     LZX_HIP(hipGetLastError());
-    u32 k = 0, rounds = 0, levels = 0;
-    u32 queued = 0;        // the queue's end: vertices marked so far
-    u32 level_pos = 0;     // the queue position at which the current level began
-    u32 core0 = 0;
-    while (queued < n) {
-        // ---- the frontier is empty: the next level.  k + 1 first (0 at the start); the minimum if that appends nothing ----
-        u32 k_try = levels == 0 ? 0u : (k == LZX_CORE_NONE ? k : k + 1);
-        u32 end = queued;
-        for (int attempt = 0; attempt < 2 && end == queued; ++attempt) {
-            u32 words[2] = {0, 0};
-            LZX_HIP(hipMemsetAsync(d_counters + 1, 0xff, sizeof(u32), st));
-            hipLaunchKernelGGL(k_core_level, dim3(gb), dim3(LZX_CORE_BLOCK), 0, st, d_deg, d_layer, d_core, d_order, d_counters, n, k_try, rounds + 1);
+    LzxPeelResult peel;
+    LZX_TRY(lzx_peel_loop(
+        fn_name, {"vertex", "remaining degree", "vertices"}, st, d_counters, n,
+        [&](u32 k_try, u32 r) -> int {
+            hipLaunchKernelGGL(k_peel_level, dim3(lzx_row_grid(n, LZX_PEEL_BLOCK)), dim3(LZX_PEEL_BLOCK), 0, st, d_deg, d_layer, d_core, d_order, d_counters,
+                               n, k_try, k_try, r);
             LZX_HIP(hipGetLastError());
-            LZX_HIP(hipMemcpyAsync(words, d_counters, sizeof(words), hipMemcpyDeviceToHost, st));
-            LZX_HIP(hipStreamSynchronize(st));
-            end = std::min(words[0], n);
-            if (end == queued) k_try = words[1];   // nobody at this k: the smallest remaining degree is the next
-        }
-        if (end == queued) LZX_FAIL(LZX_ERR_LIMIT, "%s: no vertex of remaining degree %u among the %u left after %u rounds", fn_name, k_try, n - queued, rounds);
-        k = k_try;
-        ++levels;
-        level_pos = queued;
-        u32 wbeg = queued;
-        queued = end;
-        // ---- the rounds of this level: window [wbeg, queued) ----
-        for (;;) {
-            ++rounds;
-            if ((u64)rounds > (u64)n + 1) LZX_FAIL(LZX_ERR_LIMIT, "%s: %u rounds on %u vertices", fn_name, rounds, n);
-            if (rounds == 1 && k == 0) core0 = queued;
-            if (queued >= n) break;   // everything is queued: the last window has nobody left to push to
-            const u32 wlen = queued - wbeg;
+            return LZX_OK;
+        },
+        [&](u32 wbeg, u32 wlen, u32 k, u32 r) -> int {
             lzx_with_lanes<32>(G, [&](auto g) {
                 hipLaunchKernelGGL(k_core_peel<g>, dim3(lzx_row_grid(wlen, LZX_CORE_BLOCK / g)), dim3(LZX_CORE_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx,
-                                   d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, rounds, long_row);
+                                   d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, r, long_row);
             });
             LZX_HIP(hipGetLastError());
             if (c->max_degree > long_row) {
                 hipLaunchKernelGGL(k_core_peel_long, dim3((wlen + LZX_CORE_BLOCK - 1) / LZX_CORE_BLOCK, slices), dim3(LZX_CORE_BLOCK), 0, st,
-                                   c->d_row_ptr, c->d_col_idx, d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, rounds, long_row);
+                                   c->d_row_ptr, c->d_col_idx, d_deg, d_layer, d_core, d_order, d_counters, n, wbeg, wlen, k, r, long_row);
                 LZX_HIP(hipGetLastError());
             }
-            u32 word = 0;
-            LZX_HIP(hipMemcpyAsync(&word, d_counters, sizeof(u32), hipMemcpyDeviceToHost, st));
-            LZX_HIP(hipStreamSynchronize(st));
-            end = std::min(word, n);
-            if (end == queued) break;   // nothing fell to k: the level is peeled out
-            wbeg = queued;
-            queued = end;
-        }
-    }
+            return LZX_OK;
+        },
+        &peel));
     LZX_HIP(hipEventRecord(run.ev1, st));
     if (core) LZX_HIP(hipMemcpyAsync(core, d_core, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
     if (layer) LZX_HIP(hipMemcpyAsync(layer, d_layer, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
@@ -232,11 +167,11 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
     float peel_ms = 0.f;
     LZX_HIP(hipEventElapsedTime(&peel_ms, run.ev0, run.ev1));
     if (info) {
-        info->main_core_size = (u64)n - level_pos;
-        info->core0 = core0;
-        info->degeneracy = k;
-        info->levels = levels;
-        info->rounds = rounds;
+        info->main_core_size = (u64)n - peel.level_pos;
+        info->core0 = peel.first_level == 0 ? peel.first_end : 0;
+        info->degeneracy = peel.level;
+        info->levels = peel.levels;
+        info->rounds = peel.rounds;
         info->reserved_ = 0;
         info->peel_ms = peel_ms;
         info->loop_ms = lzx_ms_since(t0);

@@ -2,7 +2,9 @@
 // lzx_bfs_multi / lzx_betweenness_f64 (lzx_paths.hip), lzx_triangles, lzx_core_numbers, lzx_truss and lzx_color /
 // lzx_label_propagation / lzx_modularity (lzx_communities.hip), lzx_sweep_cut (lzx_sweep.hip) and lzx_similarity (lzx_similarity.hip).  Host side: the preconditions of such
 // a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
-// the choice of lanes per row.  Device side: the idioms of their kernels over ascending rows and wavefront-aggregated queues.
+// the choice of lanes per row, a test shape in a rule's place.  Device side: the idioms of their kernels over ascending rows and
+// wavefront-aggregated queues.  What only some of them share has a header of its own on top of this one: the oriented copy and
+// the split of the walks over it (lzx_tri_orient.h: lzx_triangles, lzx_truss), the push peel (lzx_peel.h: lzx_core_numbers, lzx_truss).
 #pragma once
 
 #include <algorithm>
@@ -76,6 +78,8 @@ void lzx_with_lanes(u32 G, F f)
     else if (G == 32 || MAX_G == 32) f(std::integral_constant<u32, 32>{});
     else if constexpr (MAX_G == 64) f(std::integral_constant<u32, 64>{});
 }
+// a test shape that takes a rule's place: opt where it is set (> 0, capped at what a u32 holds), else dflt
+inline u32 lzx_shape_or(int64_t opt, u32 dflt) { return opt > 0 ? (u32)std::min<int64_t>(opt, 0xffffffff) : dflt; }
 // workgroups that take rows_per_block rows each
 inline u32 lzx_row_grid(u64 rows, u32 rows_per_block) { return (u32)((rows + rows_per_block - 1) / rows_per_block); }
 

@@ -433,8 +433,8 @@ extern "C" int lzx_similarity(lzx_handle c, uint64_t np64, const uint32_t *u, co
     LZX_HIP(hipEventRecord(run.ev1, st));
 
     // ---- classification: the counts, then the lists ----
-    const u32 long_pair = c->sim_long_opt > 0 ? (u32)std::min<int64_t>(c->sim_long_opt, 0xffffffff) : 64 * G;
-    const u32 slice = c->sim_slice_opt > 0 ? (u32)std::min<int64_t>(c->sim_slice_opt, 0xffffffff) : LZX_SIM_SLICE;
+    const u32 long_pair = lzx_shape_or(c->sim_long_opt, 64 * G);
+    const u32 slice = lzx_shape_or(c->sim_slice_opt, LZX_SIM_SLICE);
     SimArgs a = {c->d_row_ptr, c->d_col_idx, d_pu, d_pv, d_tab_aa, d_tab_ra, d_common, d_out_aa, d_out_ra, np, long_pair, slice, edges_mode ? 1u : 0u};
     const u32 gs = std::min<u32>(LZX_SIM_STAT_GRID, gp);
     LZX_HIP(hipEventRecord(run.ev2, st));

@@ -384,7 +384,7 @@ extern "C" int lzx_sweep_cut(lzx_handle c, uint32_t ns, const double *scores, ui
 
     // ---- the edge sweep ----
     const u32 G = lzx_lanes_per_row(c, c->nnz, 32);
-    const u32 long_row = c->sweep_long_opt > 0 ? (u32)std::min<int64_t>(c->sweep_long_opt, 0xffffffff) : 64 * G;
+    const u32 long_row = lzx_shape_or(c->sweep_long_opt, 64 * G);
     const bool long_rows = c->max_degree > long_row;
     if (long_rows) {
         LZX_HIP(hipMemsetAsync(d_long_count, 0, sizeof(u32), st));

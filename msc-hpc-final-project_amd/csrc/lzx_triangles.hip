@@ -7,7 +7,7 @@
 // lzx_tri_orient.h, which lzx_truss.hip shares.
 //   degrees    k_tri_degrees           one thread per row: lzx_degree_no_diagonal (lzx_graph_call.h)
 //   out-counts k_tri_orient (count)    a group of G lanes per row counts the neighbours of higher rank; hipcub's exclusive scan
-//                                      turns the counts into the row pointers, in place
+//                                      turns the counts into the row pointers, in place (lzx_orient_count)
 //   fill       k_tri_orient (fill)     the same walk writes them: a ballot over the group orders the kept entries, so the
 //                                      columns stay ascending by id (a monotone filter of an ascending row)
 // A vertex of out-degree k has k neighbours of degree >= k: k^2 <= nnz, every oriented list has fewer than 2^16 entries while
@@ -27,8 +27,6 @@
 //
 // Statistics.  k_tri_stats forms c_v = 2 t_v / (d_v (d_v - 1)) (one correctly rounded division; 0 where d_v < 2 or t_v = 0) and
 // block partials of sum c (fp64), sum t, sum d (d - 1) / 2 (u64) and max t; k_tri_close adds them in a fixed order.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -255,31 +253,15 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     ull *d_pt = reinterpret_cast<ull *>(d_pc + np), *d_pw = d_pt + np, *d_pm = d_pw + np, *d_out = d_pm + np;
     u32 *d_kmax = reinterpret_cast<u32 *>(d_out + 4);
     u32 *d_deg = d_kmax + 2;
-    const size_t scan_len = (size_t)n + 1;   // (hipcub takes the count's type from its argument: not limited to 2^31)
-    size_t tmp_bytes = 0;
-    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_orp, d_orp, scan_len, st));
-    tmp_bytes = std::max<size_t>(tmp_bytes, 16);
-    std::snprintf(what, sizeof what, "the scan's scratch for the row pointers of %u vertices", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, -1, tmp_bytes, tmp_bytes, &run.more[0]));
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // ---- the oriented copy ----
     const u32 Go = lzx_lanes_per_row(c, c->nnz, 64);
-    const u32 gb = (n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK;
-    LZX_HIP(hipEventRecord(run.ev0, st));
-    LZX_HIP(hipMemsetAsync(d_kmax, 0, 2 * sizeof(u32), st));
-    LZX_HIP(hipMemsetAsync(d_tri, 0, sizeof(ull) * n, st));
-    hipLaunchKernelGGL(k_tri_degrees, dim3(gb), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, n);
-    LZX_HIP(hipGetLastError());
-    orient_pass(Go, st, c, d_deg, d_orp, nullptr, nullptr, d_kmax);
-    LZX_HIP(hipGetLastError());
-    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(run.more[0], tmp_bytes, d_orp, d_orp, scan_len, st));
     u64 m = 0;
     u32 kmax = 0;
-    LZX_HIP(hipMemcpyAsync(&m, d_orp + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipMemcpyAsync(&kmax, d_kmax, sizeof(u32), hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipStreamSynchronize(st));
+    LZX_TRY(lzx_orient_count(c, fn_name, run, Go, d_deg, d_orp, d_kmax, &m, &kmax));
+    LZX_HIP(hipMemsetAsync(d_tri, 0, sizeof(ull) * n, st));
     // the oriented columns: the scan's total, which is what the fill writes whatever was handed over ((nnz - self loops) / 2 of a
     // symmetric matrix)
     const u64 col_bytes = sizeof(u32) * std::max<u64>(m, 1);
@@ -297,17 +279,17 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
 
     // ---- counting: lanes per row about half the mean oriented degree ----
     const u32 G = lzx_lanes_per_row(c, m, 32, LZX_OVER_ORIENTED);
-    const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
-    const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
     LZX_HIP(hipEventRecord(run.ev0, st));
     if (m) {
+        const LzxTriShape shape = lzx_tri_shape(c, kmax);
         lzx_with_lanes<32>(G, [&](auto g) {
-            hipLaunchKernelGGL(k_tri_count<g>, dim3(lzx_row_grid(n, LZX_TRI_BLOCK / g)), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n, long_list);
+            hipLaunchKernelGGL(k_tri_count<g>, dim3(lzx_row_grid(n, LZX_TRI_BLOCK / g)), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n,
+                               shape.long_list);
         });
         LZX_HIP(hipGetLastError());
-        if (kmax > long_list) {
-            const u32 slices = std::min<u32>(std::max<u32>(kmax / 64, 1), LZX_TRI_SLICES);
-            hipLaunchKernelGGL(k_tri_count_long, dim3(gb, slices), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n, long_list, stage);
+        if (kmax > shape.long_list) {
+            hipLaunchKernelGGL(k_tri_count_long, dim3(lzx_row_grid(n, LZX_TRI_BLOCK), shape.slices), dim3(LZX_TRI_BLOCK), 0, st, d_orp, d_oci, d_tri, n,
+                               shape.long_list, shape.stage);
             LZX_HIP(hipGetLastError());
         }
     }

@@ -23,12 +23,13 @@
 //                          LDS and leave with one add per edge
 //   k_truss_stats          block partials of the sum (u64) and the maximum of the supports; the host adds them
 //
-// Push peeling over one queue of edge ids, as lzx_core.hip peels vertices.  sup[e] is the remaining support, mark[e] is 0 for an
-// edge not yet removed and else its layer, and every edge is appended to `queue` exactly once, so that a round's frontier is a
-// window [beg, end) of it and what a launch appends behind `end` is the next window.
-//   level start  k_truss_level       one thread per edge, when the frontier is empty: an unmarked edge with sup <= s is marked
-//                                    (mark = r, truss = s + 2) and appended, the others contribute to a minimum.  The host tries
-//                                    s + 1 first and only if nothing was appended sweeps again with the minimum.
+// Push peeling over one queue of edge ids, as lzx_core.hip peels vertices: the loop, the level start and the push of lzx_peel.h.
+// sup[e] is the remaining support, mark[e] is 0 for an edge not yet removed and else its layer, and every edge is appended to
+// `queue` exactly once, so that a round's frontier is a window [beg, end) of it and what a launch appends behind `end` is the
+// next window.
+//   level start  k_peel_level        (lzx_peel.h) one thread per edge, when the frontier is empty: an unmarked edge with sup <= s
+//                                    is marked (mark = r, truss = s + 2) and appended, the others contribute to a minimum.  The
+//                                    host tries s + 1 first and only if nothing was appended sweeps again with the minimum.
 //   peel         k_truss_peel<G>     G lanes per edge e1 = (a, b) of the window: the full rows of a and b in the caller-order CSR are
 //                                    intersected, the shorter walked and the longer searched; w = a and w = b (self loops) are
 //                                    skipped.  A common neighbour w gives e2 = eid[w's place in the walked row] and e3 = eid[its
@@ -40,7 +41,7 @@
 //   both in the window       nothing: all three edges leave, nobody is left to tell
 //   exactly one, say e2      e1 and e2 both see this triangle; the one with the smaller edge id decrements e3
 //   neither                  e1 alone sees it: both are decremented
-// so every triangle that dies in round r takes exactly one from each of its edges that stays.  A decrement is
+// so every triangle that dies in round r takes exactly one from each of its edges that stays.  A decrement is lzx_peel_push:
 // old = atomicSub(&sup[x], 1); the one lane that sees old == s + 1 takes the mark by atomicCAS(&mark[x], 0, r + 1), writes
 // truss[x] = s + 2 and appends x.  A mark of 0 and a mark of r + 1 decide alike in the rule, and the marks equal to r or less
 // were written by earlier launches: which edges a round decrements, and how often, does not depend on the order in which its
@@ -55,8 +56,6 @@
 // All atomics are 32-bit integer vector atomics, in global memory and in LDS; nothing is floating-point.  No kernel waits on
 // another workgroup; every device loop is bounded by a row, list or window length.  The loops around lzx_wave_append run the same
 // trips on every lane of a wavefront.  The host reads one word per peeling round and two per level start.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <utility>
@@ -65,11 +64,11 @@
 #include "lzx_internal.h"
 #include "lzx_graph_call.h"
 #include "lzx_tri_orient.h"
+#include "lzx_peel.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
 static constexpr u32 LZX_TRUSS_BLOCK = 256;
-static constexpr u32 LZX_TRUSS_SLICES = 64;      // workgroups a long row's entries are dealt to (at most)
 static constexpr u32 LZX_TRUSS_STAT_GRID = 1024; // block partials of the support statistics (at most)
 static constexpr u32 LZX_TRUSS_NONE = 0xffffffffu;
 static_assert(LZX_TRUSS_BLOCK == LZX_TRI_BLOCK, "the support kernels are laid out as lzx_triangles' counting kernels");
@@ -246,29 +245,6 @@ __global__ void __launch_bounds__(LZX_TRUSS_BLOCK) k_truss_stats(const u32 *sup,
 }
 
 // ---- peel ---------------------------------------------------------------------------------------------------------------------
-// counters[0] = the queue's end, counters[1] = the minimum (LZX_TRUSS_NONE before the launch)
-__global__ void __launch_bounds__(LZX_TRUSS_BLOCK)
-k_truss_level(const u32 *sup, u32 *mark, u32 *truss, u32 *queue, u32 *counters, u32 m, u32 s, u32 r)
-{
-    const u64 e = (u64)blockIdx.x * LZX_TRUSS_BLOCK + threadIdx.x;
-    bool take = false;
-    u32 least = LZX_TRUSS_NONE;
-    if (e < m && mark[e] == 0) {
-        const u32 t = sup[e];
-        if (t <= s) take = true;
-        else least = t;
-    }
-    const u32 at = lzx_wave_append(take, &counters[0]);
-    if (take) {
-        mark[e] = r;
-        truss[e] = s + 2;
-        if (at < m) queue[at] = (u32)e;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) least = min(least, (u32)__shfl_xor((int)least, o, 64));
-    if ((threadIdx.x & 63) == 0 && least != LZX_TRUSS_NONE) atomicMin(&counters[1], least);
-}
-
 // what the peel works on
 struct TrussPeel {
     const u64 *row_ptr;
@@ -298,21 +274,6 @@ __device__ __forceinline__ TrussRows truss_rows(const TrussPeel &p, u32 e1)
     return t;
 }
 
-// one decrement (have: this lane holds one), the mark, the append
-__device__ __forceinline__ void truss_push(bool have, u32 x, const TrussPeel &p)
-{
-    bool take = false;
-    if (have) {
-        const u32 old = atomicSub(&p.sup[x], 1u);
-        if (old == p.s + 1) take = atomicCAS(&p.mark[x], 0u, p.r + 1) == 0u;
-    }
-    const u32 at = lzx_wave_append(take, p.tail);
-    if (take) {
-        p.truss[x] = p.s + 2;
-        if (at < p.m) p.queue[at] = x;
-    }
-}
-
 // entry j of the walked row of e1 (have: this lane holds one): the common neighbour, the triangle rule, the two decrements.
 // Every lane of the wavefront calls it together.
 __device__ __forceinline__ void truss_entry(bool have, u64 j, u32 e1, const TrussRows &t, const TrussPeel &p)
@@ -338,8 +299,8 @@ __device__ __forceinline__ void truss_entry(bool have, u64 j, u32 e1, const Trus
             }
         }
     }
-    truss_push(d2, e2, p);
-    truss_push(d3, e3, p);
+    lzx_peel_push(d2, e2, p.sup, p.mark, p.truss, p.queue, p.tail, p.m, p.s, p.s + 2, p.r);
+    lzx_peel_push(d3, e3, p.sup, p.mark, p.truss, p.queue, p.tail, p.m, p.s, p.s + 2, p.r);
 }
 
 // edges of the window queue[wbeg .. wbeg + wlen) whose shorter row has at most long_row entries: G lanes per edge
@@ -442,30 +403,15 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     ull *d_psum = reinterpret_cast<ull *>(d_orp + n + 1), *d_pmax = d_psum + np;
     u32 *d_deg = reinterpret_cast<u32 *>(d_pmax + np);
     u32 *d_words = d_deg + n, *d_kmax = d_words, *d_counters = d_words + 2;
-    const size_t scan_len = (size_t)n + 1;
-    size_t tmp_bytes = 0;
-    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_orp, d_orp, scan_len, st));
-    tmp_bytes = std::max<size_t>(tmp_bytes, 16);
-    std::snprintf(what, sizeof what, "the scan's scratch for the row pointers of %u vertices", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, -1, tmp_bytes, tmp_bytes, &run.more[0]));
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
 
     // ---- the oriented copy: lzx_triangles' ----
     const u32 Go = lzx_lanes_per_row(c, nnz, 64);
-    const u32 gb = (n + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK;
-    LZX_HIP(hipEventRecord(run.ev0, st));
-    LZX_HIP(hipMemsetAsync(d_words, 0, 4 * sizeof(u32), st));
-    hipLaunchKernelGGL(k_tri_degrees, dim3(gb), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, n);
-    LZX_HIP(hipGetLastError());
-    orient_pass(Go, st, c, d_deg, d_orp, nullptr, nullptr, d_kmax);
-    LZX_HIP(hipGetLastError());
-    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(run.more[0], tmp_bytes, d_orp, d_orp, scan_len, st));
     u64 m64 = 0;
     u32 kmax = 0;
-    LZX_HIP(hipMemcpyAsync(&m64, d_orp + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipMemcpyAsync(&kmax, d_kmax, sizeof(u32), hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipStreamSynchronize(st));
+    LZX_TRY(lzx_orient_count(c, fn_name, run, Go, d_deg, d_orp, d_kmax, &m64, &kmax));
+    LZX_HIP(hipMemsetAsync(d_counters, 0, 2 * sizeof(u32), st));
     if (m64 >= LZX_TRUSS_NONE) LZX_FAIL(LZX_ERR_LIMIT, "%s: %llu edges; edge ids are 32-bit (fewer than 2^32 - 1 edges)", fn_name, (ull)m64);
     const u32 m = (u32)m64;
 
@@ -500,16 +446,15 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     u64 sup_sum = 0, sup_max = 0;
     if (m) {
         const u32 G = lzx_lanes_per_row(c, m, 32, LZX_OVER_ORIENTED);
-        const u32 long_list = c->tri_long_opt > 0 ? (u32)std::min<int64_t>(c->tri_long_opt, 0xffffffff) : LZX_TRI_LONG;
-        const u32 stage = (u32)std::min<u64>(32ull * long_list, LZX_TRI_STAGE);
+        const LzxTriShape shape = lzx_tri_shape(c, kmax);
         lzx_with_lanes<32>(G, [&](auto g) {
             hipLaunchKernelGGL(k_truss_support<g>, dim3(lzx_row_grid(n, LZX_TRUSS_BLOCK / g)), dim3(LZX_TRUSS_BLOCK), 0, st, d_orp, d_oci, d_sup, n,
-                               long_list);
+                               shape.long_list);
         });
         LZX_HIP(hipGetLastError());
-        if (kmax > long_list) {
-            const u32 slices = std::min<u32>(std::max<u32>(kmax / 64, 1), LZX_TRI_SLICES);
-            hipLaunchKernelGGL(k_truss_support_long, dim3(gb, slices), dim3(LZX_TRUSS_BLOCK), 0, st, d_orp, d_oci, d_sup, n, long_list, stage);
+        if (kmax > shape.long_list) {
+            hipLaunchKernelGGL(k_truss_support_long, dim3(lzx_row_grid(n, LZX_TRUSS_BLOCK), shape.slices), dim3(LZX_TRUSS_BLOCK), 0, st, d_orp, d_oci, d_sup,
+                               n, shape.long_list, shape.stage);
             LZX_HIP(hipGetLastError());
         }
         const u32 gs = std::min<u32>(np, ge);
@@ -540,59 +485,34 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     // ---- the peel.  Lanes per edge: about half the mean row length.  Edges whose shorter row has more than 64 G entries go to the
     // long-row launch, which runs only when the graph has such a row ----
     const u32 G = lzx_lanes_per_row(c, nnz, 32);
-    const u32 long_row = c->truss_long_opt > 0 ? (u32)std::min<int64_t>(c->truss_long_opt, 0xffffffff) : 64 * G;
-    const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (4 * LZX_TRUSS_BLOCK), 1), LZX_TRUSS_SLICES);
+    const u32 long_row = lzx_shape_or(c->truss_long_opt, 64 * G);
+    const u32 slices = lzx_peel_slices(c->max_degree, LZX_TRUSS_BLOCK);
     TrussPeel p = {c->d_row_ptr, c->d_col_idx, d_eid, d_src, d_oci, d_sup, d_mark, d_truss, d_queue, d_counters, m, 0, 0, 0, 0, long_row};
     LZX_HIP(hipEventRecord(run.ev0, st));
-    u32 s = 0, rounds = 0, levels = 0;
-    u32 queued = 0;        // the queue's end: edges marked so far
-    u32 level_pos = 0;     // the queue position at which the current level began
-    while (queued < m) {
-        // ---- the frontier is empty: the next level.  s + 1 first (0 at the start); the minimum if that appends nothing ----
-        u32 s_try = levels == 0 ? 0u : (s == LZX_TRUSS_NONE ? s : s + 1);
-        u32 end = queued;
-        for (int attempt = 0; attempt < 2 && end == queued; ++attempt) {
-            u32 words[2] = {0, 0};
-            LZX_HIP(hipMemsetAsync(d_counters + 1, 0xff, sizeof(u32), st));
-            hipLaunchKernelGGL(k_truss_level, dim3(ge), dim3(LZX_TRUSS_BLOCK), 0, st, d_sup, d_mark, d_truss, d_queue, d_counters, m, s_try, rounds + 1);
+    LzxPeelResult peel;
+    LZX_TRY(lzx_peel_loop(
+        fn_name, {"edge", "remaining support", "edges"}, st, d_counters, m,
+        [&](u32 s_try, u32 r) -> int {
+            hipLaunchKernelGGL(k_peel_level, dim3(lzx_row_grid(m, LZX_PEEL_BLOCK)), dim3(LZX_PEEL_BLOCK), 0, st, d_sup, d_mark, d_truss, d_queue, d_counters, m, s_try, s_try + 2, r);
             LZX_HIP(hipGetLastError());
-            LZX_HIP(hipMemcpyAsync(words, d_counters, sizeof(words), hipMemcpyDeviceToHost, st));
-            LZX_HIP(hipStreamSynchronize(st));
-            end = std::min(words[0], m);
-            if (end == queued) s_try = words[1];   // nobody at this level: the smallest remaining support is the next
-        }
-        if (end == queued) LZX_FAIL(LZX_ERR_LIMIT, "%s: no edge of remaining support %u among the %u left after %u rounds", fn_name, s_try, m - queued, rounds);
-        s = s_try;
-        ++levels;
-        level_pos = queued;
-        u32 wbeg = queued;
-        queued = end;
-        // ---- the rounds of this level: window [wbeg, queued) ----
-        for (;;) {
-            ++rounds;
-            if ((u64)rounds > (u64)m + 1) LZX_FAIL(LZX_ERR_LIMIT, "%s: %u rounds on %u edges", fn_name, rounds, m);
-            if (queued >= m) break;   // everything is queued: the last window has nobody left to push to
+            return LZX_OK;
+        },
+        [&](u32 wbeg, u32 wlen, u32 s, u32 r) -> int {
             p.wbeg = wbeg;
-            p.wlen = queued - wbeg;
+            p.wlen = wlen;
             p.s = s;
-            p.r = rounds;
+            p.r = r;
             lzx_with_lanes<32>(G, [&](auto g) {
-                hipLaunchKernelGGL(k_truss_peel<g>, dim3(lzx_row_grid(p.wlen, LZX_TRUSS_BLOCK / g)), dim3(LZX_TRUSS_BLOCK), 0, st, p);
+                hipLaunchKernelGGL(k_truss_peel<g>, dim3(lzx_row_grid(wlen, LZX_TRUSS_BLOCK / g)), dim3(LZX_TRUSS_BLOCK), 0, st, p);
             });
             LZX_HIP(hipGetLastError());
             if (c->max_degree > long_row) {
-                hipLaunchKernelGGL(k_truss_peel_long, dim3((p.wlen + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK, slices), dim3(LZX_TRUSS_BLOCK), 0, st, p);
+                hipLaunchKernelGGL(k_truss_peel_long, dim3((wlen + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK, slices), dim3(LZX_TRUSS_BLOCK), 0, st, p);
                 LZX_HIP(hipGetLastError());
             }
-            u32 word = 0;
-            LZX_HIP(hipMemcpyAsync(&word, d_counters, sizeof(u32), hipMemcpyDeviceToHost, st));
-            LZX_HIP(hipStreamSynchronize(st));
-            end = std::min(word, m);
-            if (end == queued) break;   // nothing fell to s: the level is peeled out
-            wbeg = queued;
-            queued = end;
-        }
-    }
+            return LZX_OK;
+        },
+        &peel));
     LZX_HIP(hipEventRecord(run.ev1, st));
 
     // ---- hand back: one gather through eid per per-entry output (mark holds the layers), one row pass for the vertices ----
@@ -621,11 +541,11 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     if (info) {
         info->edges = m;
         info->triangles = sup_sum / 3;
-        info->main_truss_edges = m ? (u64)m - level_pos : 0;
+        info->main_truss_edges = m ? (u64)m - peel.level_pos : 0;
         info->max_support = (u32)sup_max;
-        info->max_truss = m ? s + 2 : 0;
-        info->levels = levels;
-        info->rounds = rounds;
+        info->max_truss = m ? peel.level + 2 : 0;
+        info->levels = peel.levels;
+        info->rounds = peel.rounds;
         info->loop_ms = lzx_ms_since(t0);
         info->support_ms = support_ms;
         info->peel_ms = peel_ms;
