@@ -995,8 +995,9 @@ int lzx_similarity(lzx_handle h, uint64_t np, const uint32_t *u, const uint32_t 
  *             LZX_ERR_NOMEM: as above.  The labels are checked before the device is touched.
  *   limits    resolution 1 only; the accumulators cross PCIe, 16 n bytes per call; and the common limits below.
  *
- *   limits    (all three) one GPU handle; undirected, unweighted graphs; no Louvain or Leiden, which need the weighted
- *             aggregation a pattern-only CSR does not have; no asynchronous or seeded-random label propagation.  A matrix that is
+ *   limits    (all three) one GPU handle; undirected, unweighted graphs; Louvain is lzx_louvain below, and what is still
+ *             missing is Leiden's refinement, a resolution parameter and weighted input; no asynchronous or seeded-random label
+ *             propagation.  A matrix that is
  *             not symmetric is not detected: its numbers mean nothing, but the calls return and stay within their memory --
  *             appends are clamped, rounds and sweeps are capped, every label is a vertex id. */
 #define LZX_COLOR_TIES_BY_ID 1u
@@ -1030,6 +1031,102 @@ typedef struct lzx_modularity_info {
     double   loop_ms;
 } lzx_modularity_info;
 int lzx_modularity(lzx_handle h, const uint32_t *labels /* [n], values < n */, double *q, lzx_modularity_info *info /* or NULL */);
+
+/* ---- Louvain communities --------------------------------------------------------------------------------
+ * lzx_louvain: the communities of the Louvain method (Blondel et al.; networkx.community.louvain_communities and
+ * louvain_partitions) on the handle's graph read as undirected and unweighted: local moves that raise the modularity, then the
+ * communities become the nodes of a weighted level graph, and again, until a level changes nothing.  The result is canonical: a
+ * function of the graph, the seed and the flag, formed in integers only.
+ *   outputs   A LEVEL GRAPH has n_l nodes, rows ascending by column and a weight w_ij >= 1 (u32) per stored entry; w_ii, the inner
+ *             weight, counts both directions.  Level 0 is the caller-order pattern with w_ij = 1 off the diagonal and a diagonal entry
+ *             ignored (w_ii = 0).  k_i = the sum of row i with the diagonal; M = the sum of the k_i, the same on every level (the
+ *             off-diagonal entries); d_i = the off-diagonal ENTRIES of row i.  Every level graph is coloured as lzx_color(seed, flags)
+ *             colours it: the order is (d descending, hash(seed, i) ascending, i ascending), i the node's id on that level.
+ *             A SWEEP starts from label[i] = i, tot[c] = k_c on the level's first sweep and takes the colour classes in ascending
+ *             colour.  Every node i of the class with d_i > 0 decides from the labels and tot as they stand when its class begins:
+ *             a = label[i]; for every label c among the neighbours j != i, k_ic = the sum of w_ij over those with label[j] = c
+ *             (k_ia = 0 if a does not occur); T_c = tot[c], T_a = tot[a] - k_i; G(c) = M k_ic - T_c k_i; c* = the c != a of the
+ *             largest G, ties to the smallest c; i moves to c* iff G(c*) > G(a).  When the whole class has decided, label[i] = c*,
+ *             tot[a] -= k_i, tot[c*] += k_i for every mover.  The nodes of a class share no edge, so every k_ic is exact and only
+ *             tot is one class stale.  A LEVEL: Qnum = M I - the sum of tot[c]^2, I = the sum over i of w_ii + the w_ij of the
+ *             j != i with label[j] = label[i].  A sweep without a move ends the level.  Otherwise, if Qnum after the sweep is <=
+ *             Qnum before it, the labels and tot from before the sweep are put back, the level ends and reverted = 1 (the sweep is
+ *             counted in sweeps, its moves are not counted).  Otherwise its moves are added and the next sweep runs; after
+ *             max_sweeps accepted sweeps the level ends with capped = 1, which is no error.  AGGREGATION: the distinct labels in
+ *             ascending order become the nodes 0 .. C-1 of the next level, w'_pq = the sum of the w_ij over all entries (diagonal
+ *             included) between p and q.  If C = n_l the level changed nothing: it is not counted and the call is done; it is also
+ *             done after max_levels counted levels, which is no error.
+ *             labels[v] = the SMALLEST ORIGINAL VERTEX ID of v's final community (a vertex without an edge is its own);
+ *             level_labels[l][v] = the same for the partition after counted level l; levels[l] = that level's record.  Rows of
+ *             level_labels and levels at or beyond info.levels are left untouched.  Each of the three may be NULL.
+ *   levels[l] nodes, entries (stored entries of the level graph: level 0's diagonal entries count), communities (C), moves (of the
+ *             accepted sweeps), inner_entries (I) and sum_degree_sq (the sum of tot^2) after the level; colors and color_rounds of
+ *             its colouring; sweeps (every sweep that ran: the last one without a move, or taken back, included); reverted; capped;
+ *             path_rows[3] = the rows the decide step gave to each of its three paths in one sweep, by stored row length (rows
+ *             without an entry are rows of the first).
+ *   info      (or NULL) n_communities, largest_size, largest_label (ties to the smallest label); levels = the counted levels; sweeps
+ *             and moves summed over them; inner_entries, entries, sum_degree_sq and modularity of labels exactly as lzx_modularity
+ *             gives them; the host clock of the call; the device event times of the colourings, the sweeps and the aggregations.
+ *   method    Per level: the colouring and the class sort of lzx_label_propagation on a view of the level graph; the far tables of
+ *             its rows above 2 048 entries; an init launch (k, tot, labels, I); then per sweep and class one decide launch per path
+ *             that has rows, templated on whether a weight array is read (level 0 reads none).  Rows of at most 128 entries: a
+ *             group of lanes stages labels and weights in its LDS slice, every lane sums the weights of the equal labels for its
+ *             own entries, gathers tot, forms G in int64, and (G, smallest c) is max-reduced over the group.  Rows of at most
+ *             2 048: a workgroup and the 4 096-slot LDS table, the count slot a weight sum; every slot forms its G and the pair is
+ *             max-reduced over the workgroup.  Longer rows: the table in global memory, an insert launch by up to 64 workgroups
+ *             per row and a pick launch.  A mover writes its own label in place (nobody in its class reads it) and is appended,
+ *             one atomic per wavefront, to a move list of (i, a, c*, k_ic* - k_ia); tot is NOT written while a class decides.  A
+ *             second launch over the class's window of the list applies tot[a] -= k_i, tot[c*] += k_i with 32-bit integer atomics
+ *             and adds 2 (k_ic* - k_ia) to I with one 64-bit integer atomic per wavefront: exact, since the movers of a class are
+ *             not adjacent.  The sum of tot^2 is a reduction over n_l words per sweep.  The host reads the move count and the two
+ *             integers of Qnum once per sweep.  Aggregation: flag the labels that occur, exclusive scan, every entry becomes the
+ *             64-bit key p << 32 | q with its weight (level 0's diagonal entries are dropped here), a hipcub radix sort by key, a
+ *             reduce by key, the row pointers by binary search in the keys.  The map vertex -> node of the level stays on the
+ *             device; the canonical labels are lzx_label_propagation's kernels.  No floating point and no floating-point atomic
+ *             before the modularity of the result; no kernel waits on another workgroup; every loop is bounded by a row length, a
+ *             table size or a cap; every append is clamped.
+ *   bits      labels, level_labels and every integer of levels and info are canonical: G is an integer, the arg-max is under a
+ *             total order, the sums of the aggregation are integers, so nothing depends on the path a row takes or on any thread
+ *             order.  modularity: bit for bit lzx_modularity's value of labels.
+ *   state     the call touches none of the handle's.  Everything it allocates is freed before it returns, on every path:
+ *             16 n + 56 n' + 12 min(n, 65536) + 128 bytes for the vertices (n' = n rounded up to even, the third term rounded up to
+ *             8), held through the call; 8 pow2ceil(2 len) bytes for every row of more than 2 048 entries of the level at hand;
+ *             from the first aggregation on 16 nnz + 8 nnz' + 16 bytes of keys and weights plus hipcub's scratch for nnz pairs; and
+ *             8 (C + 1) + 8 E' bytes for the level graph at hand (C nodes, E entries rounded up to even), the next one beside it
+ *             while it is built.
+ *   errors    LZX_ERR_ARG: null handle, a flag bit other than LZX_COLOR_TIES_BY_ID, max_sweeps == 0, max_levels == 0 or > 64.
+ *             LZX_ERR_STATE: no graph, a handle with a communicator, a graph from a sharded hand-over.  LZX_ERR_LIMIT: 2^31 stored
+ *             entries or more (M is at most the stored entries; below 2^31 every G, Qnum and tot^2 fits a signed 64-bit integer and
+ *             tot, k and every k_ic fit u32); a row of 2^30 entries or more; the colouring's own limits.  LZX_ERR_NOMEM: the message
+ *             states the bytes held and asked for, at every allocation.  The checks that need no device come first.
+ *   limits    one GPU handle; undirected, unweighted input; resolution 1; no refinement step (Leiden), so a community can be
+ *             internally disconnected; one colouring per level; one launch per colour class and path in every sweep; the guard
+ *             compares whole sweeps, so a sweep that is taken back ends the level even if part of it was an improvement; the
+ *             aggregation sorts all entries of the level (24 nnz bytes and hipcub's scratch at level 0); and a matrix that is not
+ *             symmetric is not detected: its numbers mean nothing, but the call returns and stays within its memory. */
+typedef struct lzx_louvain_level {
+    uint64_t nodes, entries;       /* of the level graph */
+    uint64_t communities;          /* C: the nodes of the next level */
+    uint64_t moves;                /* of the accepted sweeps */
+    uint64_t inner_entries;        /* I after the level */
+    uint64_t sum_degree_sq;        /* the sum of tot^2 after the level */
+    uint32_t colors, color_rounds; /* of the level's colouring */
+    uint32_t sweeps;               /* every sweep that ran */
+    uint32_t reverted, capped;     /* the last sweep was taken back; max_sweeps accepted sweeps ran */
+    uint32_t path_rows[3];         /* rows per decide path in one sweep */
+} lzx_louvain_level;
+typedef struct lzx_louvain_info {
+    uint64_t n_communities, largest_size;
+    uint64_t sweeps, moves;        /* over the counted levels */
+    uint64_t inner_entries, entries, sum_degree_sq;  /* lzx_modularity's integers of labels */
+    uint32_t largest_label;        /* of the largest community; ties go to the smallest label */
+    uint32_t levels;               /* counted levels */
+    double   modularity;
+    double   loop_ms, color_ms, sweep_ms, aggregate_ms;  /* host clock of the call; device event times */
+} lzx_louvain_info;
+int lzx_louvain(lzx_handle h, uint64_t seed, uint32_t flags, uint32_t max_sweeps, uint32_t max_levels /* 1 .. 64 */,
+                uint32_t *labels /* [n] or NULL */, uint32_t *level_labels /* [max_levels][n] or NULL */,
+                lzx_louvain_level *levels /* [max_levels] or NULL */, lzx_louvain_info *info /* or NULL */);
 
 /* ---- sweep cuts ----------------------------------------------------------------------------------------
  * lzx_sweep_cut: what turns a score vector -- a Fiedler vector of lzx_eigsh_f64, a personalised lzx_pagerank_f64, a heat kernel

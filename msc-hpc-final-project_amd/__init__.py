@@ -25,7 +25,7 @@ PRODUCT_OPTIONS = ("hub_entries", "propagation_blocking", "overlap_exchange", "s
 SHAPE_OPTIONS = ("pb_reduce", "pb_target", "pb_unit", "pb_column_band", "pb_run_align", "pb_taper", "pb_dyn_share", "pb_carry_scan", "pb_scatter_nt", "pb_gather_grid", "pb_gather_nt", "spmv_wgs", "pb_group", "pb_group_force",
                  "narrow_slices", "tie_sort", "long_row", "item_len", "exchange_at_world_1", "isolated_rows", "unnormalised_basis", "fuse_staged", "start_vector_scan", "defer_finish",
                  "multi_row_chunk", "eig_basis_bytes", "solve_state_bytes", "solve_poll", "bfs_state_bytes", "tri_long_list", "tri_state_bytes", "core_long_row", "core_state_bytes",
-                 "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes",
+                 "truss_long_row", "truss_state_bytes", "color_long_row", "lpa_group_row", "lpa_table_row", "lpa_state_bytes", "louvain_state_bytes",
                  "sweep_long_row", "sweep_state_bytes", "sim_long_pair", "sim_slice", "sim_state_bytes", "graph_lanes")
 
 LZX_BRANDES_ENDPOINTS = 1  # include/lzx.h: lzx_brandes_f64's flag, bc counts the endpoints of every path too
@@ -186,6 +186,25 @@ class LzxModularityInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class LzxLouvainLevel(ctypes.Structure):
+    _fields_ = [("nodes", ctypes.c_uint64), ("entries", ctypes.c_uint64), ("communities", ctypes.c_uint64), ("moves", ctypes.c_uint64),
+                ("inner_entries", ctypes.c_uint64), ("sum_degree_sq", ctypes.c_uint64), ("colors", ctypes.c_uint32), ("color_rounds", ctypes.c_uint32),
+                ("sweeps", ctypes.c_uint32), ("reverted", ctypes.c_uint32), ("capped", ctypes.c_uint32), ("path_rows", ctypes.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {f: (list(getattr(self, f)) if f == "path_rows" else getattr(self, f)) for f, _ in self._fields_}
+
+
+class LzxLouvainInfo(ctypes.Structure):
+    _fields_ = [("n_communities", ctypes.c_uint64), ("largest_size", ctypes.c_uint64), ("sweeps", ctypes.c_uint64), ("moves", ctypes.c_uint64),
+                ("inner_entries", ctypes.c_uint64), ("entries", ctypes.c_uint64), ("sum_degree_sq", ctypes.c_uint64),
+                ("largest_label", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("modularity", ctypes.c_double), ("loop_ms", ctypes.c_double),
+                ("color_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double), ("aggregate_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class LzxSweepResult(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint64), ("cut", ctypes.c_uint64), ("vol", ctypes.c_uint64), ("den", ctypes.c_uint64), ("value", ctypes.c_double)]
 
@@ -279,6 +298,8 @@ SYMBOLS = [
     ("lzx_color", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxColorInfo)]),
     ("lzx_label_propagation", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(LzxCommunitiesInfo)]),
     ("lzx_modularity", ctypes.c_int, [_h, _u32p, _f64p, ctypes.POINTER(LzxModularityInfo)]),
+    ("lzx_louvain", ctypes.c_int, [_h, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, ctypes.POINTER(LzxLouvainLevel),
+                                   ctypes.POINTER(LzxLouvainInfo)]),
     ("lzx_sweep_cut", ctypes.c_int, [_h, ctypes.c_uint32, _f64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u32p, _u64p, _u64p,
                                      ctypes.POINTER(LzxSweepResult), ctypes.POINTER(LzxSweepInfo)]),
     ("lzx_similarity", ctypes.c_int, [_h, ctypes.c_uint64, _u32p, _u32p, ctypes.c_uint32, _u32p, _u32p, _u32p, _f64p,
@@ -1480,6 +1501,40 @@ class Engine:
         if not keep.any():
             raise ValueError(f"community: no vertex has the label {which}")
         return self.induced(keep, **options)
+
+    # ---- Louvain communities (include/lzx.h: lzx_louvain) ----
+    def louvain_raw(self, seed: int = 0, ties_by_id: bool = False, max_sweeps: int = 100, max_levels: int = 32, want_labels: bool = True,
+                    want_level_labels: bool = True):
+        """(labels, level_labels, levels, info) of lzx_louvain: local moves over the colour classes of every level graph, then
+        aggregation, until a level changes nothing.  labels[v] = the smallest vertex id of v's final community (uint32, the caller's
+        order; None with want_labels=False); level_labels = the same for the partition after every counted level, (info["levels"], n)
+        (None with want_level_labels=False); levels = one dict of the lzx_louvain_level fields per counted level; info = the
+        lzx_louvain_info fields.  Everything but the timings is a function of the graph, the seed and the tie rule."""
+        labels = np.empty(self.n, dtype=np.uint32) if want_labels else None
+        per_level = np.empty((int(max_levels), self.n), dtype=np.uint32) if want_level_labels and 1 <= int(max_levels) <= 64 else None
+        records = (LzxLouvainLevel * max(min(int(max_levels), 64), 1))()
+        info = LzxLouvainInfo()
+        _check(self.L.lzx_louvain(self.h, int(seed), LZX_COLOR_TIES_BY_ID if ties_by_id else 0, int(max_sweeps), int(max_levels),
+                                  _p(labels, _u32p) if want_labels else None, _p(per_level, _u32p) if per_level is not None else None, records,
+                                  ctypes.byref(info)), "lzx_louvain", self.L)
+        return (labels, None if per_level is None else per_level[:info.levels], [records[l].as_dict() for l in range(info.levels)],
+                info.as_dict())
+
+    @staticmethod
+    def _parts_of(labels):
+        order = np.argsort(labels, kind="stable")
+        parts = np.split(order, np.flatnonzero(np.diff(labels[order])) + 1) if len(labels) else []
+        return sorted(parts, key=lambda part: (-len(part), int(part[0])))
+
+    def louvain_communities(self, seed: int = 0, ties_by_id: bool = False, max_sweeps: int = 100, max_levels: int = 32):
+        """networkx.community.louvain_communities at resolution 1: a list of index arrays (int64, ascending), ordered as
+        label_propagation_communities orders them."""
+        return self._parts_of(self.louvain_raw(seed, ties_by_id, max_sweeps, max_levels, want_level_labels=False)[0])
+
+    def louvain_partitions(self, seed: int = 0, ties_by_id: bool = False, max_sweeps: int = 100, max_levels: int = 32):
+        """networkx.community.louvain_partitions: one such list per level, the finest first; none on a graph no level changes."""
+        per_level = self.louvain_raw(seed, ties_by_id, max_sweeps, max_levels, want_labels=False)[1]
+        return [self._parts_of(row) for row in per_level]
 
     # ---- sweep cuts, spectral bisection, local clusters (include/lzx.h: lzx_sweep_cut; DESIGN.md section 22) ----
     def sweep_cut_raw(self, scores, ascending: bool = False, per_degree: bool = False, objective: str = "conductance", k_min: int = 0,

@@ -179,6 +179,7 @@ static const Option g_options[] = {
     {"lpa_group_row", &lzx_ctx::lpa_group_opt, OPT_SHAPE},
     {"lpa_table_row", &lzx_ctx::lpa_table_opt, OPT_SHAPE},
     {"lpa_state_bytes", &lzx_ctx::lpa_cap_opt, OPT_SHAPE},
+    {"louvain_state_bytes", &lzx_ctx::louvain_cap_opt, OPT_SHAPE},   // lzx_louvain: the same cap, at each of its allocations
     // lzx_sweep_cut: rows with more than this many entries take the long-row launch (default 64 times the lanes per row); a state of
     // more than this many bytes is out of device memory
     {"sweep_long_row", &lzx_ctx::sweep_long_opt, OPT_SHAPE},

@@ -1,7 +1,9 @@
 // lzx_communities.hip -- greedy colouring, label-propagation communities and modularity of the handle's graph
 // (networkx.coloring.greedy_color, networkx.community.label_propagation_communities, networkx.community.modularity), on the
 // device over the caller-order CSR the handle keeps (d_row_ptr / d_col_idx): include/lzx.h, lzx_color, lzx_label_propagation and
-// lzx_modularity; DESIGN.md section 21.
+// lzx_modularity; DESIGN.md section 21.  The colouring, the counting passes, the class sort, the far tables, the canonical labels and
+// the modularity read a graph through an LzxGraphView (lzx_communities_shared.h): the three calls here pass the handle's, lzx_louvain
+// (lzx_louvain.hip) the level graph at hand.
 //
 // Definitions.  d_v = the entries of row v without the diagonal; a diagonal entry is skipped in every walk.
 //   order        u comes before v iff d_u > d_v, or the degrees are equal and hash(u) < hash(v) (the header's probe hash with
@@ -60,41 +62,11 @@
 
 #include "lzx_internal.h"
 #include "lzx_graph_call.h"
+#include "lzx_communities_shared.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
-static constexpr u32 LZX_COM_BLOCK = 256;
-static constexpr u32 LZX_COM_NONE = 0xffffffffu;
-static constexpr u32 LZX_COLOR_CAP = 1u << 16;    // colours are below this: the LDS bitmap's bits, the histogram's classes
-static constexpr u32 LZX_LPA_STAGE = 128;         // labels a group of lanes stages in LDS
-static constexpr u32 LZX_LPA_SLOTS = 4096;        // slots of the LDS table
-static constexpr u32 LZX_LPA_MAX_ROW = 1u << 30;  // a longer row's table would have more than 2^31 slots
-// the counter words
-enum { CW_END = 0, CW_COLORS = 1, CW_CHANGED = 2, CW_LONG = 3, CW_COMMUNITIES = 4, CW_KEY = 8, CW_WORDS = 16 };
-
-// ---- the order ------------------------------------------------------------------------------------------------------------
-struct ColorOrder {
-    const u32 *d;
-    u64 seed;
-    u32 by_id;
-    __device__ __forceinline__ u64 hash(u32 v) const
-    {
-        u64 h = seed + 0x9E3779B97F4A7C15ull * ((u64)v + 1);
-        h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 27; h *= 0x94D049BB133111EBull; h ^= h >> 31;
-        return h;
-    }
-    // u comes before v
-    __device__ __forceinline__ bool before(u32 u, u32 v) const
-    {
-        const u32 du = d[u], dv = d[v];
-        if (du != dv) return du > dv;
-        if (!by_id) {
-            const u64 hu = hash(u), hv = hash(v);
-            if (hu != hv) return hu < hv;
-        }
-        return u < v;
-    }
-};
+// ---- the order (ColorOrder: lzx_communities_shared.h) -------------------------------------------------------------------------
 // what k_row_count counts in row v: the earlier neighbours; the neighbours with v's label
 struct PredEarlier {
     ColorOrder o;
@@ -104,28 +76,6 @@ struct PredSameLabel {
     const u32 *label;
     __device__ __forceinline__ bool operator()(u32 v, u32 u) const { return label[u] == label[v]; }
 };
-
-// The calling lanes for which `active` holds add one to bins[key] each, the lanes of one key with one atomic.  Every lane of the
-// wavefront must call it together.  Returns the lane's place in its bin: the count before the wavefront plus its rank among the
-// wavefront's lanes of the same key (meaningless where !active).
-__device__ __forceinline__ u32 wave_bucket_add(bool active, u32 key, u32 *bins)
-{
-    const u32 lane = threadIdx.x & 63;
-    u32 place = 0;
-    ull todo = __ballot(active);
-    while (todo) {   // (the same trips for every lane; at most 64)
-        const int leader = __builtin_ctzll(todo);
-        const u32 k0 = (u32)__shfl((int)key, leader, 64);
-        const bool mine = active && key == k0;
-        const ull same = __ballot(mine);
-        u32 base = 0;
-        if (lane == (u32)leader) base = atomicAdd(&bins[k0], (u32)__builtin_popcountll(same));
-        base = (u32)__shfl((int)base, leader, 64);
-        if (mine) place = base + (u32)__builtin_popcountll(same & ((1ull << lane) - 1ull));
-        todo &= ~same;
-    }
-    return place;
-}
 
 // ---- rows counted under a predicate -----------------------------------------------------------------------------------------
 // out[v] = the entries u != v of row v with pred(v, u): rows of at most long_row entries, G lanes per row
@@ -415,23 +365,6 @@ k_lpa_group(const u64 *row_ptr, const u32 *col_idx, u32 *label, const u32 *cls, 
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[CW_CHANGED], (u32)__builtin_popcountll(m));
 }
 
-// An open-addressing table of `slots` (a power of two) keys and counts.  A key is the label + 1 and 0 an empty slot, so that a
-// cleared table is all zeros.  One neighbour's label: atomicCAS on the key slot, atomicAdd on the count, linear probing bounded by
-// the slot count (the table is never more than half full).
-__device__ __forceinline__ void lpa_insert(u32 *keys, u32 *counts, u32 slots, u32 mine, u32 times)
-{
-    const u32 x = mine * 0x9E3779B1u;
-    u32 h = (x ^ (x >> 16)) & (slots - 1);
-    for (u32 probe = 0; probe < slots; ++probe) {
-        const u32 prev = atomicCAS(&keys[h], 0u, mine + 1);
-        if (prev == 0u || prev == mine + 1) {
-            atomicAdd(&counts[h], times);
-            break;
-        }
-        h = (h + 1) & (slots - 1);
-    }
-}
-
 // The labels of a wavefront's lanes (have: this lane holds one).  The lanes that agree with the first lane's label, and then with
 // the first of the rest, are inserted as one -- late in a run most neighbours of a hub carry one label, and a hundred thousand
 // atomics on one address are to be avoided; what is left inserts for itself.  Every lane of the wavefront must call it together.
@@ -449,14 +382,6 @@ __device__ __forceinline__ void lpa_insert_wave(bool have, u32 mine, u32 *keys, 
         todo &= ~same;
     }
     if (have) lpa_insert(keys, counts, slots, mine, 1u);
-}
-
-// pow2ceil(2 len), at least 2 and at most cap
-__device__ __forceinline__ u32 lpa_slots(u64 len, u32 cap)
-{
-    u32 slots = 2;
-    while (slots < 2 * len && slots < cap) slots *= 2;
-    return slots;
 }
 
 // the workgroup's largest key (in thread 0) becomes v's label
@@ -609,53 +534,46 @@ k_mod_add(const u32 *label, const u32 *d, const u32 *inner, ull *D, ull *I, u32 
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-struct ColorState {
-    u32 *d, *wait, *colour, *queue, *bins, *counters;
-};
-struct ColorResult {
-    u32 colours = 0, rounds = 0, largest_class = 0;
-    float ms = 0.f;
-    std::vector<u32> run;   // 3 colours + 1: where the (colour, path) runs of the sorted classes begin
-};
-
-inline u64 even(u64 x) { return (x + 1) & ~1ull; }
-inline u64 class_bins(u32 n) { return even(3 * (u64)std::min<u32>(n, LZX_COLOR_CAP)); }
-inline u32 vertex_grid(u32 n) { return (n + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK; }
-inline u32 lanes_of(lzx_ctx *c) { return lzx_lanes_per_row(c, c->nnz, 32); }
-
 // out[v] = the entries of row v that satisfy pred: both launches
 template <typename P>
-int count_rows(lzx_ctx *c, P pred, u32 *out, u32 G, u32 long_row)
+int count_rows(lzx_ctx *c, const LzxGraphView &g_, P pred, u32 *out, u32 G, u32 long_row)
 {
-    const u32 n = (u32)c->n;
+    const u32 n = g_.n;
     lzx_with_lanes<32>(G, [&](auto g) {
-        hipLaunchKernelGGL((k_row_count<g, P>), dim3(lzx_row_grid(n, LZX_COM_BLOCK / g)), dim3(LZX_COM_BLOCK), 0, c->stream, c->d_row_ptr,
-                           c->d_col_idx, pred, out, n, long_row);
+        hipLaunchKernelGGL((k_row_count<g, P>), dim3(lzx_row_grid(n, LZX_COM_BLOCK / g)), dim3(LZX_COM_BLOCK), 0, c->stream, g_.row_ptr,
+                           g_.col_idx, pred, out, n, long_row);
     });
     LZX_HIP(hipGetLastError());
-    if (c->max_degree > long_row) {
-        hipLaunchKernelGGL(k_row_count_long<P>, dim3(vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, c->stream, c->d_row_ptr, c->d_col_idx, pred, out, n,
+    if (g_.max_row > long_row) {
+        hipLaunchKernelGGL(k_row_count_long<P>, dim3(lzx_vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, c->stream, g_.row_ptr, g_.col_idx, pred, out, n,
                            long_row);
         LZX_HIP(hipGetLastError());
     }
     return LZX_OK;
 }
+}   // namespace
 
-// The colouring into s.colour and, with `sorted`, the classes into s.queue, one run per (colour, path).  run.ev0 / ev1 exist.
-int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 flags, const ColorState &s, bool sorted, u32 group_row,
-               u32 table_row, ColorResult *res)
+int lzx_color_degrees(lzx_ctx *c, const LzxGraphView &g, u32 *d, u32 *colour, u32 *counters)
 {
-    const u32 n = (u32)c->n;
+    hipLaunchKernelGGL(k_color_degrees, dim3(std::max(lzx_vertex_grid(g.n), 1u)), dim3(LZX_COM_BLOCK), 0, c->stream, g.row_ptr, g.col_idx, d, colour,
+                       counters, g.n);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
+
+int lzx_color_core(lzx_ctx *c, const LzxGraphView &g, LzxGraphRun &run, const char *fn_name, u64 seed, u32 flags, const LzxColorState &s, bool sorted,
+                   u32 group_row, u32 table_row, LzxColorResult *res)
+{
+    const u32 n = g.n;
     hipStream_t st = c->stream;
-    const u32 G = lanes_of(c);
+    const u32 G = lzx_lanes_of(c, g);
     const u32 long_row = lzx_shape_or(c->color_long_opt, 64 * G);
-    const u32 gb = vertex_grid(n);
+    const u32 gb = lzx_vertex_grid(n);
     const ColorOrder order{s.d, seed, flags & LZX_COLOR_TIES_BY_ID};
 
     LZX_HIP(hipEventRecord(run.ev0, st));
-    hipLaunchKernelGGL(k_color_degrees, dim3(std::max(gb, 1u)), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, s.d, s.colour, s.counters, n);
-    LZX_HIP(hipGetLastError());
-    LZX_TRY(count_rows(c, PredEarlier{order}, s.wait, G, long_row));
+    LZX_TRY(lzx_color_degrees(c, g, s.d, s.colour, s.counters));
+    LZX_TRY(count_rows(c, g, PredEarlier{order}, s.wait, G, long_row));
     hipLaunchKernelGGL(k_color_start, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, s.wait, s.queue, s.counters, n);
     LZX_HIP(hipGetLastError());
     u32 words[2] = {0, 0};   // the queue's end, the colours
@@ -666,14 +584,14 @@ int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 
         ++rounds;
         if ((u64)rounds > (u64)n + 1) LZX_FAIL(LZX_ERR_LIMIT, "%s: %u rounds on %u vertices", fn_name, rounds, n);
         const u32 wlen = queued - wbeg;
-        lzx_with_lanes<32>(G, [&](auto g) {
-            hipLaunchKernelGGL(k_color_round<g>, dim3(lzx_row_grid(wlen, LZX_COM_BLOCK / g)), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx,
+        lzx_with_lanes<32>(G, [&](auto lanes) {
+            hipLaunchKernelGGL(k_color_round<lanes>, dim3(lzx_row_grid(wlen, LZX_COM_BLOCK / lanes)), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx,
                                order, s.wait, s.colour, s.queue, s.counters, n, wbeg, wlen, long_row);
         });
         LZX_HIP(hipGetLastError());
-        if (c->max_degree > long_row) {
-            hipLaunchKernelGGL(k_color_round_long, dim3((wlen + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr,
-                               c->d_col_idx, order, s.wait, s.colour, s.queue, s.counters, n, wbeg, wlen, long_row);
+        if (g.max_row > long_row) {
+            hipLaunchKernelGGL(k_color_round_long, dim3((wlen + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr,
+                               g.col_idx, order, s.wait, s.colour, s.queue, s.counters, n, wbeg, wlen, long_row);
             LZX_HIP(hipGetLastError());
         }
         LZX_HIP(hipMemcpyAsync(words, s.counters, sizeof(words), hipMemcpyDeviceToHost, st));
@@ -689,7 +607,7 @@ int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 
     const u32 nb = 3 * colours;
     res->run.assign((size_t)nb + 1, 0);
     LZX_HIP(hipMemsetAsync(s.bins, 0, sizeof(u32) * nb, st));
-    hipLaunchKernelGGL(k_class_sort<false>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, s.colour, s.bins, s.queue, n, colours, group_row, table_row);
+    hipLaunchKernelGGL(k_class_sort<false>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, s.colour, s.bins, s.queue, n, colours, group_row, table_row);
     LZX_HIP(hipGetLastError());
     LZX_HIP(hipMemcpyAsync(res->run.data() + 1, s.bins, sizeof(u32) * nb, hipMemcpyDeviceToHost, st));
     LZX_HIP(hipStreamSynchronize(st));
@@ -698,7 +616,7 @@ int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 
     for (u32 b = 0; b < nb; ++b) res->run[b + 1] += res->run[b];
     if (sorted) {
         LZX_HIP(hipMemcpyAsync(s.bins, res->run.data(), sizeof(u32) * nb, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_class_sort<true>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, s.colour, s.bins, s.queue, n, colours, group_row,
+        hipLaunchKernelGGL(k_class_sort<true>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, s.colour, s.bins, s.queue, n, colours, group_row,
                            table_row);
         LZX_HIP(hipGetLastError());
     }
@@ -711,23 +629,16 @@ int color_core(lzx_ctx *c, LzxGraphRun &run, const char *fn_name, u64 seed, u32 
     return LZX_OK;
 }
 
-struct ModResult {
-    double q = 0.0;
-    u64 inner = 0, entries = 0, sum_sq = 0;
-};
-
-// The modularity of the labels in d_label (device, values < n): d_d = the degrees, d_inner = scratch, u32 [n] each; D, I: u64 [n].
-// hD, hI: the accumulators on the host.
-int modularity_core(lzx_ctx *c, const u32 *d_label, const u32 *d_d, u32 *d_inner, ull *d_D, ull *d_I, std::vector<u64> &hD, std::vector<u64> &hI,
-                    ModResult *res)
+int lzx_modularity_core(lzx_ctx *c, const LzxGraphView &g, const u32 *d_label, const u32 *d_d, u32 *d_inner, ull *d_D, ull *d_I, std::vector<u64> &hD,
+                        std::vector<u64> &hI, LzxModResult *res)
 {
-    const u32 n = (u32)c->n;
+    const u32 n = g.n;
     hipStream_t st = c->stream;
-    const u32 G = lanes_of(c);
-    LZX_TRY(count_rows(c, PredSameLabel{d_label}, d_inner, G, 64 * G));
+    const u32 G = lzx_lanes_of(c, g);
+    LZX_TRY(count_rows(c, g, PredSameLabel{d_label}, d_inner, G, 64 * G));
     LZX_HIP(hipMemsetAsync(d_D, 0, sizeof(ull) * n, st));
     LZX_HIP(hipMemsetAsync(d_I, 0, sizeof(ull) * n, st));
-    hipLaunchKernelGGL(k_mod_add, dim3(vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, st, d_label, d_d, d_inner, d_D, d_I, n);
+    hipLaunchKernelGGL(k_mod_add, dim3(lzx_vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, st, d_label, d_d, d_inner, d_D, d_I, n);
     LZX_HIP(hipGetLastError());
     hD.resize(n);
     hI.resize(n);
@@ -757,7 +668,51 @@ int modularity_core(lzx_ctx *c, const u32 *d_label, const u32 *d_d, u32 *d_inner
     res->sum_sq = sq;
     return LZX_OK;
 }
-}   // namespace
+
+int lzx_lpa_far_tables(lzx_ctx *c, const LzxGraphView &g, const char *fn_name, u32 table_above, int64_t cap, u64 held, u32 *d_lpos, u32 *d_llen,
+                       u64 *d_loff, u32 *counters, void **tables, u64 *table_bytes)
+{
+    const u32 n = g.n;
+    hipStream_t st = c->stream;
+    *tables = nullptr;
+    *table_bytes = 0;
+    hipLaunchKernelGGL(k_lpa_long_rows, dim3(lzx_vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, d_lpos, d_llen, counters, n, table_above);
+    LZX_HIP(hipGetLastError());
+    u32 nl = 0;
+    LZX_HIP(hipMemcpyAsync(&nl, counters + CW_LONG, sizeof(u32), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    nl = std::min(nl, n);
+    if (!nl) return LZX_OK;
+    std::vector<u32> len(nl);
+    std::vector<u64> off((size_t)nl + 1, 0);
+    LZX_HIP(hipMemcpy(len.data(), d_llen, sizeof(u32) * nl, hipMemcpyDeviceToHost));
+    for (u32 i = 0; i < nl; ++i) {
+        u64 slots = 2;
+        while (slots < 2 * (u64)len[i]) slots *= 2;
+        off[i + 1] = off[i] + slots;
+    }
+    *table_bytes = 2 * off[nl] * sizeof(u32);
+    char what[128];
+    std::snprintf(what, sizeof what, "the label tables of %u rows of more than %u entries", nl, table_above);
+    LZX_TRY(lzx_alloc_state(fn_name, what, cap, held + *table_bytes, *table_bytes, tables));
+    LZX_HIP(hipMemsetAsync(*tables, 0, *table_bytes, st));
+    LZX_HIP(hipMemcpyAsync(d_loff, off.data(), sizeof(u64) * nl, hipMemcpyHostToDevice, st));
+    LZX_HIP(hipStreamSynchronize(st));   // (off goes out of scope)
+    return LZX_OK;
+}
+
+int lzx_comm_canonical(lzx_ctx *c, const u32 *d_label, u32 n, u32 *d_first, u32 *d_out, u32 *d_sizes, u32 *counters)
+{
+    hipStream_t st = c->stream;
+    const u32 gb = lzx_vertex_grid(n);
+    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_first, n, LZX_COM_NONE, 0u);
+    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_sizes, n, 0u, 0u);
+    hipLaunchKernelGGL(k_comm_first, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, d_first, n);
+    hipLaunchKernelGGL(k_comm_gather, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, (const u32 *)d_first, d_out, d_sizes, n);
+    hipLaunchKernelGGL(k_comm_stats, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_out, (const u32 *)d_sizes, counters, n);
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
 
 extern "C" int lzx_color(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t *color, lzx_color_info *info)
 {
@@ -766,16 +721,17 @@ extern "C" int lzx_color(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t *
     if (flags & ~LZX_COLOR_TIES_BY_ID) LZX_FAIL(LZX_ERR_ARG, "%s: unknown flag bits 0x%x (LZX_COLOR_TIES_BY_ID is the only flag)", fn_name, flags & ~LZX_COLOR_TIES_BY_ID);
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
+    const LzxGraphView g = lzx_view_of(c);
 
     // one arena: d, wait, colour, queue (u32 [n] each, rounded to 8 bytes), three bins per colour, the counter words
-    const u64 n_al = even(n), nb = class_bins(n);
+    const u64 n_al = lzx_even(n), nb = lzx_class_bins(n);
     const u64 bytes = (4 * n_al + nb + CW_WORDS) * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
     LzxGraphRun run(c);
     char what[96];
     std::snprintf(what, sizeof what, "the state of %u vertices (degrees, waits, colours, the queue)", n);
     LZX_TRY(lzx_alloc_state(fn_name, what, -1, bytes, bytes, &run.arena));
-    ColorState s;
+    LzxColorState s;
     s.d = static_cast<u32 *>(run.arena);
     s.wait = s.d + n_al;
     s.colour = s.wait + n_al;
@@ -784,8 +740,8 @@ extern "C" int lzx_color(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t *
     s.counters = s.bins + nb;
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
-    ColorResult res;
-    LZX_TRY(color_core(c, run, fn_name, seed, flags, s, false, 0xffffffffu, 0xffffffffu, &res));
+    LzxColorResult res;
+    LZX_TRY(lzx_color_core(c, g, run, fn_name, seed, flags, s, false, 0xffffffffu, 0xffffffffu, &res));
     if (color) LZX_HIP(hipMemcpyAsync(color, s.colour, sizeof(u32) * n, hipMemcpyDeviceToHost, c->stream));
     LZX_HIP(hipStreamSynchronize(c->stream));
     if (info) {
@@ -809,13 +765,14 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     if (c->max_degree >= LZX_LPA_MAX_ROW) LZX_FAIL(LZX_ERR_LIMIT, "%s: a row of %llu entries; rows of 2^30 entries or more are not supported", fn_name, (ull)c->max_degree);
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
+    const LzxGraphView g = lzx_view_of(c);
     hipStream_t st = c->stream;
     const u32 group_row = c->lpa_group_opt > 0 ? (u32)std::min<int64_t>(c->lpa_group_opt, LZX_LPA_MAX_ROW) : LZX_LPA_STAGE;
     const u32 table_row = c->lpa_table_opt > 0 && c->lpa_table_opt < LZX_LPA_SLOTS / 2 ? (u32)c->lpa_table_opt : LZX_LPA_SLOTS / 2;
 
     // one arena: D, I (u64 [n]), d, wait, colour, queue, label (u32 [n] each, rounded to 8 bytes), three bins per colour, the counter
     // words; the tables of the rows above table_row follow once they are known
-    const u64 n_al = even(n), nb = class_bins(n);
+    const u64 n_al = lzx_even(n), nb = lzx_class_bins(n);
     const u64 bytes = 2 * (u64)n * sizeof(u64) + (5 * n_al + nb + CW_WORDS) * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
     LzxGraphRun run(c);
@@ -823,7 +780,7 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     std::snprintf(what, sizeof what, "the state of %u vertices (degrees, colours, classes, labels, the modularity's sums)", n);
     LZX_TRY(lzx_alloc_state(fn_name, what, c->lpa_cap_opt, bytes, bytes, &run.arena));
     ull *d_D = static_cast<ull *>(run.arena), *d_I = d_D + n;
-    ColorState s;
+    LzxColorState s;
     s.d = reinterpret_cast<u32 *>(d_I + n);
     s.wait = s.d + n_al;
     s.colour = s.wait + n_al;
@@ -833,10 +790,10 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     s.counters = s.bins + nb;
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
-    const u32 gb = vertex_grid(n);
+    const u32 gb = lzx_vertex_grid(n);
 
-    ColorResult col;
-    LZX_TRY(color_core(c, run, fn_name, seed, flags, s, true, group_row, table_row, &col));
+    LzxColorResult col;
+    LZX_TRY(lzx_color_core(c, g, run, fn_name, seed, flags, s, true, group_row, table_row, &col));
     const u32 *d_cls = s.queue;
 
     // the rows above table_row: their places (in `wait`, which the colouring is done with), the offsets of their tables
@@ -845,35 +802,15 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     u32 *d_tables = nullptr;
     const u32 table_above = std::max(group_row, table_row);   // (a test shape may send longer rows to the groups of lanes)
     if (c->max_degree > table_above) {
-        hipLaunchKernelGGL(k_lpa_long_rows, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, d_lpos, d_llen, s.counters, n, table_above);
-        LZX_HIP(hipGetLastError());
-        u32 nl = 0;
-        LZX_HIP(hipMemcpyAsync(&nl, s.counters + CW_LONG, sizeof(u32), hipMemcpyDeviceToHost, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        nl = std::min(nl, n);
-        std::vector<u32> len(nl);
-        std::vector<u64> off((size_t)nl + 1, 0);
-        if (nl) LZX_HIP(hipMemcpy(len.data(), d_llen, sizeof(u32) * nl, hipMemcpyDeviceToHost));
-        for (u32 i = 0; i < nl; ++i) {
-            u64 slots = 2;
-            while (slots < 2 * (u64)len[i]) slots *= 2;
-            off[i + 1] = off[i] + slots;
-        }
-        if (nl) {
-            const u64 table_bytes = 2 * off[nl] * sizeof(u32);
-            std::snprintf(what, sizeof what, "the label tables of %u rows of more than %u entries", nl, table_above);
-            LZX_TRY(lzx_alloc_state(fn_name, what, c->lpa_cap_opt, bytes + table_bytes, table_bytes, &run.more[0]));
-            d_tables = static_cast<u32 *>(run.more[0]);
-            LZX_HIP(hipMemsetAsync(d_tables, 0, table_bytes, st));
-            LZX_HIP(hipMemcpyAsync(d_loff, off.data(), sizeof(u64) * nl, hipMemcpyHostToDevice, st));
-            LZX_HIP(hipStreamSynchronize(st));   // (off goes out of scope)
-        }
+        u64 table_bytes = 0;
+        LZX_TRY(lzx_lpa_far_tables(c, g, fn_name, table_above, c->lpa_cap_opt, bytes, d_lpos, d_llen, d_loff, s.counters, &run.more[0], &table_bytes));
+        d_tables = static_cast<u32 *>(run.more[0]);
     }
 
     // ---- the sweeps ----
     hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, n, 0u, 1u);
     LZX_HIP(hipGetLastError());
-    const u32 G = lanes_of(c);
+    const u32 G = lzx_lanes_of(c, g);
     const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (8 * LZX_COM_BLOCK), 1), 64);   // workgroups that share a long row's entries
     u32 sweeps = 0;
     u64 updates = 0;
@@ -910,17 +847,12 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
 
     // ---- canonical labels (into `wait`), sizes (into `colour`), the statistics, the modularity (its scratch: `queue`) ----
     u32 *d_first = s.queue, *d_out = s.wait, *d_sizes = s.colour;
-    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_first, n, LZX_COM_NONE, 0u);
-    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_sizes, n, 0u, 0u);
-    hipLaunchKernelGGL(k_comm_first, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_label, d_first, n);
-    hipLaunchKernelGGL(k_comm_gather, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_label, (const u32 *)d_first, d_out, d_sizes, n);
-    hipLaunchKernelGGL(k_comm_stats, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_out, (const u32 *)d_sizes, s.counters, n);
-    LZX_HIP(hipGetLastError());
+    LZX_TRY(lzx_comm_canonical(c, d_label, n, d_first, d_out, d_sizes, s.counters));
     u32 words[CW_WORDS];
     LZX_HIP(hipMemcpyAsync(words, s.counters, sizeof(words), hipMemcpyDeviceToHost, st));
     std::vector<u64> hD, hI;
-    ModResult mod;
-    LZX_TRY(modularity_core(c, d_out, s.d, s.queue, d_D, d_I, hD, hI, &mod));
+    LzxModResult mod;
+    LZX_TRY(lzx_modularity_core(c, g, d_out, s.d, s.queue, d_D, d_I, hD, hI, &mod));
     if (labels) LZX_HIP(hipMemcpyAsync(labels, d_out, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
     LZX_HIP(hipStreamSynchronize(st));
     float sweep_ms = 0.f;
@@ -954,6 +886,7 @@ extern "C" int lzx_modularity(lzx_handle c, const uint32_t *labels, double *q, l
     if (!labels || !q) LZX_FAIL(LZX_ERR_ARG, "%s: null %s", fn_name, !labels ? "labels" : "q");
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
+    const LzxGraphView g = lzx_view_of(c);
     std::vector<bool> occurs(n, false);
     u64 communities = 0;
     for (u32 i = 0; i < n; ++i) {
@@ -966,7 +899,7 @@ extern "C" int lzx_modularity(lzx_handle c, const uint32_t *labels, double *q, l
     hipStream_t st = c->stream;
 
     // one arena: D, I (u64 [n]), label, d, inner (u32 [n] each, rounded to 8 bytes), the counter words
-    const u64 n_al = even(n);
+    const u64 n_al = lzx_even(n);
     const u64 bytes = 2 * (u64)n * sizeof(u64) + (3 * n_al + CW_WORDS) * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
     LzxGraphRun run(c);
@@ -976,12 +909,10 @@ extern "C" int lzx_modularity(lzx_handle c, const uint32_t *labels, double *q, l
     ull *d_D = static_cast<ull *>(run.arena), *d_I = d_D + n;
     u32 *d_label = reinterpret_cast<u32 *>(d_I + n), *d_d = d_label + n_al, *d_inner = d_d + n_al, *d_counters = d_inner + n_al;
     LZX_HIP(hipMemcpyAsync(d_label, labels, sizeof(u32) * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_color_degrees, dim3(std::max(vertex_grid(n), 1u)), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_d, (u32 *)nullptr,
-                       d_counters, n);
-    LZX_HIP(hipGetLastError());
+    LZX_TRY(lzx_color_degrees(c, g, d_d, nullptr, d_counters));
     std::vector<u64> hD, hI;
-    ModResult mod;
-    LZX_TRY(modularity_core(c, d_label, d_d, d_inner, d_D, d_I, hD, hI, &mod));
+    LzxModResult mod;
+    LZX_TRY(lzx_modularity_core(c, g, d_label, d_d, d_inner, d_D, d_I, hD, hI, &mod));
     *q = mod.q;
     if (info) {
         info->communities = communities;

@@ -1,6 +1,6 @@
 // lzx_graph_call.h -- what the graph routines on the caller-order CSR (d_row_ptr / d_col_idx) share: lzx_components,
 // lzx_bfs_multi / lzx_betweenness_f64 (lzx_paths.hip), lzx_triangles, lzx_core_numbers, lzx_truss and lzx_color /
-// lzx_label_propagation / lzx_modularity (lzx_communities.hip), lzx_sweep_cut (lzx_sweep.hip) and lzx_similarity (lzx_similarity.hip).  Host side: the preconditions of such
+// lzx_label_propagation / lzx_modularity (lzx_communities.hip), lzx_louvain (lzx_louvain.hip), lzx_sweep_cut (lzx_sweep.hip) and lzx_similarity (lzx_similarity.hip).  Host side: the preconditions of such
 // a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
 // the choice of lanes per row, a test shape in a rule's place.  Device side: the idioms of their kernels over ascending rows and
 // wavefront-aggregated queues.  What only some of them share has a header of its own on top of this one: the oriented copy and
@@ -56,15 +56,20 @@ enum LzxLanesOver { LZX_OVER_ROWS, LZX_OVER_ORIENTED };
 // graph_lanes takes the rule's place (capped at max_g as well).  What it returns goes on record for lzx_test_get_shape
 // (graph_lanes_rows / graph_lanes_oriented): the widest of a call where its launches differ -- lzx_truss peels over
 // min(that, 32) lanes per edge.
-inline u32 lzx_lanes_per_row(lzx_ctx *c, u64 entries, u32 max_g, LzxLanesOver over = LZX_OVER_ROWS)
+// (rows_of: the same rule for a graph other than the handle's, of `rows` rows that have an entry -- a level graph of lzx_louvain)
+inline u32 lzx_lanes_per_row_of(lzx_ctx *c, u64 entries, u64 rows, u32 max_g, LzxLanesOver over = LZX_OVER_ROWS)
 {
-    const u64 mean = entries / std::max<u64>(c->n_active, 1);
+    const u64 mean = entries / std::max<u64>(rows, 1);
     u32 G = 4;
     while (G < max_g && 2 * G <= mean) G *= 2;
     if (c->graph_lanes_opt > 0) G = (u32)std::min<int64_t>(c->graph_lanes_opt, max_g);
     u32 &ran = over == LZX_OVER_ORIENTED ? c->lanes_oriented_ran : c->lanes_rows_ran;
     ran = std::max(ran, G);
     return G;
+}
+inline u32 lzx_lanes_per_row(lzx_ctx *c, u64 entries, u32 max_g, LzxLanesOver over = LZX_OVER_ROWS)
+{
+    return lzx_lanes_per_row_of(c, entries, c->n_active, max_g, over);
 }
 
 // f(std::integral_constant<u32, G>{}) for G = 4, 8, ... MAX_G (32 or 64; anything else counts as MAX_G): the launch of a

@@ -373,6 +373,7 @@ struct lzx_ctx {
     int64_t lpa_group_opt = -1;        // test shape lpa_group_row: entries up to which lzx_label_propagation updates a row by a group of lanes (<= 0: 128)
     int64_t lpa_table_opt = -1;        // test shape lpa_table_row: entries up to which it counts a longer row in the LDS table (<= 0 or above it: half its slots, 2048)
     int64_t lpa_cap_opt = -1;          // test shape lpa_state_bytes: lzx_label_propagation treats a state larger than this as out of device memory
+    int64_t louvain_cap_opt = -1;      // test shape louvain_state_bytes: lzx_louvain treats a state larger than this as out of device memory, at every allocation
     int64_t sweep_long_opt = -1;       // test shape sweep_long_row: entries beyond which lzx_sweep_cut gives a row to its long-row launch (<= 0: 64 lanes-per-row)
     int64_t sweep_cap_opt = -1;        // test shape sweep_state_bytes: lzx_sweep_cut treats a state larger than this as out of device memory
     int64_t sim_long_opt = -1;         // test shape sim_long_pair: entries of the shorter row beyond which lzx_similarity gives a pair to a workgroup of its own (<= 0: 64 lanes-per-pair)

@@ -32,7 +32,10 @@
 // is updated by a group of lanes, which stages the first 128 labels in LDS and reads the rest of a longer row where it lies; default 128),
 // "lpa_table_row" (a longer row of at most this many entries is counted in the LDS table by a workgroup, the rest in a table in global
 // memory; default and at most 2048, half the LDS table's slots), "lpa_state_bytes" (lzx_label_propagation takes a state larger than this many
-// bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables), "sweep_long_row"
+// bytes as out of device memory, at the vertices' arena before the device is touched and at the global tables), "louvain_state_bytes"
+// (lzx_louvain, which honours "color_long_row", "lpa_group_row" and "lpa_table_row" on every level graph, takes a state larger than this
+// many bytes as out of device memory at each of its allocations: the vertices' arena, a level's global tables, the aggregation's keys
+// and weights, a level graph -- the bytes held plus the bytes asked for), "sweep_long_row"
 // (lzx_sweep_cut: a row with more than this many entries is swept by the long-row launch, a workgroup per row; default 64 times the
 // lanes per row), "sweep_state_bytes" (lzx_sweep_cut takes a state larger than this many bytes as out of device memory, before the
 // device is touched), "sim_long_pair" (lzx_similarity: a pair whose shorter row has more than this many entries is intersected by a
@@ -40,7 +43,7 @@
 // also has more than this many entries is dealt to one workgroup per slice of that many entries, 64 at the most, whose partials a
 // closing launch adds in slice order; default 16384), "sim_state_bytes" (lzx_similarity takes a state larger than this many bytes as
 // out of device memory, at either of its two allocations), "graph_lanes" (lzx_components, lzx_triangles, lzx_core_numbers, lzx_truss,
-// lzx_color, lzx_label_propagation, lzx_modularity, lzx_sweep_cut and lzx_similarity: 4 | 8 | 16 | 32 | 64 lanes per row in every kernel
+// lzx_color, lzx_label_propagation, lzx_modularity, lzx_louvain, lzx_sweep_cut and lzx_similarity: 4 | 8 | 16 | 32 | 64 lanes per row in every kernel
 // template they launch, in place of the rule on the mean row length and capped at the widest instantiation of each launch -- 64 for the
 // orientation pass and lzx_truss's per-row passes, 32 elsewhere; 0, or -1 like every unset shape: the rule; any other value is refused
 // with LZX_ERR_ARG.  The defaults of "core_long_row", "truss_long_row", "color_long_row", "sweep_long_row", "sim_long_pair" and
