@@ -34,20 +34,21 @@
 // Classes: a counting sort of the vertices by (colour, path) -- k_class_sort<false> the histogram, the host the scan (three words
 // per colour), k_class_sort<true> the fill -- so that every (class, path) is one run of `cls` and one launch with exactly its rows.
 //
-// Propagation, in place (the vertices of a class share no edge, so a launch reads only labels it does not write):
-//   short   k_lpa_group<G>     rows of at most lpa_group_row entries (128).  G lanes per row; the neighbours' labels are staged in
-//                              the group's LDS slice (the first 128; a longer row, which only the test shape sends here, reads the
-//                              rest where it lies); every lane counts, for its own entries, the equal labels in the row, and the
-//                              key  count << 33 | (label == old) << 32 | label  is max-reduced over the group
-//   medium  k_lpa_table        rows of at most lpa_table_row entries (2048): a workgroup per row and an open-addressing table in
-//                              LDS, keys u32 and counts u32, pow2ceil(2 len) of its 4096 slots (32 KiB: five workgroups per
-//                              compute unit, twenty of its thirty-two wavefronts): atomicCAS on the key slot, atomicAdd on the
-//                              count, linear probing bounded by the slot count, never more than half full; then the maximum of
-//                              the same key over the slots
-//   long    k_lpa_far_insert   the same insertion into a table of pow2ceil(2 len) slots in global memory, at an offset from a scan
-//           k_lpa_far_pick     over the long rows made once per call: up to 64 workgroups share the entries of a row (one alone
-//                              is a chain of dependent round trips per 256 entries), and a second launch, the workgroup that owns
-//                              the table, takes the maximum and clears the slots it read.  The tables are zeroed once per call.
+// Propagation, in place (the vertices of a class share no edge, so a launch reads only labels it does not write).  The pass over
+// the classes, the wave insert and the far insert are lzx_class_sweep.h's, which lzx_louvain shares; the decide kernels are these:
+//   short   k_lpa_group<G>        rows of at most lpa_group_row entries (128).  G lanes per row; the neighbours' labels are staged in
+//                                 the group's LDS slice (the first 128; a longer row, which only the test shape sends here, reads
+//                                 the rest where it lies); every lane counts, for its own entries, the equal labels in the row, and
+//                                 the key  count << 33 | (label == old) << 32 | label  is max-reduced over the group
+//   medium  k_lpa_table           rows of at most lpa_table_row entries (2048): a workgroup per row and an open-addressing table in
+//                                 LDS, keys u32 and counts u32, pow2ceil(2 len) of its 4096 slots (32 KiB: five workgroups per
+//                                 compute unit, twenty of its thirty-two wavefronts): atomicCAS on the key slot, atomicAdd on the
+//                                 count, linear probing bounded by the slot count, never more than half full; then the maximum of
+//                                 the same key over the slots
+//   long    k_class_far_insert<W> the same insertion into a table of pow2ceil(2 len) slots in global memory, at an offset from a scan
+//           k_lpa_far_pick        over the long rows made once per call: up to 64 workgroups share the entries of a row (one alone
+//                                 is a chain of dependent round trips per 256 entries), and a second launch, the workgroup that owns
+//                                 the table, takes the maximum and clears the slots it read.  The tables are zeroed once per call.
 // The new label is an arg-max under a total order: it depends neither on the path a row takes nor on any thread order.  Changed
 // labels are counted per wavefront into one word, which the host reads once per sweep.
 //
@@ -62,7 +63,7 @@
 
 #include "lzx_internal.h"
 #include "lzx_graph_call.h"
-#include "lzx_communities_shared.h"
+#include "lzx_class_sweep.h"
 #include "lzx_spmv_body.h"
 #include "lzx_reduce.h"
 
@@ -295,13 +296,6 @@ k_class_sort(const u64 *row_ptr, const u32 *colour, u32 *bins, u32 *cls, u32 n, 
 }
 
 // ---- propagation --------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(LZX_COM_BLOCK)
-k_fill_u32(u32 *x, u32 n, u32 value, u32 iota)
-{
-    const u64 i = (u64)blockIdx.x * LZX_COM_BLOCK + threadIdx.x;
-    if (i < n) x[i] = iota ? (u32)i : value;
-}
-
 // the rows of more than table_row entries: lpos[v] = the row's place in the list, llen[place] = its length
 __global__ void __launch_bounds__(LZX_COM_BLOCK)
 k_lpa_long_rows(const u64 *row_ptr, u32 *lpos, u32 *llen, u32 *counters, u32 n, u32 table_row)
@@ -365,25 +359,6 @@ k_lpa_group(const u64 *row_ptr, const u32 *col_idx, u32 *label, const u32 *cls, 
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[CW_CHANGED], (u32)__builtin_popcountll(m));
 }
 
-// The labels of a wavefront's lanes (have: this lane holds one).  The lanes that agree with the first lane's label, and then with
-// the first of the rest, are inserted as one -- late in a run most neighbours of a hub carry one label, and a hundred thousand
-// atomics on one address are to be avoided; what is left inserts for itself.  Every lane of the wavefront must call it together.
-__device__ __forceinline__ void lpa_insert_wave(bool have, u32 mine, u32 *keys, u32 *counts, u32 slots)
-{
-    const u32 lane = threadIdx.x & 63;
-    ull todo = __ballot(have);
-    for (int it = 0; it < 2 && todo; ++it) {   // (the same trips for every lane)
-        const int leader = __builtin_ctzll(todo);
-        const u32 k0 = (u32)__shfl((int)mine, leader, 64);
-        const bool agree = have && mine == k0;
-        const ull same = __ballot(agree);
-        if (lane == (u32)leader) lpa_insert(keys, counts, slots, k0, (u32)__builtin_popcountll(same));
-        if (agree) have = false;
-        todo &= ~same;
-    }
-    if (have) lpa_insert(keys, counts, slots, mine, 1u);
-}
-
 // the workgroup's largest key (in thread 0) becomes v's label
 __device__ __forceinline__ void lpa_take(ull best, u32 v, u32 old, u32 *label, u32 *counters, ull *s_k)
 {
@@ -415,7 +390,7 @@ k_lpa_table(const u64 *row_ptr, const u32 *col_idx, u32 *label, const u32 *cls, 
     for (u64 e0 = beg; e0 < end; e0 += LZX_COM_BLOCK) {   // (the same trips for every lane of the workgroup)
         const u64 e = e0 + threadIdx.x;
         const u32 u = e < end ? col_idx[e] : v;
-        lpa_insert_wave(u != v, u != v ? label[u] : 0u, keys, counts, slots);
+        lzx_insert_wave<false>(u != v, u != v ? label[u] : 0u, 1u, keys, counts, slots);
     }
     __syncthreads();
     ull best = 0;
@@ -427,23 +402,8 @@ k_lpa_table(const u64 *row_ptr, const u32 *col_idx, u32 *label, const u32 *cls, 
     lpa_take(best, v, old, label, counters, s_k);
 }
 
-// The rows cls[sbeg .. sbeg + gridDim.x) of more entries: the table of row v lies at tables + 2 loff[lpos[v]] in global memory, all
-// zeros between the launches.  First launch: workgroup (row, slice) inserts every gridDim.y-th run of 256 entries of the row ...
-__global__ void __launch_bounds__(LZX_COM_BLOCK)
-k_lpa_far_insert(const u64 *row_ptr, const u32 *col_idx, const u32 *label, const u32 *cls, u32 sbeg, const u32 *lpos, const u64 *loff, u32 *tables)
-{
-    const u32 v = cls[sbeg + blockIdx.x];
-    const u64 beg = row_ptr[v], end = row_ptr[v + 1];
-    const u32 slots = lpa_slots(end - beg, 1u << 31);
-    u32 *keys = tables + 2 * loff[lpos[v]], *counts = keys + slots;
-    for (u64 e0 = beg + (u64)blockIdx.y * LZX_COM_BLOCK; e0 < end; e0 += (u64)gridDim.y * LZX_COM_BLOCK) {   // (the same trips for every lane)
-        const u64 e = e0 + threadIdx.x;
-        const u32 u = e < end ? col_idx[e] : v;
-        lpa_insert_wave(u != v, u != v ? label[u] : 0u, keys, counts, slots);
-    }
-}
-
-// ... second launch: the workgroup that owns the table takes the maximum over its slots and clears them
+// The rows cls[sbeg .. sbeg + gridDim.x) of more entries, after k_class_far_insert (lzx_class_sweep.h): the workgroup that owns the
+// row's table takes the maximum over its slots and clears them
 __global__ void __launch_bounds__(LZX_COM_BLOCK)
 k_lpa_far_pick(const u64 *row_ptr, u32 *label, const u32 *cls, u32 sbeg, const u32 *lpos, const u64 *loff, u32 *tables, u32 *counters)
 {
@@ -705,8 +665,8 @@ int lzx_comm_canonical(lzx_ctx *c, const u32 *d_label, u32 n, u32 *d_first, u32 
 {
     hipStream_t st = c->stream;
     const u32 gb = lzx_vertex_grid(n);
-    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_first, n, LZX_COM_NONE, 0u);
-    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_sizes, n, 0u, 0u);
+    hipLaunchKernelGGL(k_fill_u32<false>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_first, n, LZX_COM_NONE);
+    hipLaunchKernelGGL(k_fill_u32<false>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_sizes, n, 0u);
     hipLaunchKernelGGL(k_comm_first, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, d_first, n);
     hipLaunchKernelGGL(k_comm_gather, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, (const u32 *)d_first, d_out, d_sizes, n);
     hipLaunchKernelGGL(k_comm_stats, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_out, (const u32 *)d_sizes, counters, n);
@@ -767,8 +727,7 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     const u32 n = (u32)c->n;
     const LzxGraphView g = lzx_view_of(c);
     hipStream_t st = c->stream;
-    const u32 group_row = c->lpa_group_opt > 0 ? (u32)std::min<int64_t>(c->lpa_group_opt, LZX_LPA_MAX_ROW) : LZX_LPA_STAGE;
-    const u32 table_row = c->lpa_table_opt > 0 && c->lpa_table_opt < LZX_LPA_SLOTS / 2 ? (u32)c->lpa_table_opt : LZX_LPA_SLOTS / 2;
+    LzxClassSweep cs(c);
 
     // one arena: D, I (u64 [n]), d, wait, colour, queue, label (u32 [n] each, rounded to 8 bytes), three bins per colour, the counter
     // words; the tables of the rows above table_row follow once they are known
@@ -790,28 +749,18 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     s.counters = s.bins + nb;
     LZX_HIP(hipEventCreate(&run.ev0));
     LZX_HIP(hipEventCreate(&run.ev1));
-    const u32 gb = lzx_vertex_grid(n);
-
-    LzxColorResult col;
-    LZX_TRY(lzx_color_core(c, g, run, fn_name, seed, flags, s, true, group_row, table_row, &col));
-    const u32 *d_cls = s.queue;
-
-    // the rows above table_row: their places (in `wait`, which the colouring is done with), the offsets of their tables
-    u32 *d_lpos = s.wait, *d_llen = reinterpret_cast<u32 *>(d_I);
-    u64 *d_loff = reinterpret_cast<u64 *>(d_D);
-    u32 *d_tables = nullptr;
-    const u32 table_above = std::max(group_row, table_row);   // (a test shape may send longer rows to the groups of lanes)
-    if (c->max_degree > table_above) {
-        u64 table_bytes = 0;
-        LZX_TRY(lzx_lpa_far_tables(c, g, fn_name, table_above, c->lpa_cap_opt, bytes, d_lpos, d_llen, d_loff, s.counters, &run.more[0], &table_bytes));
-        d_tables = static_cast<u32 *>(run.more[0]);
-    }
+    u64 table_bytes = 0;
+    LZX_TRY(lzx_class_sweep_open(c, g, run, fn_name, seed, flags, s, d_D, d_I, c->lpa_cap_opt, bytes, &run.more[0], &table_bytes, &cs));
 
     // ---- the sweeps ----
-    hipLaunchKernelGGL(k_fill_u32, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, d_label, n, 0u, 1u);
+    hipLaunchKernelGGL(k_fill_u32<true>, dim3(lzx_vertex_grid(n)), dim3(LZX_COM_BLOCK), 0, st, d_label, n, 0u);
     LZX_HIP(hipGetLastError());
-    const u32 G = lzx_lanes_of(c, g);
-    const u32 slices = (u32)std::min<u64>(std::max<u64>(c->max_degree / (8 * LZX_COM_BLOCK), 1), 64);   // workgroups that share a long row's entries
+    // the three decide launches of a class: its rows cls[first .. first + rows) of one path
+    auto group = [&](u32 first, u32 rows) {
+        lzx_with_lanes<32>(cs.G, [&](auto lanes) { hipLaunchKernelGGL(k_lpa_group<lanes>, dim3(lzx_row_grid(rows, LZX_COM_BLOCK / lanes)), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, d_label, cs.cls, first, rows, s.counters); });
+    };
+    auto table = [&](u32 first, u32 rows) { hipLaunchKernelGGL(k_lpa_table, dim3(rows), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, d_label, cs.cls, first, s.counters); };
+    auto far_pick = [&](u32 first, u32 rows) { hipLaunchKernelGGL(k_lpa_far_pick, dim3(rows), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, d_label, cs.cls, first, cs.lpos, cs.loff, cs.tables, s.counters); };
     u32 sweeps = 0;
     u64 updates = 0;
     bool converged = false;
@@ -819,24 +768,7 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     while (sweeps < max_sweeps && !converged) {
         ++sweeps;
         LZX_HIP(hipMemsetAsync(s.counters + CW_CHANGED, 0, sizeof(u32), st));
-        for (u32 k = 0; k < col.colours; ++k) {
-            const u32 *r = col.run.data() + 3 * (size_t)k;
-            if (r[1] > r[0])
-                lzx_with_lanes<32>(G, [&](auto g) {
-                    hipLaunchKernelGGL(k_lpa_group<g>, dim3(lzx_row_grid(r[1] - r[0], LZX_COM_BLOCK / g)), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr,
-                                       c->d_col_idx, d_label, d_cls, r[0], r[1] - r[0], s.counters);
-                });
-            if (r[2] > r[1])
-                hipLaunchKernelGGL(k_lpa_table, dim3(r[2] - r[1]), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_label, d_cls, r[1], s.counters);
-            if (r[3] > r[2]) {
-                if (!d_tables) LZX_FAIL(LZX_ERR_LIMIT, "%s: a row above %u entries without a table", fn_name, table_above);
-                hipLaunchKernelGGL(k_lpa_far_insert, dim3(r[3] - r[2], slices), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx,
-                                   (const u32 *)d_label, d_cls, r[2], (const u32 *)d_lpos, (const u64 *)d_loff, d_tables);
-                hipLaunchKernelGGL(k_lpa_far_pick, dim3(r[3] - r[2]), dim3(LZX_COM_BLOCK), 0, st, c->d_row_ptr, d_label, d_cls, r[2],
-                                   (const u32 *)d_lpos, (const u64 *)d_loff, d_tables, s.counters);
-            }
-            LZX_HIP(hipGetLastError());
-        }
+        LZX_TRY(lzx_class_pass(c, g, cs, fn_name, d_label, group, table, far_pick, [](u32) {}));
         u32 changed = 0;
         LZX_HIP(hipMemcpyAsync(&changed, s.counters + CW_CHANGED, sizeof(u32), hipMemcpyDeviceToHost, st));
         LZX_HIP(hipStreamSynchronize(st));
@@ -845,32 +777,17 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     }
     LZX_HIP(hipEventRecord(run.ev1, st));
 
-    // ---- canonical labels (into `wait`), sizes (into `colour`), the statistics, the modularity (its scratch: `queue`) ----
-    u32 *d_first = s.queue, *d_out = s.wait, *d_sizes = s.colour;
-    LZX_TRY(lzx_comm_canonical(c, d_label, n, d_first, d_out, d_sizes, s.counters));
-    u32 words[CW_WORDS];
-    LZX_HIP(hipMemcpyAsync(words, s.counters, sizeof(words), hipMemcpyDeviceToHost, st));
-    std::vector<u64> hD, hI;
-    LzxModResult mod;
-    LZX_TRY(lzx_modularity_core(c, g, d_out, s.d, s.queue, d_D, d_I, hD, hI, &mod));
-    if (labels) LZX_HIP(hipMemcpyAsync(labels, d_out, sizeof(u32) * n, hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipStreamSynchronize(st));
+    LzxCommResult res;
+    LZX_TRY(lzx_comm_finish(c, g, d_label, s, d_D, d_I, labels, &res));
     float sweep_ms = 0.f;
     LZX_HIP(hipEventElapsedTime(&sweep_ms, run.ev0, run.ev1));
     if (info) {
-        const u64 key = (u64)words[CW_KEY] | ((u64)words[CW_KEY + 1] << 32);
-        info->n_communities = words[CW_COMMUNITIES];
-        info->largest_size = key >> 32;
-        info->largest_label = LZX_COM_NONE - (u32)(key & 0xffffffffull);
+        res.fill(info);
         info->updates = updates;
-        info->inner_entries = mod.inner;
-        info->entries = mod.entries;
-        info->sum_degree_sq = mod.sum_sq;
         info->sweeps = sweeps;
-        info->colors = col.colours;
-        info->color_rounds = col.rounds;
-        info->modularity = mod.q;
-        info->color_ms = col.ms;
+        info->colors = cs.col.colours;
+        info->color_rounds = cs.col.rounds;
+        info->color_ms = cs.col.ms;
         info->sweep_ms = sweep_ms;
         info->loop_ms = lzx_ms_since(t0);
     }

@@ -85,6 +85,16 @@ __device__ __forceinline__ void lpa_insert(u32 *keys, u32 *counts, u32 slots, u3
 }
 
 
+// x[i] = i (IOTA) or value, i < n.  (static, like every kernel of a header two files include: each file launches the copy in its
+// own code object, so the file a call's first launch loads does not depend on the link order)
+template <bool IOTA>
+static __global__ void __launch_bounds__(LZX_COM_BLOCK)
+k_fill_u32(u32 *x, u32 n, u32 value)
+{
+    const u64 i = (u64)blockIdx.x * LZX_COM_BLOCK + threadIdx.x;
+    if (i < n) x[i] = IOTA ? (u32)i : value;
+}
+
 // pow2ceil(2 len), at least 2 and at most cap
 __device__ __forceinline__ u32 lpa_slots(u64 len, u32 cap)
 {

@@ -4,7 +4,9 @@
 // a call, what it holds on the device, the capped allocation of its state (also the CG entry points' and the eigensolver's),
 // the choice of lanes per row, a test shape in a rule's place.  Device side: the idioms of their kernels over ascending rows and
 // wavefront-aggregated queues.  What only some of them share has a header of its own on top of this one: the oriented copy and
-// the split of the walks over it (lzx_tri_orient.h: lzx_triangles, lzx_truss), the push peel (lzx_peel.h: lzx_core_numbers, lzx_truss).
+// the split of the walks over it (lzx_tri_orient.h: lzx_triangles, lzx_truss), the push peel (lzx_peel.h: lzx_core_numbers, lzx_truss), the
+// graph view, the colouring and the modularity (lzx_communities_shared.h: lzx_communities.hip, lzx_louvain.hip) and, on top of that, the
+// sweep over the colour classes (lzx_class_sweep.h: lzx_label_propagation, lzx_louvain).
 #pragma once
 
 #include <algorithm>

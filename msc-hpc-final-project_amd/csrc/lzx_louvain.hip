@@ -1,7 +1,7 @@
 // lzx_louvain.hip -- Louvain communities of the handle's graph (networkx.community.louvain_communities / louvain_partitions): local
 // moves over the colour classes of every level graph, then aggregation, in integers only: include/lzx.h, lzx_louvain; DESIGN.md
 // section 25.  The colouring, the class sort, the canonical labels and the modularity are lzx_communities.hip's, run on a view of the
-// level graph (lzx_communities_shared.h).
+// level graph (lzx_communities_shared.h); the sweep over the classes is lzx_class_sweep.h's.
 //
 // Definitions.  A level graph has n_l nodes, rows ascending by column and a weight w_ij >= 1 per stored entry (u32); level 0 is the
 // caller-order pattern, every off-diagonal entry 1 and a diagonal entry 0.  k_i = the sum of row i, the diagonal included; M = the sum
@@ -16,13 +16,14 @@
 //
 // Kernels, wave64, 256 threads, templated on W (a weight array is read) so that level 0 reads none:
 //   init      k_louvain_init<W>        one thread per row: label = i, k = tot = the row sum, I += the diagonal
-//   decide    k_louvain_group<G, W>    rows of at most lpa_group_row entries (128): G lanes per row stage the neighbours' labels (and
+//   decide    (the pass over the classes, the wave insert and the far insert: lzx_class_sweep.h, shared with the propagation)
+//             k_louvain_group<G, W>    rows of at most lpa_group_row entries (128): G lanes per row stage the neighbours' labels (and
 //                                      weights) in the group's LDS slice; every lane sums, for its own entries, the weight of the equal
 //                                      labels, gathers tot, forms G in i64, and (G, smallest c) is max-reduced over the group
 //             k_louvain_table<W>       rows of at most lpa_table_row entries (2048): a workgroup per row and the open-addressing table
 //                                      of the propagation in LDS, the count slot a weight sum; then every slot forms its G and the
 //                                      pair is max-reduced over the workgroup
-//             k_louvain_far_insert<W>  longer rows: the same insertion into the row's table in global memory by up to 64 workgroups,
+//             k_class_far_insert<W>    longer rows: the same insertion into the row's table in global memory by up to 64 workgroups,
 //             k_louvain_far_pick       and the pick by the workgroup that owns the table, which clears the slots it read
 //             A mover writes its label in place -- nobody in its class reads it -- and is appended (lzx_wave_append) to the move list
 //             as (i, a, c*, k_ic* - k_ia); tot is not written while a class decides.
@@ -46,7 +47,7 @@
 
 #include "lzx_internal.h"
 #include "lzx_graph_call.h"
-#include "lzx_communities_shared.h"
+#include "lzx_class_sweep.h"
 #include "lzx_reduce.h"
 
 typedef long long i64;
@@ -184,26 +185,6 @@ k_louvain_group(const u64 *row_ptr, const u32 *col_idx, const u32 *weights, Louv
     louvain_decide(sub == 0 && idx < slen, s, v, a, kia, best);
 }
 
-// The labels of a wavefront's lanes (have: this lane holds one of weight w) into the table: the lanes that agree with the first lane's
-// label, and then with the first of the rest, are inserted as one sum; what is left inserts for itself.  Every lane of the wavefront
-// must call it together.
-__device__ __forceinline__ void louvain_insert_wave(bool have, u32 mine, u32 w, u32 *keys, u32 *sums, u32 slots)
-{
-    const u32 lane = threadIdx.x & 63;
-    ull todo = __ballot(have);
-    for (int it = 0; it < 2 && todo; ++it) {   // (the same trips for every lane)
-        const int leader = __builtin_ctzll(todo);
-        const u32 k0 = (u32)__shfl((int)mine, leader, 64);
-        const bool agree = have && mine == k0;
-        const ull same = __ballot(agree);
-        const u32 sum = lzx_wave_sum_u32(agree ? w : 0u);
-        if (lane == (u32)leader) lpa_insert(keys, sums, slots, k0, sum);
-        if (agree) have = false;
-        todo &= ~same;
-    }
-    if (have) lpa_insert(keys, sums, slots, mine, w);
-}
-
 // what the slots [threadIdx.x, +256, ...) of a table hold: the best candidate, and k_ia into *s_kia (one slot holds a at the most)
 __device__ __forceinline__ LouvainPick louvain_scan(u32 *keys, u32 *sums, u32 slots, bool clear, const LouvainSweep &s, u32 a, i64 ki, u32 *s_kia)
 {
@@ -255,32 +236,15 @@ k_louvain_table(const u64 *row_ptr, const u32 *col_idx, const u32 *weights, Louv
     for (u64 e0 = beg; e0 < end; e0 += LZX_COM_BLOCK) {   // (the same trips for every lane of the workgroup)
         const u64 e = e0 + threadIdx.x;
         const u32 u = e < end ? col_idx[e] : v;
-        louvain_insert_wave(u != v, u != v ? s.label[u] : 0u, (W && u != v) ? weights[e] : 1u, keys, sums, slots);
+        lzx_insert_wave<W>(u != v, u != v ? s.label[u] : 0u, (W && u != v) ? weights[e] : 1u, keys, sums, slots);
     }
     __syncthreads();
     const LouvainPick best = louvain_scan(keys, sums, slots, false, s, a, s.k[v], &s_kia);
     louvain_take(best, s, v, a, &s_kia, s_pick);
 }
 
-// The rows cls[sbeg .. sbeg + gridDim.x) of more entries: the table of row v lies at tables + 2 loff[lpos[v]] in global memory, all
-// zeros between the launches.  First launch: workgroup (row, slice) inserts every gridDim.y-th run of 256 entries of the row ...
-template <bool W>
-__global__ void __launch_bounds__(LZX_COM_BLOCK)
-k_louvain_far_insert(const u64 *row_ptr, const u32 *col_idx, const u32 *weights, const u32 *label, const u32 *cls, u32 sbeg, const u32 *lpos,
-                     const u64 *loff, u32 *tables)
-{
-    const u32 v = cls[sbeg + blockIdx.x];
-    const u64 beg = row_ptr[v], end = row_ptr[v + 1];
-    const u32 slots = lpa_slots(end - beg, 1u << 31);
-    u32 *keys = tables + 2 * loff[lpos[v]], *sums = keys + slots;
-    for (u64 e0 = beg + (u64)blockIdx.y * LZX_COM_BLOCK; e0 < end; e0 += (u64)gridDim.y * LZX_COM_BLOCK) {   // (the same trips for every lane)
-        const u64 e = e0 + threadIdx.x;
-        const u32 u = e < end ? col_idx[e] : v;
-        louvain_insert_wave(u != v, u != v ? label[u] : 0u, (W && u != v) ? weights[e] : 1u, keys, sums, slots);
-    }
-}
-
-// ... second launch: the workgroup that owns the table picks over its slots and clears them
+// The rows cls[sbeg .. sbeg + gridDim.x) of more entries, after k_class_far_insert<W> (lzx_class_sweep.h): the workgroup that owns
+// the row's table picks over its slots and clears them
 __global__ void __launch_bounds__(LZX_COM_BLOCK)
 k_louvain_far_pick(const u64 *row_ptr, LouvainSweep s, const u32 *cls, u32 sbeg, const u32 *lpos, const u64 *loff, u32 *tables)
 {
@@ -405,13 +369,6 @@ k_agg_compose(u32 *comp, const u32 *label, const u32 *newid, u32 n0)
     if (v < n0) comp[v] = newid[label[comp[v]]];
 }
 
-__global__ void __launch_bounds__(LZX_COM_BLOCK)
-k_louvain_iota(u32 *x, u32 n)
-{
-    const u64 i = (u64)blockIdx.x * LZX_COM_BLOCK + threadIdx.x;
-    if (i < n) x[i] = (u32)i;
-}
-
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
 // the level graphs and the far tables of a level: what the call allocates beyond the LzxGraphRun's three blocks.  Declared after
@@ -441,11 +398,228 @@ struct LouvainBlocks {
     LouvainBlocks &operator=(const LouvainBlocks &) = delete;
 };
 
-inline u32 entry_grid(u64 entries) { return (u32)((entries + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK); }
+// The arena: D, I (u64 [n0]); d, wait, colour, queue, label, tot, k, the saved labels and tot, comp (u32 [n0] each, rounded to 8
+// bytes), the move list (4 per node); three bins per colour; the counter words and the accumulators.
+struct LouvainArena {
+    ull *D, *I;
+    LzxColorState s;
+    u32 *label, *tot, *k, *label0, *tot0, *comp, *moves;
+    ull *acc;
+};
+// the arena's bytes for n0 vertices, and its pointers carved from base in the order they are counted
+u64 louvain_arena(u32 n0, void *base, LouvainArena *a)
+{
+    const u64 n_al = lzx_even(n0);
+    u64 at = 0;
+    auto carve = [&](auto *&p, u64 count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + at);
+        at += count * sizeof(*p);
+    };
+    for (ull **p : {&a->D, &a->I}) carve(*p, n0);
+    for (u32 **p : {&a->s.d, &a->s.wait, &a->s.colour, &a->s.queue, &a->label, &a->tot, &a->k, &a->label0, &a->tot0, &a->comp}) carve(*p, n_al);
+    carve(a->moves, 4 * n_al);
+    carve(a->s.bins, lzx_class_bins(n0));
+    carve(a->s.counters, CW_WORDS);
+    carve(a->acc, AC_WORDS);
+    return at;
+}
+
+// what the sweeps of a level leave
+struct LouvainLevel {
+    lzx_louvain_level rec{};   // sweeps, reverted, capped, the moves of the accepted sweeps, I and the sum of tot^2 after them
+    u32 accepted = 0;
+    float ms = 0.f;
+};
+
+// The local moves of one level: label = i, tot = k, then sweeps over the classes of cs until one moves nothing, one does not raise
+// Qnum and is taken back, or max_sweeps are accepted.  *M: the sum of the k_i, which the first level sets.
+int louvain_level_sweeps(lzx_ctx *c, const LzxGraphView &g, LzxGraphRun &run, const LouvainArena &a, const LzxClassSweep &cs, const char *fn_name, u32 max_sweeps, bool first_level, i64 *M_, LouvainLevel *lv)
+{
+    hipStream_t st = c->stream;
+    const u32 n = g.n, gb = lzx_vertex_grid(n);
+    LZX_HIP(hipEventRecord(run.ev2, st));
+    LZX_HIP(hipMemsetAsync(a.acc, 0, AC_WORDS * sizeof(u64), st));
+    lzx_with_weights(g.weights != nullptr, [&](auto w) {
+        hipLaunchKernelGGL(k_louvain_init<w>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)a.s.d, a.k, a.label, a.tot, a.acc, n);
+    });
+    hipLaunchKernelGGL(k_louvain_sum_sq, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)a.tot, a.acc, n);
+    LZX_HIP(hipGetLastError());
+    u64 words[AC_WORDS] = {};   // I, sum tot^2, the moves, the window words, ..., sum tot
+    LZX_HIP(hipMemcpyAsync(words, a.acc, sizeof(words), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    lv->rec.inner_entries = words[AC_INNER];
+    lv->rec.sum_degree_sq = words[AC_SQ];
+    if (first_level) *M_ = (i64)words[AC_SUM];   // the sum of the k_i = the off-diagonal entries (tot is k here)
+    const i64 M = *M_;
+    i64 qnum = M * (i64)lv->rec.inner_entries - (i64)lv->rec.sum_degree_sq;
+    const LouvainSweep sw{a.k, a.label, a.tot, a.moves, reinterpret_cast<u32 *>(a.acc + AC_TAIL), M, n};
+    while (true) {
+        if (lv->accepted == max_sweeps) {
+            lv->rec.capped = 1;
+            break;
+        }
+        ++lv->rec.sweeps;
+        LZX_HIP(hipMemcpyAsync(a.label0, a.label, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+        LZX_HIP(hipMemcpyAsync(a.tot0, a.tot, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+        LZX_HIP(hipMemsetAsync(a.acc + AC_SQ, 0, 3 * sizeof(u64), st));   // the sum, the list's end, the window words
+        u32 parity = 0;
+        // tot moves when the whole class has decided
+        auto apply = [&](u32 rows) {
+            if (!rows) return;
+            hipLaunchKernelGGL(k_louvain_apply, dim3(lzx_vertex_grid(rows)), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)a.moves, (const u32 *)a.k, a.tot, a.acc, parity, n);
+            parity ^= 1u;
+        };
+        int rc = LZX_OK;
+        lzx_with_weights(g.weights != nullptr, [&](auto w) {   // the three decide launches of a class: its rows cls[first .. first + rows) of one path
+            auto group = [&](u32 first, u32 rows) {
+                lzx_with_lanes<32>(cs.G, [&](auto lanes) { hipLaunchKernelGGL((k_louvain_group<lanes, w>), dim3(lzx_row_grid(rows, LZX_COM_BLOCK / lanes)), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, cs.cls, first, rows); });
+            };
+            auto table = [&](u32 first, u32 rows) { hipLaunchKernelGGL(k_louvain_table<w>, dim3(rows), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, cs.cls, first); };
+            auto far_pick = [&](u32 first, u32 rows) { hipLaunchKernelGGL(k_louvain_far_pick, dim3(rows), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, sw, cs.cls, first, cs.lpos, cs.loff, cs.tables); };
+            rc = lzx_class_pass(c, g, cs, fn_name, a.label, group, table, far_pick, apply);
+        });
+        LZX_TRY(rc);
+        hipLaunchKernelGGL(k_louvain_sum_sq, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)a.tot, a.acc, n);
+        LZX_HIP(hipGetLastError());
+        LZX_HIP(hipMemcpyAsync(words, a.acc, sizeof(words), hipMemcpyDeviceToHost, st));
+        LZX_HIP(hipStreamSynchronize(st));
+        const u32 moved = std::min((u32)(words[AC_TAIL] & 0xffffffffull), n);
+        if (moved == 0) break;
+        const i64 after = M * (i64)words[AC_INNER] - (i64)words[AC_SQ];
+        if (after <= qnum) {   // the sweep is taken back
+            LZX_HIP(hipMemcpyAsync(a.label, a.label0, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+            LZX_HIP(hipMemcpyAsync(a.tot, a.tot0, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+            LZX_HIP(hipMemcpyAsync(a.acc + AC_INNER, &lv->rec.inner_entries, sizeof(u64), hipMemcpyHostToDevice, st));
+            LZX_HIP(hipStreamSynchronize(st));
+            lv->rec.reverted = 1;
+            break;
+        }
+        lv->rec.inner_entries = words[AC_INNER];
+        lv->rec.sum_degree_sq = words[AC_SQ];
+        qnum = after;
+        lv->rec.moves += moved;
+        ++lv->accepted;
+    }
+    LZX_HIP(hipEventRecord(run.ev3, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    LZX_HIP(hipEventElapsedTime(&lv->ms, run.ev2, run.ev3));
+    return LZX_OK;
+}
+
+// The aggregation's scratch, allocated by the first level that aggregates and sized for level 0 (every later level has fewer
+// nodes and no more entries): two key and two value arrays of e0 entries, hipcub's, the count of the runs.
+struct LouvainScratch {
+    u64 *keys = nullptr, *keys2 = nullptr;
+    u32 *vals = nullptr, *vals2 = nullptr, *runs = nullptr;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    u64 bytes = 0;
+};
+// what hipcub asks for: the scan over n + 1 flags, the sort and the reduction by key of `entries` pairs
+int louvain_cub_bytes(u32 n, u64 entries, hipStream_t st, size_t *bytes)
+{
+    size_t scan_b = 0, sort_b = 0, reduce_b = 0;
+    u64 *keys = nullptr;   // (the sizes do not depend on the pointers)
+    u32 *vals = nullptr;
+    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, vals, vals, (u64)n + 1, st));
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, keys, keys, vals, vals, entries, 0, 64, st));
+    LZX_HIP(hipcub::DeviceReduce::ReduceByKey(nullptr, reduce_b, keys, keys, vals, vals, vals, hipcub::Sum(), entries, st));
+    *bytes = std::max(scan_b, std::max(sort_b, reduce_b));
+    return LZX_OK;
+}
+
+// From the labels of level graph g to the next level's graph: *next, in blocks.graph[1], and comp composed with the level's labels
+// (level_out, or NULL: the partition of the n0 vertices after this level, canonical).  A level that merged nothing says so in
+// *merged, builds no graph and leaves *next and *ms alone.  *held: the bytes the call holds, to which the scratch is added where it is allocated here.
+int louvain_aggregate(lzx_ctx *c, const LzxGraphView &g, LzxGraphRun &run, LouvainBlocks &blocks, const LouvainArena &a, LouvainScratch &sc,
+                      const char *fn_name, u32 n0, u64 e0, u32 G, int64_t cap, u64 *held, u32 *level_out, bool *merged, LzxGraphView *next, float *ms)
+{
+    hipStream_t st = c->stream;
+    const u32 n = g.n, gb = lzx_vertex_grid(n);
+    char what[160];
+    // the labels that occur (flags and new ids in the move list's words)
+    LZX_HIP(hipEventRecord(run.ev2, st));
+    u32 *d_newid = a.moves;
+    LZX_HIP(hipMemsetAsync(d_newid, 0, sizeof(u32) * ((u64)n + 1), st));
+    hipLaunchKernelGGL(k_agg_flag, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)a.label, d_newid, n);
+    LZX_HIP(hipGetLastError());
+    if (!run.more[0]) {
+        LZX_TRY(louvain_cub_bytes(n0, e0, st, &sc.tmp_bytes));
+        sc.tmp_bytes = (sc.tmp_bytes + 15) & ~(size_t)15;
+        sc.bytes = 2 * e0 * sizeof(u64) + 2 * lzx_even(e0) * sizeof(u32) + sc.tmp_bytes + 16;
+        std::snprintf(what, sizeof what, "the aggregation's keys and weights of %llu entries", (ull)e0);
+        LZX_TRY(lzx_alloc_state(fn_name, what, cap, *held + sc.bytes, sc.bytes, &run.more[0]));
+        *held += sc.bytes;
+        sc.keys = static_cast<u64 *>(run.more[0]);
+        sc.keys2 = sc.keys + e0;
+        sc.vals = reinterpret_cast<u32 *>(sc.keys2 + e0);
+        sc.vals2 = sc.vals + lzx_even(e0);
+        sc.tmp = sc.vals2 + lzx_even(e0);
+        sc.runs = reinterpret_cast<u32 *>(static_cast<char *>(sc.tmp) + sc.tmp_bytes);
+    }
+    size_t asked = 0;   // (a level that asked for more than level 0 would be refused here, not run)
+    LZX_TRY(louvain_cub_bytes(n, g.entries, st, &asked));
+    if (asked > sc.tmp_bytes)
+        LZX_FAIL(LZX_ERR_LIMIT, "%s: the scratch of the sort of %llu entries exceeds that of level 0 (%zu bytes)", fn_name, (ull)g.entries, sc.tmp_bytes);
+    size_t tb = sc.tmp_bytes;
+    LZX_HIP(hipcub::DeviceScan::ExclusiveSum(sc.tmp, tb, d_newid, d_newid, (u64)n + 1, st));
+    u32 C = 0;
+    LZX_HIP(hipMemcpyAsync(&C, d_newid + n, sizeof(u32), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    *merged = C < n;
+    if (!*merged) return LZX_OK;
+
+    lzx_with_lanes<32>(G, [&](auto lanes) {
+        lzx_with_weights(g.weights != nullptr, [&](auto w) {
+            hipLaunchKernelGGL((k_agg_keys<lanes, w>), dim3(lzx_row_grid(n, LZX_COM_BLOCK / lanes)), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)a.label, (const u32 *)d_newid, sc.keys, sc.vals, n, C);
+        });
+    });
+    LZX_HIP(hipGetLastError());
+    int key_bits = 33;
+    while (key_bits < 64 && ((u64)C >> (key_bits - 32))) ++key_bits;
+    tb = sc.tmp_bytes;
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairs(sc.tmp, tb, sc.keys, sc.keys2, sc.vals, sc.vals2, g.entries, 0, key_bits, st));
+    tb = sc.tmp_bytes;
+    LZX_HIP(hipcub::DeviceReduce::ReduceByKey(sc.tmp, tb, sc.keys2, sc.keys, sc.vals2, sc.vals, sc.runs, hipcub::Sum(), g.entries, st));
+    u32 runs = 0;
+    LZX_HIP(hipMemcpyAsync(&runs, sc.runs, sizeof(u32), hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    u64 entries = std::min<u64>(runs, g.entries);
+    if (entries) {
+        u64 last = 0;
+        LZX_HIP(hipMemcpy(&last, sc.keys + entries - 1, sizeof(u64), hipMemcpyDeviceToHost));
+        if ((last >> 32) >= C) --entries;   // the dropped diagonal entries' run
+    }
+    // the next level's graph: row_ptr u64 [C + 1], col_idx and weights u32 [entries]
+    const u64 graph_bytes = ((u64)C + 1) * sizeof(u64) + 2 * lzx_even(entries) * sizeof(u32);
+    std::snprintf(what, sizeof what, "the level graph of %u nodes and %llu entries", C, (ull)entries);
+    LZX_TRY(lzx_alloc_state(fn_name, what, cap, *held + graph_bytes, graph_bytes, &blocks.graph[1]));
+    blocks.graph_bytes[1] = graph_bytes;
+    u64 *d_rp = static_cast<u64 *>(blocks.graph[1]);
+    u32 *d_ci = reinterpret_cast<u32 *>(d_rp + C + 1), *d_w = d_ci + lzx_even(entries);
+    u32 *d_stats = reinterpret_cast<u32 *>(a.acc + AC_STATS);
+    LZX_HIP(hipMemsetAsync(d_stats, 0, 2 * sizeof(u32), st));
+    hipLaunchKernelGGL(k_agg_rows, dim3(lzx_vertex_grid(C + 1)), dim3(LZX_COM_BLOCK), 0, st, (const u64 *)sc.keys, entries, d_rp, d_stats, C);
+    if (entries) hipLaunchKernelGGL(k_agg_cols, dim3(lzx_row_grid(entries, LZX_COM_BLOCK)), dim3(LZX_COM_BLOCK), 0, st, (const u64 *)sc.keys, (const u32 *)sc.vals, d_ci, d_w, entries);
+    hipLaunchKernelGGL(k_agg_compose, dim3(lzx_vertex_grid(n0)), dim3(LZX_COM_BLOCK), 0, st, a.comp, (const u32 *)a.label, (const u32 *)d_newid, n0);
+    LZX_HIP(hipGetLastError());
+    u32 stats[2] = {0, 0};
+    LZX_HIP(hipMemcpyAsync(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+    // the partition after this level, canonical (first: `queue`, out: `wait`, sizes: `colour` -- the colouring is done with them)
+    if (level_out) {
+        LZX_HIP(hipMemsetAsync(a.s.counters, 0, CW_WORDS * sizeof(u32), st));
+        LZX_TRY(lzx_comm_canonical(c, a.comp, n0, a.s.queue, a.s.wait, a.s.colour, a.s.counters));
+        LZX_HIP(hipMemcpyAsync(level_out, a.s.wait, sizeof(u32) * n0, hipMemcpyDeviceToHost, st));
+    }
+    LZX_HIP(hipEventRecord(run.ev3, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    LZX_HIP(hipEventElapsedTime(ms, run.ev2, run.ev3));
+    *next = LzxGraphView{d_rp, d_ci, d_w, C, entries, stats[0], stats[1]};
+    return LZX_OK;
+}
 }   // namespace
 
-extern "C" int lzx_louvain(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t max_sweeps, uint32_t max_levels, uint32_t *labels,
-                           uint32_t *level_labels, lzx_louvain_level *levels, lzx_louvain_info *info)
+extern "C" int lzx_louvain(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t max_sweeps, uint32_t max_levels, uint32_t *labels, uint32_t *level_labels, lzx_louvain_level *levels, lzx_louvain_info *info)
 {
     const char *fn_name = "lzx_louvain";
     LZX_TRY(lzx_graph_call_check(c, fn_name, "communities are aggregated"));
@@ -457,298 +631,73 @@ extern "C" int lzx_louvain(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t
     if (c->max_degree >= LZX_LPA_MAX_ROW) LZX_FAIL(LZX_ERR_LIMIT, "%s: a row of %llu entries; rows of 2^30 entries or more are not supported", fn_name, (ull)c->max_degree);
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n0 = (u32)c->n;
-    const u64 e0 = c->nnz;
-    hipStream_t st = c->stream;
-    const u32 group_row = c->lpa_group_opt > 0 ? (u32)std::min<int64_t>(c->lpa_group_opt, LZX_LPA_MAX_ROW) : LZX_LPA_STAGE;
-    const u32 table_row = c->lpa_table_opt > 0 && c->lpa_table_opt < LZX_LPA_SLOTS / 2 ? (u32)c->lpa_table_opt : LZX_LPA_SLOTS / 2;
-    const u32 table_above = std::max(group_row, table_row);   // (a test shape may send longer rows to the groups of lanes)
     const int64_t cap = c->louvain_cap_opt;
+    LzxClassSweep cs(c);
 
-    // the arena: D, I (u64 [n]); d, wait, colour, queue, label, tot, k, the saved labels and tot, comp (u32 [n] each, rounded to 8
-    // bytes), the move list (4 per node); three bins per colour; the counter words and the accumulators
-    const u64 n_al = lzx_even(n0), nb = lzx_class_bins(n0);
-    const u64 bytes = 2 * (u64)n0 * sizeof(u64) + (14 * n_al + nb + CW_WORDS) * sizeof(u32) + AC_WORDS * sizeof(u64);
+    LouvainArena a;
+    const u64 bytes = louvain_arena(n0, nullptr, &a);
     LZX_HIP(hipSetDevice(c->device));
     LzxGraphRun run(c);
     LouvainBlocks blocks(c);
     char what[160];
     std::snprintf(what, sizeof what, "the state of %u vertices (colours, classes, labels, totals, the move list, the modularity's sums)", n0);
     LZX_TRY(lzx_alloc_state(fn_name, what, cap, bytes, bytes, &run.arena));
+    louvain_arena(n0, run.arena, &a);
     u64 held = bytes;   // what the call holds on the device
-    ull *d_D = static_cast<ull *>(run.arena), *d_I = d_D + n0;
-    LzxColorState s;
-    s.d = reinterpret_cast<u32 *>(d_I + n0);
-    s.wait = s.d + n_al;
-    s.colour = s.wait + n_al;
-    s.queue = s.colour + n_al;
-    u32 *d_label = s.queue + n_al, *d_tot = d_label + n_al, *d_k = d_tot + n_al, *d_label0 = d_k + n_al, *d_tot0 = d_label0 + n_al;
-    u32 *d_comp = d_tot0 + n_al, *d_moves = d_comp + n_al;
-    s.bins = d_moves + 4 * n_al;
-    s.counters = s.bins + nb;
-    ull *d_acc = reinterpret_cast<ull *>(s.counters + CW_WORDS);
-    u32 *d_stats = reinterpret_cast<u32 *>(d_acc + AC_STATS);
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
-    LZX_HIP(hipEventCreate(&run.ev2));
-    LZX_HIP(hipEventCreate(&run.ev3));
-    const u32 gb0 = lzx_vertex_grid(n0);
-    hipLaunchKernelGGL(k_louvain_iota, dim3(gb0), dim3(LZX_COM_BLOCK), 0, st, d_comp, n0);
+    for (hipEvent_t *e : {&run.ev0, &run.ev1, &run.ev2, &run.ev3}) LZX_HIP(hipEventCreate(e));
+    hipLaunchKernelGGL(k_fill_u32<true>, dim3(lzx_vertex_grid(n0)), dim3(LZX_COM_BLOCK), 0, c->stream, a.comp, n0, 0u);
     LZX_HIP(hipGetLastError());
 
-    // the aggregation's scratch, allocated by the first level that aggregates: two key and two value arrays of e0 entries, hipcub's
-    u64 *d_keys = nullptr, *d_keys2 = nullptr;
-    u32 *d_vals = nullptr, *d_vals2 = nullptr, *d_runs = nullptr;
-    void *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    u64 scratch_bytes = 0;
-
+    LouvainScratch sc;
     LzxGraphView g = lzx_view_of(c);
     i64 M = 0;
     u32 counted = 0;
-    u64 total_sweeps = 0, total_moves = 0;
-    double color_ms = 0.0, sweep_ms = 0.0, aggregate_ms = 0.0;
+    lzx_louvain_info out{};   // the totals over the counted levels and the times
     while (counted < max_levels) {
-        const u32 n = g.n;
-        const bool weighted = g.weights != nullptr;
-        const u32 gb = lzx_vertex_grid(n);
-        LzxColorResult col;
-        LZX_TRY(lzx_color_core(c, g, run, fn_name, seed, flags, s, true, group_row, table_row, &col));
-        color_ms += col.ms;
-        const u32 *d_cls = s.queue;
-        const u32 G = lzx_lanes_of(c, g);
-
-        // the rows above table_above: their places (in `wait`, which the colouring is done with), the offsets of their tables
-        u32 *d_lpos = s.wait, *d_llen = reinterpret_cast<u32 *>(d_I);
-        u64 *d_loff = reinterpret_cast<u64 *>(d_D);
-        if (g.max_row > table_above) {
-            LZX_TRY(lzx_lpa_far_tables(c, g, fn_name, table_above, cap, held, d_lpos, d_llen, d_loff, s.counters, &blocks.tables, &blocks.table_bytes));
-            held += blocks.table_bytes;
-        }
-        u32 *d_tables = static_cast<u32 *>(blocks.tables);
-        const u32 slices = (u32)std::min<u64>(std::max<u64>(g.max_row / (8 * LZX_COM_BLOCK), 1), 64);   // workgroups that share a long row's entries
-
-        // ---- the sweeps ----
-        LZX_HIP(hipEventRecord(run.ev2, st));
-        LZX_HIP(hipMemsetAsync(d_acc, 0, AC_WORDS * sizeof(u64), st));
-        if (weighted) hipLaunchKernelGGL(k_louvain_init<true>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)s.d, d_k, d_label, d_tot, d_acc, n);
-        else hipLaunchKernelGGL(k_louvain_init<false>, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)s.d, d_k, d_label, d_tot, d_acc, n);
-        hipLaunchKernelGGL(k_louvain_sum_sq, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_tot, d_acc, n);
-        LZX_HIP(hipGetLastError());
-        u64 words[AC_WORDS] = {};   // I, sum tot^2, the moves, the window words, ..., sum tot
-        LZX_HIP(hipMemcpyAsync(words, d_acc, sizeof(words), hipMemcpyDeviceToHost, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        u64 inner = words[AC_INNER], sum_sq = words[AC_SQ];
-        if (counted == 0) M = (i64)words[AC_SUM];   // the sum of the k_i = the off-diagonal entries (tot is k here)
-        i64 qnum = M * (i64)inner - (i64)sum_sq;
-        const LouvainSweep sw{d_k, d_label, d_tot, d_moves, reinterpret_cast<u32 *>(d_acc + AC_TAIL), M, n};
-        u32 sweeps = 0, accepted = 0, reverted = 0, capped = 0;
-        u64 moves = 0;
-        u32 path_rows[3] = {0, 0, 0};
-        for (u32 k = 0; k < col.colours; ++k)
-            for (u32 p = 0; p < 3; ++p) path_rows[p] += col.run[3 * (size_t)k + p + 1] - col.run[3 * (size_t)k + p];
-        while (true) {
-            if (accepted == max_sweeps) {
-                capped = 1;
-                break;
-            }
-            ++sweeps;
-            LZX_HIP(hipMemcpyAsync(d_label0, d_label, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
-            LZX_HIP(hipMemcpyAsync(d_tot0, d_tot, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
-            LZX_HIP(hipMemsetAsync(d_acc + AC_SQ, 0, 3 * sizeof(u64), st));   // the sum, the list's end, the window words
-            u32 parity = 0;
-            for (u32 k = 0; k < col.colours; ++k) {
-                const u32 *r = col.run.data() + 3 * (size_t)k;
-                if (r[1] > r[0])
-                    lzx_with_lanes<32>(G, [&](auto lanes) {
-                        const dim3 grid(lzx_row_grid(r[1] - r[0], LZX_COM_BLOCK / lanes));
-                        if (weighted) hipLaunchKernelGGL((k_louvain_group<lanes, true>), grid, dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, d_cls, r[0], r[1] - r[0]);
-                        else hipLaunchKernelGGL((k_louvain_group<lanes, false>), grid, dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, d_cls, r[0], r[1] - r[0]);
-                    });
-                if (r[2] > r[1]) {
-                    if (weighted) hipLaunchKernelGGL(k_louvain_table<true>, dim3(r[2] - r[1]), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, d_cls, r[1]);
-                    else hipLaunchKernelGGL(k_louvain_table<false>, dim3(r[2] - r[1]), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, sw, d_cls, r[1]);
-                }
-                if (r[3] > r[2]) {
-                    if (!d_tables) LZX_FAIL(LZX_ERR_LIMIT, "%s: a row above %u entries without a table", fn_name, table_above);
-                    if (weighted) hipLaunchKernelGGL(k_louvain_far_insert<true>, dim3(r[3] - r[2], slices), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)d_label, d_cls, r[2], (const u32 *)d_lpos, (const u64 *)d_loff, d_tables);
-                    else hipLaunchKernelGGL(k_louvain_far_insert<false>, dim3(r[3] - r[2], slices), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)d_label, d_cls, r[2], (const u32 *)d_lpos, (const u64 *)d_loff, d_tables);
-                    hipLaunchKernelGGL(k_louvain_far_pick, dim3(r[3] - r[2]), dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, sw, d_cls, r[2], (const u32 *)d_lpos, (const u64 *)d_loff, d_tables);
-                }
-                if (r[3] > r[0]) {
-                    hipLaunchKernelGGL(k_louvain_apply, dim3(lzx_vertex_grid(r[3] - r[0])), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_moves, (const u32 *)d_k, d_tot, d_acc, parity, n);
-                    parity ^= 1u;
-                }
-                LZX_HIP(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_louvain_sum_sq, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_tot, d_acc, n);
-            LZX_HIP(hipGetLastError());
-            LZX_HIP(hipMemcpyAsync(words, d_acc, sizeof(words), hipMemcpyDeviceToHost, st));
-            LZX_HIP(hipStreamSynchronize(st));
-            const u32 moved = std::min((u32)(words[AC_TAIL] & 0xffffffffull), n);
-            if (moved == 0) break;
-            const i64 after = M * (i64)words[AC_INNER] - (i64)words[AC_SQ];
-            if (after <= qnum) {   // the sweep is taken back
-                LZX_HIP(hipMemcpyAsync(d_label, d_label0, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
-                LZX_HIP(hipMemcpyAsync(d_tot, d_tot0, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
-                LZX_HIP(hipMemcpyAsync(d_acc + AC_INNER, &inner, sizeof(u64), hipMemcpyHostToDevice, st));
-                LZX_HIP(hipStreamSynchronize(st));
-                reverted = 1;
-                break;
-            }
-            inner = words[AC_INNER];
-            sum_sq = words[AC_SQ];
-            qnum = after;
-            moves += moved;
-            ++accepted;
-        }
-        LZX_HIP(hipEventRecord(run.ev3, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        LZX_HIP(hipEventElapsedTime(&ms, run.ev2, run.ev3));
-        sweep_ms += ms;
-        held -= blocks.table_bytes;
+        // the colouring and the classes, the tables of the rows above table_above, the sweeps
+        LZX_TRY(lzx_class_sweep_open(c, g, run, fn_name, seed, flags, a.s, a.D, a.I, cap, held, &blocks.tables, &blocks.table_bytes, &cs));
+        out.color_ms += cs.col.ms;
+        LouvainLevel lv;
+        LZX_TRY(louvain_level_sweeps(c, g, run, a, cs, fn_name, max_sweeps, counted == 0, &M, &lv));
+        out.sweep_ms += lv.ms;
         blocks.drop(blocks.tables, blocks.table_bytes);
 
-        // ---- aggregation: the labels that occur (flags and new ids in the move list's words) ----
-        LZX_HIP(hipEventRecord(run.ev2, st));
-        u32 *d_newid = d_moves;
-        LZX_HIP(hipMemsetAsync(d_newid, 0, sizeof(u32) * ((u64)n + 1), st));
-        hipLaunchKernelGGL(k_agg_flag, dim3(gb), dim3(LZX_COM_BLOCK), 0, st, (const u32 *)d_label, d_newid, n);
-        LZX_HIP(hipGetLastError());
-        if (!run.more[0]) {
-            // (sized for level 0: every later level has fewer nodes and no more entries)
-            size_t scan_b = 0, sort_b = 0, reduce_b = 0;
-            LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, d_newid, d_newid, (u64)n0 + 1, st));
-            LZX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, d_keys, d_keys2, d_vals, d_vals2, e0, 0, 64, st));
-            LZX_HIP(hipcub::DeviceReduce::ReduceByKey(nullptr, reduce_b, d_keys2, d_keys, d_vals2, d_vals, d_runs, hipcub::Sum(), e0, st));
-            tmp_bytes = (std::max(scan_b, std::max(sort_b, reduce_b)) + 15) & ~(size_t)15;
-            scratch_bytes = 2 * e0 * sizeof(u64) + 2 * lzx_even(e0) * sizeof(u32) + tmp_bytes + 16;
-            std::snprintf(what, sizeof what, "the aggregation's keys and weights of %llu entries", (ull)e0);
-            LZX_TRY(lzx_alloc_state(fn_name, what, cap, held + scratch_bytes, scratch_bytes, &run.more[0]));
-            held += scratch_bytes;
-            d_keys = static_cast<u64 *>(run.more[0]);
-            d_keys2 = d_keys + e0;
-            d_vals = reinterpret_cast<u32 *>(d_keys2 + e0);
-            d_vals2 = d_vals + lzx_even(e0);
-            d_tmp = d_vals2 + lzx_even(e0);
-            d_runs = reinterpret_cast<u32 *>(static_cast<char *>(d_tmp) + tmp_bytes);
-        }
-        {   // (hipcub's scratch was sized for level 0: a level that asked for more would be refused here, not run)
-            size_t scan_b = 0, sort_b = 0, reduce_b = 0;
-            LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, d_newid, d_newid, (u64)n + 1, st));
-            LZX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, d_keys, d_keys2, d_vals, d_vals2, g.entries, 0, 64, st));
-            LZX_HIP(hipcub::DeviceReduce::ReduceByKey(nullptr, reduce_b, d_keys2, d_keys, d_vals2, d_vals, d_runs, hipcub::Sum(), g.entries, st));
-            if (std::max(scan_b, std::max(sort_b, reduce_b)) > tmp_bytes)
-                LZX_FAIL(LZX_ERR_LIMIT, "%s: the scratch of the sort of %llu entries exceeds that of level 0 (%zu bytes)", fn_name, (ull)g.entries, tmp_bytes);
-        }
-        size_t tb = tmp_bytes;
-        LZX_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_newid, d_newid, (u64)n + 1, st));
-        u32 C = 0;
-        LZX_HIP(hipMemcpyAsync(&C, d_newid + n, sizeof(u32), hipMemcpyDeviceToHost, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        if (C >= n) break;   // the level changed nothing: it is not counted
-
-        lzx_with_lanes<32>(G, [&](auto lanes) {
-            const dim3 grid(lzx_row_grid(n, LZX_COM_BLOCK / lanes));
-            if (weighted) hipLaunchKernelGGL((k_agg_keys<lanes, true>), grid, dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)d_label, (const u32 *)d_newid, d_keys, d_vals, n, C);
-            else hipLaunchKernelGGL((k_agg_keys<lanes, false>), grid, dim3(LZX_COM_BLOCK), 0, st, g.row_ptr, g.col_idx, g.weights, (const u32 *)d_label, (const u32 *)d_newid, d_keys, d_vals, n, C);
-        });
-        LZX_HIP(hipGetLastError());
-        int key_bits = 33;
-        while (key_bits < 64 && ((u64)C >> (key_bits - 32))) ++key_bits;
-        tb = tmp_bytes;
-        LZX_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, g.entries, 0, key_bits, st));
-        tb = tmp_bytes;
-        LZX_HIP(hipcub::DeviceReduce::ReduceByKey(d_tmp, tb, d_keys2, d_keys, d_vals2, d_vals, d_runs, hipcub::Sum(), g.entries, st));
-        u32 runs = 0;
-        LZX_HIP(hipMemcpyAsync(&runs, d_runs, sizeof(u32), hipMemcpyDeviceToHost, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        u64 entries = std::min<u64>(runs, g.entries);
-        if (entries) {
-            u64 last = 0;
-            LZX_HIP(hipMemcpy(&last, d_keys + entries - 1, sizeof(u64), hipMemcpyDeviceToHost));
-            if ((last >> 32) >= C) --entries;   // the dropped diagonal entries' run
-        }
-        // the next level's graph: row_ptr u64 [C + 1], col_idx and weights u32 [entries]
-        const u64 graph_bytes = ((u64)C + 1) * sizeof(u64) + 2 * lzx_even(entries) * sizeof(u32);
-        std::snprintf(what, sizeof what, "the level graph of %u nodes and %llu entries", C, (ull)entries);
-        LZX_TRY(lzx_alloc_state(fn_name, what, cap, held + graph_bytes, graph_bytes, &blocks.graph[1]));
-        blocks.graph_bytes[1] = graph_bytes;
-        u64 *d_rp = static_cast<u64 *>(blocks.graph[1]);
-        u32 *d_ci = reinterpret_cast<u32 *>(d_rp + C + 1), *d_w = d_ci + lzx_even(entries);
-        LZX_HIP(hipMemsetAsync(d_stats, 0, 2 * sizeof(u32), st));
-        hipLaunchKernelGGL(k_agg_rows, dim3(lzx_vertex_grid(C + 1)), dim3(LZX_COM_BLOCK), 0, st, (const u64 *)d_keys, entries, d_rp, d_stats, C);
-        if (entries) hipLaunchKernelGGL(k_agg_cols, dim3(entry_grid(entries)), dim3(LZX_COM_BLOCK), 0, st, (const u64 *)d_keys, (const u32 *)d_vals, d_ci, d_w, entries);
-        hipLaunchKernelGGL(k_agg_compose, dim3(gb0), dim3(LZX_COM_BLOCK), 0, st, d_comp, (const u32 *)d_label, (const u32 *)d_newid, n0);
-        LZX_HIP(hipGetLastError());
-        u32 stats[2] = {0, 0};
-        LZX_HIP(hipMemcpyAsync(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost, st));
-        // the partition after this level, canonical (first: `queue`, out: `wait`, sizes: `colour` -- the colouring is done with them)
-        if (level_labels) {
-            LZX_HIP(hipMemsetAsync(s.counters, 0, CW_WORDS * sizeof(u32), st));
-            LZX_TRY(lzx_comm_canonical(c, d_comp, n0, s.queue, s.wait, s.colour, s.counters));
-            LZX_HIP(hipMemcpyAsync(level_labels + (size_t)counted * n0, s.wait, sizeof(u32) * n0, hipMemcpyDeviceToHost, st));
-        }
-        LZX_HIP(hipEventRecord(run.ev3, st));
-        LZX_HIP(hipStreamSynchronize(st));
-        LZX_HIP(hipEventElapsedTime(&ms, run.ev2, run.ev3));
-        aggregate_ms += ms;
+        LzxGraphView next;
+        bool merged = false;
+        float ms = 0.f;
+        LZX_TRY(louvain_aggregate(c, g, run, blocks, a, sc, fn_name, n0, c->nnz, cs.G, cap, &held, level_labels ? level_labels + (size_t)counted * n0 : nullptr, &merged, &next, &ms));
+        if (!merged) break;   // the level changed nothing: it is not counted
+        out.aggregate_ms += ms;
         if (levels) {
-            lzx_louvain_level *L = levels + counted;
-            L->nodes = n;
-            L->entries = g.entries;
-            L->communities = C;
-            L->moves = moves;
-            L->inner_entries = inner;
-            L->sum_degree_sq = sum_sq;
-            L->colors = col.colours;
-            L->color_rounds = col.rounds;
-            L->sweeps = sweeps;
-            L->reverted = reverted;
-            L->capped = capped;
-            for (u32 p = 0; p < 3; ++p) L->path_rows[p] = path_rows[p];
+            lzx_louvain_level &L = lv.rec;
+            L.nodes = g.n;
+            L.entries = g.entries;
+            L.communities = next.n;
+            L.colors = cs.col.colours;
+            L.color_rounds = cs.col.rounds;
+            for (u32 p = 0; p < 3; ++p)   // the rows per path in one sweep
+                for (u32 k = 0; k < cs.col.colours; ++k) L.path_rows[p] += cs.col.run[3 * (size_t)k + p + 1] - cs.col.run[3 * (size_t)k + p];
+            levels[counted] = L;
         }
         ++counted;
-        total_sweeps += sweeps;
-        total_moves += moves;
+        out.sweeps += lv.rec.sweeps;
+        out.moves += lv.rec.moves;
         // the next level takes the place of this one
         blocks.drop(blocks.graph[0], blocks.graph_bytes[0]);
-        blocks.graph[0] = blocks.graph[1];
-        blocks.graph_bytes[0] = blocks.graph_bytes[1];
-        blocks.graph[1] = nullptr;
-        blocks.graph_bytes[1] = 0;
-        held = bytes + scratch_bytes + blocks.graph_bytes[0];
-        g = LzxGraphView{d_rp, d_ci, d_w, C, entries, stats[0], stats[1]};
+        std::swap(blocks.graph[0], blocks.graph[1]);
+        std::swap(blocks.graph_bytes[0], blocks.graph_bytes[1]);
+        held = bytes + sc.bytes + blocks.graph_bytes[0];
+        g = next;
     }
 
     // ---- the result: canonical labels, the statistics, the modularity on the handle's pattern ----
     const LzxGraphView g0 = lzx_view_of(c);
-    LZX_TRY(lzx_color_degrees(c, g0, s.d, nullptr, s.counters));   // (the degrees of level 0 again, the counter words 0)
-    u32 *d_out = s.wait;
-    LZX_TRY(lzx_comm_canonical(c, d_comp, n0, s.queue, d_out, s.colour, s.counters));
-    u32 cw[CW_WORDS];
-    LZX_HIP(hipMemcpyAsync(cw, s.counters, sizeof(cw), hipMemcpyDeviceToHost, st));
-    std::vector<u64> hD, hI;
-    LzxModResult mod;
-    LZX_TRY(lzx_modularity_core(c, g0, d_out, s.d, s.queue, d_D, d_I, hD, hI, &mod));
-    if (labels) LZX_HIP(hipMemcpyAsync(labels, d_out, sizeof(u32) * n0, hipMemcpyDeviceToHost, st));
-    LZX_HIP(hipStreamSynchronize(st));
-    if (info) {
-        const u64 key = (u64)cw[CW_KEY] | ((u64)cw[CW_KEY + 1] << 32);
-        info->n_communities = cw[CW_COMMUNITIES];
-        info->largest_size = key >> 32;
-        info->sweeps = total_sweeps;
-        info->moves = total_moves;
-        info->inner_entries = mod.inner;
-        info->entries = mod.entries;
-        info->sum_degree_sq = mod.sum_sq;
-        info->largest_label = LZX_COM_NONE - (u32)(key & 0xffffffffull);
-        info->levels = counted;
-        info->modularity = mod.q;
-        info->color_ms = color_ms;
-        info->sweep_ms = sweep_ms;
-        info->aggregate_ms = aggregate_ms;
-        info->loop_ms = lzx_ms_since(t0);
-    }
+    LZX_TRY(lzx_color_degrees(c, g0, a.s.d, nullptr, a.s.counters));   // (the degrees of level 0 again, the counter words 0)
+    LzxCommResult res;
+    LZX_TRY(lzx_comm_finish(c, g0, a.comp, a.s, a.D, a.I, labels, &res));
+    res.fill(&out);
+    out.levels = counted;
+    out.loop_ms = lzx_ms_since(t0);
+    if (info) *info = out;
     return LZX_OK;
 }
