@@ -683,23 +683,17 @@ extern "C" int lzx_color(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t *
     const u32 n = (u32)c->n;
     const LzxGraphView g = lzx_view_of(c);
 
-    // one arena: d, wait, colour, queue (u32 [n] each, rounded to 8 bytes), three bins per colour, the counter words
-    const u64 n_al = lzx_even(n), nb = lzx_class_bins(n);
-    const u64 bytes = (4 * n_al + nb + CW_WORDS) * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
+    LzxColorState s;
     LzxGraphRun run(c);
     char what[96];
     std::snprintf(what, sizeof what, "the state of %u vertices (degrees, waits, colours, the queue)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, -1, bytes, bytes, &run.arena));
-    LzxColorState s;
-    s.d = static_cast<u32 *>(run.arena);
-    s.wait = s.d + n_al;
-    s.colour = s.wait + n_al;
-    s.queue = s.colour + n_al;
-    s.bins = s.queue + n_al;
-    s.counters = s.bins + nb;
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, -1, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        for (u32 **p : {&s.d, &s.wait, &s.colour, &s.queue}) k.take(*p, lzx_even(n));
+        k.take(s.bins, lzx_class_bins(n));   // three per colour
+        k.take(s.counters, CW_WORDS);
+    }));
+    LZX_TRY(run.events(2));
     LzxColorResult res;
     LZX_TRY(lzx_color_core(c, g, run, fn_name, seed, flags, s, false, 0xffffffffu, 0xffffffffu, &res));
     if (color) LZX_HIP(hipMemcpyAsync(color, s.colour, sizeof(u32) * n, hipMemcpyDeviceToHost, c->stream));
@@ -729,26 +723,23 @@ extern "C" int lzx_label_propagation(lzx_handle c, uint64_t seed, uint32_t flags
     hipStream_t st = c->stream;
     LzxClassSweep cs(c);
 
-    // one arena: D, I (u64 [n]), d, wait, colour, queue, label (u32 [n] each, rounded to 8 bytes), three bins per colour, the counter
-    // words; the tables of the rows above table_row follow once they are known
-    const u64 n_al = lzx_even(n), nb = lzx_class_bins(n);
-    const u64 bytes = 2 * (u64)n * sizeof(u64) + (5 * n_al + nb + CW_WORDS) * sizeof(u32);
+    // the vertices' arena; the tables of the rows above table_row follow in one of their own once they are known
     LZX_HIP(hipSetDevice(c->device));
+    ull *d_D, *d_I;
+    LzxColorState s;
+    u32 *d_label;
+    u64 bytes = 0;
     LzxGraphRun run(c);
     char what[128];
     std::snprintf(what, sizeof what, "the state of %u vertices (degrees, colours, classes, labels, the modularity's sums)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->lpa_cap_opt, bytes, bytes, &run.arena));
-    ull *d_D = static_cast<ull *>(run.arena), *d_I = d_D + n;
-    LzxColorState s;
-    s.d = reinterpret_cast<u32 *>(d_I + n);
-    s.wait = s.d + n_al;
-    s.colour = s.wait + n_al;
-    s.queue = s.colour + n_al;
-    u32 *d_label = s.queue + n_al;
-    s.bins = d_label + n_al;
-    s.counters = s.bins + nb;
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, c->lpa_cap_opt, 0, &run.arena, &bytes, [&](LzxCarver &k) {
+        k.take(d_D, n);
+        k.take(d_I, n);
+        for (u32 **p : {&s.d, &s.wait, &s.colour, &s.queue, &d_label}) k.take(*p, lzx_even(n));
+        k.take(s.bins, lzx_class_bins(n));   // three per colour
+        k.take(s.counters, CW_WORDS);
+    }));
+    LZX_TRY(run.events(2));
     u64 table_bytes = 0;
     LZX_TRY(lzx_class_sweep_open(c, g, run, fn_name, seed, flags, s, d_D, d_I, c->lpa_cap_opt, bytes, &run.more[0], &table_bytes, &cs));
 
@@ -815,16 +806,18 @@ extern "C" int lzx_modularity(lzx_handle c, const uint32_t *labels, double *q, l
     }
     hipStream_t st = c->stream;
 
-    // one arena: D, I (u64 [n]), label, d, inner (u32 [n] each, rounded to 8 bytes), the counter words
-    const u64 n_al = lzx_even(n);
-    const u64 bytes = 2 * (u64)n * sizeof(u64) + (3 * n_al + CW_WORDS) * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
+    ull *d_D, *d_I;
+    u32 *d_label, *d_d, *d_inner, *d_counters;
     LzxGraphRun run(c);
     char what[96];
     std::snprintf(what, sizeof what, "the state of %u vertices (labels, degrees, inner entries, the sums)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, -1, bytes, bytes, &run.arena));
-    ull *d_D = static_cast<ull *>(run.arena), *d_I = d_D + n;
-    u32 *d_label = reinterpret_cast<u32 *>(d_I + n), *d_d = d_label + n_al, *d_inner = d_d + n_al, *d_counters = d_inner + n_al;
+    LZX_TRY(lzx_carve_state(fn_name, what, -1, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        k.take(d_D, n);
+        k.take(d_I, n);
+        for (u32 **p : {&d_label, &d_d, &d_inner}) k.take(*p, lzx_even(n));
+        k.take(d_counters, CW_WORDS);
+    }));
     LZX_HIP(hipMemcpyAsync(d_label, labels, sizeof(u32) * n, hipMemcpyHostToDevice, st));
     LZX_TRY(lzx_color_degrees(c, g, d_d, nullptr, d_counters));
     std::vector<u64> hD, hI;

@@ -130,7 +130,6 @@ struct LzxModResult {
     u64 inner = 0, entries = 0, sum_sq = 0;
 };
 
-inline u64 lzx_even(u64 x) { return (x + 1) & ~1ull; }
 inline u64 lzx_class_bins(u32 n) { return lzx_even(3 * (u64)std::min<u32>(n, LZX_COLOR_CAP)); }
 inline u32 lzx_vertex_grid(u32 n) { return (n + LZX_COM_BLOCK - 1) / LZX_COM_BLOCK; }
 inline u32 lzx_lanes_of(lzx_ctx *c, const LzxGraphView &g) { return lzx_lanes_per_row_of(c, g.entries, g.rows_active, 32); }

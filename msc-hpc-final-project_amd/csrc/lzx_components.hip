@@ -178,20 +178,21 @@ extern "C" int lzx_components(lzx_handle c, uint32_t *labels, lzx_components_inf
     const u32 n = (u32)c->n;
     hipStream_t st = c->stream;
 
-    // one arena: f, gf, fn, sizes (u32 [n] each, rounded to 8 bytes), the counting pass's partials, the two result words, the flag
-    const u64 n_al = ((u64)n + 1) & ~1ull;
-    const u32 np = (u32)std::min<u64>(LZX_CC_STAT_GRID, ((u64)n + LZX_CC_BLOCK - 1) / LZX_CC_BLOCK);
-    const u64 bytes = 4 * n_al * sizeof(u32) + (u64)np * (sizeof(double) + sizeof(unsigned long long)) + 2 * sizeof(unsigned long long) + 8;
+    const u32 np = (u32)std::min<u64>(LZX_CC_STAT_GRID, ((u64)n + LZX_CC_BLOCK - 1) / LZX_CC_BLOCK);   // the counting pass's partials
+    u32 *d_f, *d_gf, *d_fn, *d_sizes, *d_changed;
+    double *d_pc;
+    unsigned long long *d_pk, *d_out;
     LzxGraphRun run(c);
     char what[96];
     std::snprintf(what, sizeof what, "the state of %u vertices (parents, grandparents, next parents, sizes)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, -1, bytes, bytes, &run.arena));
-    u32 *d_f = static_cast<u32 *>(run.arena), *d_gf = d_f + n_al, *d_fn = d_gf + n_al, *d_sizes = d_fn + n_al;
-    double *d_pc = reinterpret_cast<double *>(d_sizes + n_al);
-    unsigned long long *d_pk = reinterpret_cast<unsigned long long *>(d_pc + np), *d_out = d_pk + np;
-    u32 *d_changed = reinterpret_cast<u32 *>(d_out + 2);
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, -1, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        for (u32 **p : {&d_f, &d_gf, &d_fn, &d_sizes}) k.take(*p, lzx_even(n));
+        k.take(d_pc, np);
+        k.take(d_pk, np);
+        k.take(d_out, 2);
+        k.take(d_changed, 2);   // (the flag, in a word of eight bytes)
+    }));
+    LZX_TRY(run.events(2));
 
     // lanes per row: about half the mean degree of the rows that have an edge, so that a typical row is two loads per lane
     const u32 G = lzx_lanes_per_row(c, c->nnz, 32);

@@ -113,19 +113,17 @@ extern "C" int lzx_core_numbers(lzx_handle c, uint32_t *core, uint32_t *layer, l
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
 
-    // one arena: deg, layer, core, order (u32 [n] each, rounded to 8 bytes), the queue's end and the minimum
-    const u64 n_al = ((u64)n + 1) & ~1ull;
-    const u64 bytes = 4 * n_al * sizeof(u32) + 2 * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    u32 *d_deg, *d_layer, *d_core, *d_order, *d_counters;
     LzxGraphRun run(c);
     char what[96];
     std::snprintf(what, sizeof what, "the state of %u vertices (remaining degrees, layers, core numbers, the queue)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->core_cap_opt, bytes, bytes, &run.arena));
-    u32 *d_deg = static_cast<u32 *>(run.arena), *d_layer = d_deg + n_al, *d_core = d_layer + n_al, *d_order = d_core + n_al;
-    u32 *d_counters = d_order + n_al;
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, c->core_cap_opt, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        for (u32 **p : {&d_deg, &d_layer, &d_core, &d_order}) k.take(*p, lzx_even(n));
+        k.take(d_counters, 2);   // the queue's end and the minimum
+    }));
+    LZX_TRY(run.events(2));
 
     // lanes per row of the window: about half the mean degree of the rows that have an edge.  Rows of more than 64 G entries
     // (256 ... 2048: more than 64 trips of a group) go to the long-row launch.

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "lzx_internal.h"
+#include "lzx_carve.h"
 
 // one GPU, a graph, all of it on this handle; `what`: "<what the call does> on one GPU handle".  A call that passes starts with
 // no lanes per row on record (lzx_lanes_per_row)
@@ -33,6 +34,14 @@ struct LzxGraphRun {
     void *arena = nullptr, *more[2] = {nullptr, nullptr};
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     explicit LzxGraphRun(lzx_ctx *c_) : c(c_) {}
+    // ev0 .. ev(k - 1), k <= 4
+    int events(u32 k)
+    {
+        hipEvent_t *ev[4] = {&ev0, &ev1, &ev2, &ev3};
+        if (k > 4) LZX_FAIL(LZX_ERR_ARG, "LzxGraphRun::events: %u events asked for, a run holds 4", k);
+        for (u32 i = 0; i < k; ++i) LZX_HIP(hipEventCreate(ev[i]));
+        return LZX_OK;
+    }
     ~LzxGraphRun()
     {
         (void)hipSetDevice(c->device);
@@ -49,6 +58,26 @@ struct LzxGraphRun {
 // *out = alloc_bytes of device memory for a state of state_bytes (`what` names it), or the error: a state above cap (a test
 // shape *_state_bytes; < 0: none) counts as out of device memory (lzx_solve.hip)
 int lzx_alloc_state(const char *fn, const char *what, int64_t cap, u64 state_bytes, u64 alloc_bytes, void **out);
+
+// One arena through the carver (lzx_carve.h).  layout(LzxCarver &) is the list of the arena's pieces: it is counted over a null
+// base, allocated into *slot by lzx_alloc_state -- the state is `held`, the bytes the call holds already, plus the list's state
+// bytes; the allocation is everything the list takes -- and carved from the allocation.  *bytes (where given): the list's state
+// bytes.  A list whose two passes disagree, or that puts a piece off its type's alignment, fails here, before any kernel is
+// launched on it; *slot is the caller's to free, as after any other failure.
+template <typename Layout>
+int lzx_carve_state(const char *fn, const char *what, int64_t cap, u64 held, void **slot, u64 *bytes, Layout layout)
+{
+    LzxCarver counted;
+    layout(counted);
+    LZX_TRY(lzx_alloc_state(fn, what, cap, held + counted.state_bytes(), counted.at, slot));
+    LzxCarver carved(*slot);
+    layout(carved);
+    if (!carved.agrees_with(counted))
+        LZX_FAIL(LZX_ERR_LIMIT, "%s: the layout of %s counts %llu bytes and carves %llu%s", fn, what, (ull)counted.at, (ull)carved.at,
+                 carved.misaligned || counted.misaligned ? ", with a piece off its alignment" : "");
+    if (bytes) *bytes = counted.state_bytes();
+    return LZX_OK;
+}
 
 // what a launch over G lanes per row walks: the caller-order rows, or the rows of the oriented copy (lzx_tri_orient.h)
 enum LzxLanesOver { LZX_OVER_ROWS, LZX_OVER_ORIENTED };

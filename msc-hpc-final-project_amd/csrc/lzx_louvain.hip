@@ -398,30 +398,22 @@ struct LouvainBlocks {
     LouvainBlocks &operator=(const LouvainBlocks &) = delete;
 };
 
-// The arena: D, I (u64 [n0]); d, wait, colour, queue, label, tot, k, the saved labels and tot, comp (u32 [n0] each, rounded to 8
-// bytes), the move list (4 per node); three bins per colour; the counter words and the accumulators.
 struct LouvainArena {
     ull *D, *I;
     LzxColorState s;
     u32 *label, *tot, *k, *label0, *tot0, *comp, *moves;
     ull *acc;
 };
-// the arena's bytes for n0 vertices, and its pointers carved from base in the order they are counted
-u64 louvain_arena(u32 n0, void *base, LouvainArena *a)
+// the arena of n0 vertices (label0, tot0: the labels and tot a sweep may be taken back to)
+void louvain_arena(LzxCarver &k, u32 n0, LouvainArena *a)
 {
     const u64 n_al = lzx_even(n0);
-    u64 at = 0;
-    auto carve = [&](auto *&p, u64 count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + at);
-        at += count * sizeof(*p);
-    };
-    for (ull **p : {&a->D, &a->I}) carve(*p, n0);
-    for (u32 **p : {&a->s.d, &a->s.wait, &a->s.colour, &a->s.queue, &a->label, &a->tot, &a->k, &a->label0, &a->tot0, &a->comp}) carve(*p, n_al);
-    carve(a->moves, 4 * n_al);
-    carve(a->s.bins, lzx_class_bins(n0));
-    carve(a->s.counters, CW_WORDS);
-    carve(a->acc, AC_WORDS);
-    return at;
+    for (ull **p : {&a->D, &a->I}) k.take(*p, n0);
+    for (u32 **p : {&a->s.d, &a->s.wait, &a->s.colour, &a->s.queue, &a->label, &a->tot, &a->k, &a->label0, &a->tot0, &a->comp}) k.take(*p, n_al);
+    k.take(a->moves, 4 * n_al);   // 4 words per node
+    k.take(a->s.bins, lzx_class_bins(n0));
+    k.take(a->s.counters, CW_WORDS);
+    k.take(a->acc, AC_WORDS);
 }
 
 // what the sweeps of a level leave
@@ -546,16 +538,16 @@ int louvain_aggregate(lzx_ctx *c, const LzxGraphView &g, LzxGraphRun &run, Louva
     if (!run.more[0]) {
         LZX_TRY(louvain_cub_bytes(n0, e0, st, &sc.tmp_bytes));
         sc.tmp_bytes = (sc.tmp_bytes + 15) & ~(size_t)15;
-        sc.bytes = 2 * e0 * sizeof(u64) + 2 * lzx_even(e0) * sizeof(u32) + sc.tmp_bytes + 16;
         std::snprintf(what, sizeof what, "the aggregation's keys and weights of %llu entries", (ull)e0);
-        LZX_TRY(lzx_alloc_state(fn_name, what, cap, *held + sc.bytes, sc.bytes, &run.more[0]));
+        LZX_TRY(lzx_carve_state(fn_name, what, cap, *held, &run.more[0], &sc.bytes, [&](LzxCarver &k) {
+            k.take(sc.keys, e0);
+            k.take(sc.keys2, e0);
+            k.take(sc.vals, lzx_even(e0));
+            k.take(sc.vals2, lzx_even(e0));
+            k.take_bytes(sc.tmp, sc.tmp_bytes);
+            k.take(sc.runs, 4);   // (the count, in 16 bytes)
+        }));
         *held += sc.bytes;
-        sc.keys = static_cast<u64 *>(run.more[0]);
-        sc.keys2 = sc.keys + e0;
-        sc.vals = reinterpret_cast<u32 *>(sc.keys2 + e0);
-        sc.vals2 = sc.vals + lzx_even(e0);
-        sc.tmp = sc.vals2 + lzx_even(e0);
-        sc.runs = reinterpret_cast<u32 *>(static_cast<char *>(sc.tmp) + sc.tmp_bytes);
     }
     size_t asked = 0;   // (a level that asked for more than level 0 would be refused here, not run)
     LZX_TRY(louvain_cub_bytes(n, g.entries, st, &asked));
@@ -590,13 +582,15 @@ int louvain_aggregate(lzx_ctx *c, const LzxGraphView &g, LzxGraphRun &run, Louva
         LZX_HIP(hipMemcpy(&last, sc.keys + entries - 1, sizeof(u64), hipMemcpyDeviceToHost));
         if ((last >> 32) >= C) --entries;   // the dropped diagonal entries' run
     }
-    // the next level's graph: row_ptr u64 [C + 1], col_idx and weights u32 [entries]
-    const u64 graph_bytes = ((u64)C + 1) * sizeof(u64) + 2 * lzx_even(entries) * sizeof(u32);
+    // the next level's graph
+    u64 *d_rp;
+    u32 *d_ci, *d_w;
     std::snprintf(what, sizeof what, "the level graph of %u nodes and %llu entries", C, (ull)entries);
-    LZX_TRY(lzx_alloc_state(fn_name, what, cap, *held + graph_bytes, graph_bytes, &blocks.graph[1]));
-    blocks.graph_bytes[1] = graph_bytes;
-    u64 *d_rp = static_cast<u64 *>(blocks.graph[1]);
-    u32 *d_ci = reinterpret_cast<u32 *>(d_rp + C + 1), *d_w = d_ci + lzx_even(entries);
+    LZX_TRY(lzx_carve_state(fn_name, what, cap, *held, &blocks.graph[1], &blocks.graph_bytes[1], [&](LzxCarver &k) {
+        k.take(d_rp, (u64)C + 1);
+        k.take(d_ci, lzx_even(entries));
+        k.take(d_w, lzx_even(entries));
+    }));
     u32 *d_stats = reinterpret_cast<u32 *>(a.acc + AC_STATS);
     LZX_HIP(hipMemsetAsync(d_stats, 0, 2 * sizeof(u32), st));
     hipLaunchKernelGGL(k_agg_rows, dim3(lzx_vertex_grid(C + 1)), dim3(LZX_COM_BLOCK), 0, st, (const u64 *)sc.keys, entries, d_rp, d_stats, C);
@@ -635,16 +629,15 @@ extern "C" int lzx_louvain(lzx_handle c, uint64_t seed, uint32_t flags, uint32_t
     LzxClassSweep cs(c);
 
     LouvainArena a;
-    const u64 bytes = louvain_arena(n0, nullptr, &a);
+    u64 bytes = 0;
     LZX_HIP(hipSetDevice(c->device));
     LzxGraphRun run(c);
     LouvainBlocks blocks(c);
     char what[160];
     std::snprintf(what, sizeof what, "the state of %u vertices (colours, classes, labels, totals, the move list, the modularity's sums)", n0);
-    LZX_TRY(lzx_alloc_state(fn_name, what, cap, bytes, bytes, &run.arena));
-    louvain_arena(n0, run.arena, &a);
+    LZX_TRY(lzx_carve_state(fn_name, what, cap, 0, &run.arena, &bytes, [&](LzxCarver &k) { louvain_arena(k, n0, &a); }));
     u64 held = bytes;   // what the call holds on the device
-    for (hipEvent_t *e : {&run.ev0, &run.ev1, &run.ev2, &run.ev3}) LZX_HIP(hipEventCreate(e));
+    LZX_TRY(run.events(4));
     hipLaunchKernelGGL(k_fill_u32<true>, dim3(lzx_vertex_grid(n0)), dim3(LZX_COM_BLOCK), 0, c->stream, a.comp, n0, 0u);
     LZX_HIP(hipGetLastError());
 

@@ -368,7 +368,6 @@ struct PathsState {
     double sweep_ms = 0.0, edge_ms = 0.0;
 };
 
-u64 round16(u64 bytes) { return (bytes + 15) & ~15ull; }
 }   // namespace
 
 template <u32 B, int MODE>
@@ -519,36 +518,31 @@ static int paths_run(lzx_handle h, const PathsCall &q)
     const lzx_multi_state *m = c->multi;
     const u64 n = c->n;
     const u32 Bmax = lzx_multi_pad_width(std::min<u32>(q.ns, LZX_BFS_BATCH));
+    const u64 nB = n * Bmax, b_ebc = q.ebc ? sizeof(double) * c->nnz : 0;
     const bool third = q.bc || q.ebc || q.dist || q.paths, fourth = q.bc && q.ebc;
-    const u64 b_dist = round16(sizeof(int32_t) * n * Bmax), b_vec = sizeof(double) * n * Bmax, b_bc = q.bc ? sizeof(double) * n : 0;
-    const u64 b_part = sizeof(double) * (u64)m->n_parts * Bmax, b_prow = round16(sizeof(u32) * (u64)m->n_parts);
-    const u64 b_ebc = q.ebc ? sizeof(double) * c->nnz : 0, b_cnt = q.endpoints ? sizeof(long long) * n : 0;
-    const u64 bytes = b_dist + b_vec * (1 + (third ? 1 : 0) + (fourth ? 1 : 0)) + b_bc + b_ebc + b_cnt + b_part + b_prow + sizeof(u32) * LZX_BFS_BATCH;
+    PathsState s{};
     LzxGraphRun run(c);
     char what[80];
     std::snprintf(what, sizeof what, "the state of %u interleaved columns on %llu vertices", Bmax, (ull)n);
-    LZX_TRY(lzx_alloc_state(fn, what, c->bfs_cap_opt, bytes, bytes, &run.arena));
-    PathsState s{};
-    char *p = static_cast<char *>(run.arena);
-    s.dist = reinterpret_cast<int32_t *>(p); p += b_dist;
-    s.sigma = reinterpret_cast<double *>(p); p += b_vec;
-    s.third = third ? reinterpret_cast<double *>(p) : nullptr; p += third ? b_vec : 0;
-    s.delta = fourth ? reinterpret_cast<double *>(p) : nullptr; p += fourth ? b_vec : 0;
-    s.bc = q.bc ? reinterpret_cast<double *>(p) : nullptr; p += b_bc;
-    s.ebc = q.ebc ? reinterpret_cast<double *>(p) : nullptr; p += b_ebc;
-    s.cnt = q.endpoints ? reinterpret_cast<long long *>(p) : nullptr; p += b_cnt;
-    s.part = reinterpret_cast<double *>(p); p += b_part;
-    s.part_row = reinterpret_cast<u32 *>(p); p += b_prow;
-    s.reached = reinterpret_cast<u32 *>(p);
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn, what, c->bfs_cap_opt, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        k.take(s.dist, nB);
+        k.align(16);
+        k.take(s.sigma, nB);
+        k.take_if(third, s.third, nB);
+        k.take_if(fourth, s.delta, nB);
+        k.take_if(q.bc != nullptr, s.bc, n);
+        k.take_if(q.ebc != nullptr, s.ebc, c->nnz);
+        k.take_if(q.endpoints, s.cnt, n);
+        k.take(s.part, (u64)m->n_parts * Bmax);
+        k.take(s.part_row, ((u64)m->n_parts + 3) & ~3ull);   // (16 bytes at a time)
+        k.take(s.reached, LZX_BFS_BATCH);
+    }));
+    LZX_TRY(run.events(q.ebc ? 4 : 2));
     if (q.ebc) {
-        LZX_HIP(hipEventCreate(&run.ev2));
-        LZX_HIP(hipEventCreate(&run.ev3));
         s.lanes = lzx_lanes_per_row(c, c->nnz, 32);
         if (b_ebc) LZX_HIP(hipMemsetAsync(s.ebc, 0, b_ebc, c->stream));
     }
-    if (q.endpoints) LZX_HIP(hipMemsetAsync(s.cnt, 0, b_cnt, c->stream));
+    if (q.endpoints) LZX_HIP(hipMemsetAsync(s.cnt, 0, sizeof(long long) * n, c->stream));
     if (m->n_split) {
         hipLaunchKernelGGL(k_paths_part_rows, dim3((m->n_split + 255) / 256), dim3(256), 0, c->stream, m->d_split_row, m->d_split_first, m->n_split, s.part_row);
         LZX_HIP(hipGetLastError());

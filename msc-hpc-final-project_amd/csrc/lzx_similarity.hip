@@ -379,42 +379,43 @@ extern "C" int lzx_similarity(lzx_handle c, uint64_t np64, const uint32_t *u, co
         return LZX_OK;
     }
 
-    // one arena.  fp64: a table per sum [n], the values [nm][np]; u64: the block partials; u32: the degrees [n], the pairs
-    // 2 x [np], the counts [np], a degree output [np] each where asked for, four words (two tails, the maximum, a spare)
     const bool want_aa = measures & LZX_SIM_ADAMIC_ADAR, want_ra = measures & LZX_SIM_RESOURCE_ALLOCATION;
     const u32 nsums = (want_aa ? 1u : 0u) + (want_ra ? 1u : 0u);
     const u32 nm = (u32)__builtin_popcount(measures);
-    const u32 nratios = nm - nsums;
-    const u64 n_al = ((u64)n + 1) & ~1ull, np_al = ((u64)np + 1) & ~1ull;
-    const u32 ndeg_out = (deg_u ? 1u : 0u) + (deg_v ? 1u : 0u);
-    const u64 bytes = sizeof(double) * ((u64)nsums * n + (u64)nm * np) + sizeof(ull) * 2 * LZX_SIM_STAT_GRID +
-                      sizeof(u32) * (n_al + (3 + ndeg_out) * np_al + 4);
+    const u64 np_al = lzx_even(np);
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    double *d_tab_aa, *d_tab_ra, *d_values, *d_out_aa, *d_out_ra;
+    ull *d_part;
+    u32 *d_deg, *d_pu, *d_pv, *d_common, *d_dgu, *d_dgv, *d_tails, *d_max;
+    u64 bytes = 0;
     LzxGraphRun run(c);   // more[0]: the lists of long and sliced pairs and the slices' table
     char what[200];
     std::snprintf(what, sizeof what, "the state of %u vertices and %u pairs (degrees, %u tables, pairs, counts, %u measures)", n, np, nsums, nm);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->sim_cap_opt, bytes, bytes, &run.arena));
-    double *d_tab = static_cast<double *>(run.arena);
-    double *d_tab_aa = want_aa ? d_tab : nullptr, *d_tab_ra = want_ra ? d_tab + (want_aa ? n : 0) : nullptr;
-    double *d_values = d_tab + (u64)nsums * n;
-    // (the rows of the values: the ratios asked for, then Adamic-Adar, then resource allocation -- the flags' ascending order)
-    double *d_out_aa = want_aa ? d_values + (u64)nratios * np : nullptr;
-    double *d_out_ra = want_ra ? d_values + (u64)(nratios + (want_aa ? 1 : 0)) * np : nullptr;
-    ull *d_part = reinterpret_cast<ull *>(d_values + (u64)nm * np);
-    u32 *d_deg = reinterpret_cast<u32 *>(d_part + 2 * LZX_SIM_STAT_GRID);
-    u32 *d_pu = d_deg + n_al, *d_pv = d_pu + np_al, *d_common = d_pv + np_al;
-    u32 *d_dgu = deg_u ? d_common + np_al : nullptr;
-    u32 *d_dgv = deg_v ? d_common + np_al * (deg_u ? 2 : 1) : nullptr;
-    u32 *d_words = d_common + np_al * (1 + ndeg_out), *d_tails = d_words, *d_max = d_words + 2;
-    for (hipEvent_t *e : {&run.ev0, &run.ev1, &run.ev2, &run.ev3}) LZX_HIP(hipEventCreate(e));
+    LZX_TRY(lzx_carve_state(fn_name, what, c->sim_cap_opt, 0, &run.arena, &bytes, [&](LzxCarver &k) {
+        k.take_if(want_aa, d_tab_aa, n);   // a table per sum
+        k.take_if(want_ra, d_tab_ra, n);
+        // the values [nm][np] begin here.  Their rows: the ratios asked for, then Adamic-Adar, then resource allocation -- the
+        // flags' ascending order
+        k.take(d_values, (u64)(nm - nsums) * np);
+        k.take_if(want_aa, d_out_aa, np);
+        k.take_if(want_ra, d_out_ra, np);
+        k.take(d_part, 2 * LZX_SIM_STAT_GRID);   // the block partials
+        k.take(d_deg, lzx_even(n));
+        for (u32 **p : {&d_pu, &d_pv, &d_common}) k.take(*p, np_al);
+        k.take_if(deg_u != nullptr, d_dgu, np_al);
+        k.take_if(deg_v != nullptr, d_dgv, np_al);
+        k.take(d_tails, 2);
+        k.take(d_max, 2);   // the maximum, a spare
+    }));
+    LZX_TRY(run.events(4));
 
     // ---- preparation ----
     const u32 G = lzx_lanes_per_row(c, nnz, 32);
     const u32 gb = (n + LZX_SIM_BLOCK - 1) / LZX_SIM_BLOCK;
     const u32 gp = (u32)(((u64)np + LZX_SIM_BLOCK - 1) / LZX_SIM_BLOCK);
     LZX_HIP(hipEventRecord(run.ev0, st));
-    LZX_HIP(hipMemsetAsync(d_words, 0, 4 * sizeof(u32), st));
+    LZX_HIP(hipMemsetAsync(d_tails, 0, 4 * sizeof(u32), st));   // (the tails and the maximum)
     hipLaunchKernelGGL(k_tri_degrees, dim3(gb), dim3(LZX_TRI_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, d_deg, n);
     LZX_HIP(hipGetLastError());
     if (nsums) {
@@ -454,16 +455,15 @@ extern "C" int lzx_similarity(lzx_handle c, uint64_t np64, const uint32_t *u, co
     u32 *d_list_long = nullptr, *d_list_sliced = nullptr, *d_pc = nullptr;
     double *d_paa = nullptr, *d_pra = nullptr;
     if (n_long + n_sliced) {
-        // the slices' table fp64 2 x [n_sliced][64] and u32 [n_sliced][64], then the two lists
-        const u64 cells = (u64)n_sliced * LZX_SIM_SLICES;
-        const u64 more = (2 * sizeof(double) + sizeof(u32)) * cells + sizeof(u32) * ((u64)n_long + n_sliced);
+        const u64 cells = (u64)n_sliced * LZX_SIM_SLICES;   // of the slices' table
         std::snprintf(what, sizeof what, "the state of %u vertices and %u pairs (%u of them on a workgroup each, %u in slices)", n, np, n_long, n_sliced);
-        LZX_TRY(lzx_alloc_state(fn_name, what, c->sim_cap_opt, bytes + more, more, &run.more[0]));
-        d_paa = static_cast<double *>(run.more[0]);
-        d_pra = d_paa + cells;
-        d_pc = reinterpret_cast<u32 *>(d_pra + cells);
-        d_list_sliced = d_pc + cells;
-        d_list_long = d_list_sliced + n_sliced;
+        LZX_TRY(lzx_carve_state(fn_name, what, c->sim_cap_opt, bytes, &run.more[0], nullptr, [&](LzxCarver &k) {
+            k.take(d_paa, cells);
+            k.take(d_pra, cells);
+            k.take(d_pc, cells);
+            k.take(d_list_sliced, n_sliced);
+            k.take(d_list_long, n_long);
+        }));
         LZX_HIP(hipMemsetAsync(d_tails, 0, 2 * sizeof(u32), st));
         hipLaunchKernelGGL(k_sim_classify, dim3(gs), dim3(LZX_SIM_BLOCK), 0, st, a, d_tails, d_list_long, d_list_sliced, n_long, n_sliced, d_part);
         LZX_HIP(hipGetLastError());

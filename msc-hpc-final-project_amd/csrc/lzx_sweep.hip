@@ -293,8 +293,6 @@ k_sweep_close(const SweepCand *part, u32 np, const ull *vol, ull *res, u32 n)
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-inline u64 round_up(u64 x, u64 to) { return (x + to - 1) / to * to; }
-
 // f(std::integral_constant<u32, B>{}) for the width B = 1, 2, 4, 8 or 16
 template <typename F>
 void with_width(u32 B, F f)
@@ -335,12 +333,6 @@ extern "C" int lzx_sweep_cut(lzx_handle c, uint32_t ns, const double *scores, ui
     u32 B = 1;
     while (B < ns) B *= 2;
     const u32 nblk = lo <= hi ? (u32)std::min<u64>((hi - lo) / LZX_SWEEP_BLOCK + 1, LZX_SWEEP_BEST_GRID) : 0u;
-    // one arena: pos (u32 [n][B], rounded to 16 bytes), the keys and the sorted keys (u64 [n] each; the scores are uploaded into the
-    // second), the two arrays of every column (i64, u64 [ns][n]), the blocks' candidates, the results and the count of the long rows,
-    // the ids (later the list of the long rows) and the order (u32 [n] each, rounded to 8 bytes); hipcub's temporary storage follows
-    const u64 pos_bytes = round_up((u64)n * B * sizeof(u32), 16), n_al = round_up(n, 2);
-    const u64 bytes = pos_bytes + 2 * (u64)n * sizeof(u64) + 2 * (u64)ns * n * sizeof(u64) + (u64)ns * nblk * sizeof(SweepCand) + (5 * (u64)ns + 1) * sizeof(u64) +
-                      2 * n_al * sizeof(u32);
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     size_t tmp_sort = 0, tmp_cut = 0, tmp_vol = 0;
@@ -348,28 +340,38 @@ extern "C" int lzx_sweep_cut(lzx_handle c, uint32_t ns, const double *scores, ui
     LZX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_cut, (i64 *)nullptr, (i64 *)nullptr, (size_t)n, st));
     LZX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_vol, (ull *)nullptr, (ull *)nullptr, (size_t)n, st));
     const size_t tmp_bytes = std::max<size_t>(std::max(tmp_sort, std::max(tmp_cut, tmp_vol)), 16);
+    const u64 pos_words = ((u64)n * B + 3) & ~3ull;   // pos, u32 [n][B], rounded to 16 bytes
+    u32 *d_pos, *d_long_count, *d_ids, *d_order;
+    ull *d_keys, *d_sorted, *d_vol, *d_res;
+    i64 *d_cut;
+    SweepCand *d_part;
+    void *d_tmp;
     LzxGraphRun run(c);
     char what[128];
     std::snprintf(what, sizeof what, "the state of %u vertices and %u columns (positions, keys, the profiles)", n, ns);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->sweep_cap_opt, bytes, round_up(bytes, 256) + tmp_bytes, &run.arena));
-    char *at = static_cast<char *>(run.arena);
-    u32 *d_pos = reinterpret_cast<u32 *>(at);
-    ull *d_keys = reinterpret_cast<ull *>(at + pos_bytes), *d_sorted = d_keys + n;
-    i64 *d_cut = reinterpret_cast<i64 *>(d_sorted + n);
-    ull *d_vol = reinterpret_cast<ull *>(d_cut + (u64)ns * n);
-    SweepCand *d_part = reinterpret_cast<SweepCand *>(d_vol + (u64)ns * n);
-    ull *d_res = reinterpret_cast<ull *>(d_part + (u64)ns * nblk);
-    u32 *d_long_count = reinterpret_cast<u32 *>(d_res + 5 * (u64)ns);   // (a word of eight bytes)
-    u32 *d_ids = d_long_count + 2, *d_order = d_ids + n_al;
+    LZX_TRY(lzx_carve_state(fn_name, what, c->sweep_cap_opt, 0, &run.arena, nullptr, [&](LzxCarver &k) {
+        k.take(d_pos, pos_words);
+        k.take(d_keys, n);
+        k.take(d_sorted, n);   // (the scores are uploaded here)
+        k.take(d_cut, (u64)ns * n);
+        k.take(d_vol, (u64)ns * n);
+        k.take(d_part, (u64)ns * nblk);   // the blocks' candidates
+        k.take(d_res, 5 * (u64)ns);
+        k.take(d_long_count, 2);   // (a word of eight bytes)
+        k.take(d_ids, lzx_even(n));
+        k.take(d_order, lzx_even(n));
+        k.end_of_state();   // hipcub's temporary storage follows
+        k.align(256);
+        k.take_bytes(d_tmp, tmp_bytes);
+    }));
     u32 *d_long = d_ids;   // the list of the long rows (the ids are done with when the sorts are)
-    void *d_tmp = at + round_up(bytes, 256);
     double *d_score = reinterpret_cast<double *>(d_sorted);   // (read by k_sweep_keys before the sort writes there)
-    for (hipEvent_t *e : {&run.ev0, &run.ev1, &run.ev2, &run.ev3}) LZX_HIP(hipEventCreate(e));
+    LZX_TRY(run.events(4));
     const u32 gb = (n + LZX_SWEEP_BLOCK - 1) / LZX_SWEEP_BLOCK;
 
     // ---- the orders and the positions, column by column ----
     LZX_HIP(hipEventRecord(run.ev0, st));
-    if (B != ns) LZX_HIP(hipMemsetAsync(d_pos, 0, pos_bytes, st));   // (the padding columns are compared, never stored)
+    if (B != ns) LZX_HIP(hipMemsetAsync(d_pos, 0, sizeof(u32) * pos_words, st));   // (the padding columns are compared, never stored)
     for (u32 col = 0; col < ns; ++col) {
         LZX_HIP(hipMemcpyAsync(d_score, scores + (u64)col * n, sizeof(double) * n, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_sweep_keys, dim3(gb), dim3(LZX_SWEEP_BLOCK), 0, st, c->d_row_ptr, c->d_col_idx, (const double *)d_score, d_keys, d_ids, n, flags);

@@ -234,27 +234,29 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     const auto t0 = std::chrono::steady_clock::now();
     const u32 n = (u32)c->n;
 
-    // one arena: row pointers u64 [n + 1], t u64 [n], c f64 [n], the partials, the four result words, two u32 words, the degrees
-    // u32 [n]; the oriented columns u32 [oriented_entries] follow once the scan has counted them
-    const u64 n_al = ((u64)n + 1) & ~1ull;
-    const u32 np = (u32)std::min<u64>(LZX_TRI_STAT_GRID, ((u64)n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK);
-    const u64 bytes = sizeof(u64) * ((u64)n + 1) + sizeof(ull) * n + sizeof(double) * n + (u64)np * (sizeof(double) + 3 * sizeof(ull)) +
-                      4 * sizeof(ull) + 2 * sizeof(u32) + sizeof(u32) * n_al;
+    // the vertices' arena; the oriented columns follow in one of their own once the scan has counted them
+    const u32 np = (u32)std::min<u64>(LZX_TRI_STAT_GRID, ((u64)n + LZX_TRI_BLOCK - 1) / LZX_TRI_BLOCK);   // the partials of the statistics
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    u64 *d_orp;
+    ull *d_tri, *d_pt, *d_pw, *d_pm, *d_out;
+    double *d_clus, *d_pc;
+    u32 *d_kmax, *d_deg, *d_oci;
+    u64 bytes = 0;
     LzxGraphRun run(c);   // more[0]: the scan's scratch, more[1]: the oriented columns
     char what[160];
     std::snprintf(what, sizeof what, "the state of %u vertices (row pointers, degrees, counts, coefficients, before the oriented columns)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->tri_cap_opt, bytes, bytes, &run.arena));
-    u64 *d_orp = static_cast<u64 *>(run.arena);
-    ull *d_tri = reinterpret_cast<ull *>(d_orp + n + 1);
-    double *d_clus = reinterpret_cast<double *>(d_tri + n);
-    double *d_pc = d_clus + n;
-    ull *d_pt = reinterpret_cast<ull *>(d_pc + np), *d_pw = d_pt + np, *d_pm = d_pw + np, *d_out = d_pm + np;
-    u32 *d_kmax = reinterpret_cast<u32 *>(d_out + 4);
-    u32 *d_deg = d_kmax + 2;
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, c->tri_cap_opt, 0, &run.arena, &bytes, [&](LzxCarver &k) {
+        k.take(d_orp, (u64)n + 1);
+        k.take(d_tri, n);
+        k.take(d_clus, n);
+        k.take(d_pc, np);
+        for (ull **p : {&d_pt, &d_pw, &d_pm}) k.take(*p, np);
+        k.take(d_out, 4);
+        k.take(d_kmax, 2);
+        k.take(d_deg, lzx_even(n));
+    }));
+    LZX_TRY(run.events(2));
 
     // ---- the oriented copy ----
     const u32 Go = lzx_lanes_per_row(c, c->nnz, 64);
@@ -264,10 +266,8 @@ extern "C" int lzx_triangles(lzx_handle c, uint64_t *tri, double *clustering, lz
     LZX_HIP(hipMemsetAsync(d_tri, 0, sizeof(ull) * n, st));
     // the oriented columns: the scan's total, which is what the fill writes whatever was handed over ((nnz - self loops) / 2 of a
     // symmetric matrix)
-    const u64 col_bytes = sizeof(u32) * std::max<u64>(m, 1);
     std::snprintf(what, sizeof what, "the state of %u vertices (an oriented copy of %llu entries, degrees, counts, coefficients)", n, (ull)m);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->tri_cap_opt, bytes + col_bytes, col_bytes, &run.more[1]));
-    u32 *d_oci = static_cast<u32 *>(run.more[1]);
+    LZX_TRY(lzx_carve_state(fn_name, what, c->tri_cap_opt, bytes, &run.more[1], nullptr, [&](LzxCarver &k) { k.take(d_oci, std::max<u64>(m, 1)); }));
     if (m) {
         orient_pass(Go, st, c, d_deg, nullptr, d_orp, d_oci, nullptr);
         LZX_HIP(hipGetLastError());

@@ -389,22 +389,26 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     const u32 n = (u32)c->n;
     const u64 nnz = c->nnz;
 
-    // the vertex arena: the oriented row pointers u64 [n + 1], the partials of the statistics, the degrees u32 [n] (the vertices'
-    // truss numbers once the oriented copy stands), four words (the longest oriented list, a spare, the queue's end, the minimum)
-    const u32 np = LZX_TRUSS_STAT_GRID;
-    const u64 bytes = sizeof(u64) * ((u64)n + 1) + 2 * sizeof(ull) * np + sizeof(u32) * (u64)n + 4 * sizeof(u32);
+    // the vertex arena
+    const u32 np = LZX_TRUSS_STAT_GRID;   // the partials of the statistics
     LZX_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    u64 *d_orp;
+    ull *d_psum, *d_pmax;
+    u32 *d_deg, *d_kmax, *d_counters;
+    u64 bytes = 0;
     LzxGraphRun run(c);   // more[0]: the scan's scratch, more[1]: the edge state
     char what[192];
     std::snprintf(what, sizeof what, "the state of %u vertices (oriented row pointers, degrees, before the state of the edges)", n);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->truss_cap_opt, bytes, bytes, &run.arena));
-    u64 *d_orp = static_cast<u64 *>(run.arena);
-    ull *d_psum = reinterpret_cast<ull *>(d_orp + n + 1), *d_pmax = d_psum + np;
-    u32 *d_deg = reinterpret_cast<u32 *>(d_pmax + np);
-    u32 *d_words = d_deg + n, *d_kmax = d_words, *d_counters = d_words + 2;
-    LZX_HIP(hipEventCreate(&run.ev0));
-    LZX_HIP(hipEventCreate(&run.ev1));
+    LZX_TRY(lzx_carve_state(fn_name, what, c->truss_cap_opt, 0, &run.arena, &bytes, [&](LzxCarver &k) {
+        k.take(d_orp, (u64)n + 1);
+        k.take(d_psum, np);
+        k.take(d_pmax, np);
+        k.take(d_deg, n);        // (the vertices' truss numbers once the oriented copy stands)
+        k.take(d_kmax, 2);       // the longest oriented list, a spare
+        k.take(d_counters, 2);   // the queue's end, the minimum
+    }));
+    LZX_TRY(run.events(2));
 
     // ---- the oriented copy: lzx_triangles' ----
     const u32 Go = lzx_lanes_per_row(c, nnz, 64);
@@ -415,15 +419,15 @@ extern "C" int lzx_truss(lzx_handle c, uint32_t *support, uint32_t *truss, uint3
     if (m64 >= LZX_TRUSS_NONE) LZX_FAIL(LZX_ERR_LIMIT, "%s: %llu edges; edge ids are 32-bit (fewer than 2^32 - 1 edges)", fn_name, (ull)m64);
     const u32 m = (u32)m64;
 
-    // the edge state: oci, src, sup, mark, truss, queue u32 [m] each, eid u32 [nnz] and one staging buffer u32 [nnz] for the
-    // per-entry outputs
+    // the edge state; d_stage: one staging buffer for the per-entry outputs
     const u64 m_al = std::max<u64>(m, 1), z_al = std::max<u64>(nnz, 1);
-    const u64 edge_bytes = sizeof(u32) * (6 * m_al + 2 * z_al);
+    u32 *d_oci, *d_src, *d_sup, *d_mark, *d_truss, *d_queue, *d_eid, *d_stage;
     std::snprintf(what, sizeof what, "the state of %u vertices and %u edges (oriented copy, edge ids of %llu entries, supports, marks, truss numbers, the queue)",
                   n, m, (ull)nnz);
-    LZX_TRY(lzx_alloc_state(fn_name, what, c->truss_cap_opt, bytes + edge_bytes, edge_bytes, &run.more[1]));
-    u32 *d_oci = static_cast<u32 *>(run.more[1]), *d_src = d_oci + m_al, *d_sup = d_src + m_al, *d_mark = d_sup + m_al;
-    u32 *d_truss = d_mark + m_al, *d_queue = d_truss + m_al, *d_eid = d_queue + m_al, *d_stage = d_eid + z_al;
+    LZX_TRY(lzx_carve_state(fn_name, what, c->truss_cap_opt, bytes, &run.more[1], nullptr, [&](LzxCarver &k) {
+        for (u32 **p : {&d_oci, &d_src, &d_sup, &d_mark, &d_truss, &d_queue}) k.take(*p, m_al);
+        for (u32 **p : {&d_eid, &d_stage}) k.take(*p, z_al);
+    }));
     const u32 ge = (u32)(((u64)m + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK);
     const u32 gz = (u32)((nnz + LZX_TRUSS_BLOCK - 1) / LZX_TRUSS_BLOCK);
     // (sup, mark, truss: zero; the queue is written before it is read)
