@@ -846,508 +846,429 @@ static int shard_build_rows(lzx_ctx *c)
     return LZX_OK;
 }
 
-static u32 round_up(u32 a, u32 m) { return (a + m - 1) / m * m; }
-
-int lzx_graph_prepare(lzx_ctx *c)
-{
-    const u64 n = c->n;
-    const u32 world = (u32)c->world, rank = (u32)c->rank;
-    if (n == 0) LZX_FAIL(LZX_ERR_ARG, "graph has no vertices");
-    if (n >= (1ull << 31)) LZX_FAIL(LZX_ERR_LIMIT, "n = %llu: this build indexes vertices with 31 bits", (unsigned long long)n);
-
-    hipStream_t st = c->stream;
-    const u32 per = (u32)((n + world - 1) / world);
-    c->n_loc_pad = round_up(per, LZX_SLICE);
-    c->ldq = c->n_loc_pad + LZX_TAIL;
-    c->iolen = (u64)world * c->n_loc_pad + LZX_TAIL;
-    c->xs = c->n_loc_pad;          // refined below once the number of vertices with an edge is known
-    c->xlen = c->iolen;
-    c->n_loc_real = (rank < n) ? (u32)((n - rank + world - 1) / world) : 0;
-    if (c->iolen + 65536 >= (1ull << 32)) LZX_FAIL(LZX_ERR_LIMIT, "exchange layout does not fit 32-bit codes");
-
-    // Propagation blocking (lzx_pb.hip) for every entry whose column is not staged in LDS.  -1 = decide here.
-    // Measured (DESIGN.md section 3, 1 GPU, plain / blocked SpMV): C3 (10 M vertices, x far beyond the L2s) 2.13 / 1.05 ms;
-    // C2 (1 M vertices, x = 8 MB, L2-resident) 0.136 / 0.103 ms -- since high-degree rows cross the two passes as partial
-    // sums the blocked form also wins while x still fits the caches.  Below about 8 Mi entries per rank its extra
-    // launches and the per-unit 128 KiB column band cost more than the gathers they replace.
-    bool pb = c->pb_opt > 0 || (c->pb_opt < 0 && n >= (512u << 10) && c->nnz / (u64)world >= (8u << 20));
-    // hub entries staged in LDS by k_spmv: 8192 (64 KiB, two workgroups per CU) when k_spmv also gathers from
-    // memory; 16384 (128 KiB, one per CU) in propagation-blocking mode, where it only ever reads LDS.
-    // (round 4, second session: 18 Ki staged values beside 18 Ki column bands on ONE rank from 4 Mi vertices -- 10 M-vertex graph
-    //  SpMV - 1.9 % in two parity-controlled sweeps, profiles/r4_wide_band.txt; the 1 M-vertex graph loses 2.5 % with more staged
-    //  values and keeps 16 Ki of them)
-    u64 hub = (c->hub_opt >= 0) ? (u64)c->hub_opt : (pb ? (world == 1 && !c->force_multi && n >= (4u << 20) ? LZX_PB_CB_WIDE : 16384) : 8192);
-    hub = std::min<u64>(hub, n);
-    hub = std::min<u64>(hub, 20000);  // 160 KiB LDS per CU
-    hub &= ~1ull;
-    if (hub == 0 || hub >= n) pb = false;   // nothing staged, or everything staged: nothing to block
-    c->hub_real = (u32)hub;
-    c->hub = (u32)hub + (pb ? 2 : 0);       // PB mode: two zero slots behind the staged values (padding target)
-    c->spmv_lds = ((size_t)c->hub + LZX_SPMV_BLOCK / 64) * sizeof(double);
-
-    // ---- 1. degree ranking ----
+// --------------------------------------------------------------------------------------------------
+// The hand-over.  What is decided -- the layout, blocked mode and the staged slots, the split of the rows, the slices' order, the
+// grid -- is decided on the host by lzx_prepare_plan.h; the stages below measure what those decisions need and build what they
+// ask for, and lzx_graph_prepare at the end is their sequence.
+//
+// What one stage leaves for the next.  Freed in this order wherever the hand-over ends.
+struct PrepScratch {
     u32 *d_deg = nullptr, *d_ids = nullptr, *d_sdeg = nullptr, *d_sids = nullptr, *d_code = nullptr;
     u32 *d_old_of_local = nullptr, *d_deg_local = nullptr;
     u32 *d_hub_deg = nullptr, *d_nh_deg = nullptr, *d_nh_off = nullptr;
-    void *d_tmp = nullptr;
+    void *d_tmp = nullptr;             // temporary storage of the sorts and the scan
+    size_t tmp_bytes = 0;
     u64 *d_long_ptr = nullptr;
-    int rc = LZX_OK;
-    std::vector<u32> degl, h_nh;
-    std::vector<u64> h_slice_off, h_long_ptr, h_item_beg;
-    std::vector<u32> h_slice_w, h_item_len, h_item_first;
-    auto cleanup = [&]() {
+    std::vector<u32> degl, h_nh;       // per local row: the entries its tables hold, and (blocked mode) those they leave to the blocked passes
+    u64 pb_total = 0;                  // the sum of h_nh
+    void drop_tmp()
+    {
+        if (d_tmp) (void)hipFree(d_tmp);
+        d_tmp = nullptr;
+    }
+    void release()
+    {
         dev_free(d_deg); dev_free(d_ids); dev_free(d_sdeg); dev_free(d_sids); dev_free(d_code);
         dev_free(d_old_of_local); dev_free(d_deg_local); dev_free(d_long_ptr);
         dev_free(d_hub_deg); dev_free(d_nh_deg); dev_free(d_nh_off);
-        if (d_tmp) (void)hipFree(d_tmp);
-        d_tmp = nullptr;
-    };
-#define PREP(call) do { rc = (call); if (rc != LZX_OK) { cleanup(); return rc; } } while (0)
-#define PREP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-        lzx_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); cleanup(); \
-        return e_ == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP; } } while (0)
+        drop_tmp();
+    }
+    ~PrepScratch() { release(); }
+};
 
-    PREP(dev_alloc(&d_deg, n)); PREP(dev_alloc(&d_ids, n));
-    PREP(dev_alloc(&d_sdeg, n)); PREP(dev_alloc(&d_sids, n));
-    PREP(dev_alloc(&d_code, n));
-    PREP(dev_alloc(&c->d_gidx_of_old, n));
+static lzx_plan_in plan_inputs(const lzx_ctx *c)
+{
+    lzx_plan_in in;
+    in.n = c->n; in.nnz = c->nnz;
+    in.world = (u32)c->world; in.rank = (u32)c->rank; in.cu_count = (u32)c->cu_count;
+    in.comm_kind = c->comm_kind; in.force_multi = c->force_multi;
+    in.pb_opt = c->pb_opt; in.hub_opt = c->hub_opt; in.overlap_opt = c->overlap_opt; in.xfp32_opt = c->xfp32_opt;
+    in.pb_cb_opt = c->pb_cb_opt; in.sparse_opt = c->sparse_opt; in.tie_sort_opt = c->tie_sort_opt;
+    in.long_row_opt = c->long_row_opt; in.item_opt = c->item_opt; in.narrow_opt = c->narrow_opt;
+    in.wgs_per_cu_opt = c->wgs_per_cu_opt; in.spmv_wgs_opt = c->spmv_wgs_opt;
+    return in;
+}
+
+static void slices_to_ctx(lzx_ctx *c, const lzx_plan &P)
+{
+    c->n_loc_pad = P.n_loc_pad;
+    c->ldq = P.ldq;
+    c->iolen = P.iolen;
+    c->xs = P.xs;
+    c->xlen = P.xlen;
+    c->n_loc_real = P.n_loc_real;
+}
+
+static void staging_to_ctx(lzx_ctx *c, const lzx_plan &P)
+{
+    c->hub_real = P.hub_real;
+    c->hub = P.hub;
+    c->spmv_lds = P.spmv_lds;
+}
+
+// ---- 1. degree ranking ----
+static int prep_rank_by_degree(lzx_ctx *c, lzx_plan &P, PrepScratch &s)
+{
+    const u64 n = c->n;
+    hipStream_t st = c->stream;
+    LZX_TRY(dev_alloc(&s.d_deg, n)); LZX_TRY(dev_alloc(&s.d_ids, n));
+    LZX_TRY(dev_alloc(&s.d_sdeg, n)); LZX_TRY(dev_alloc(&s.d_sids, n));
+    LZX_TRY(dev_alloc(&s.d_code, n));
+    LZX_TRY(dev_alloc(&c->d_gidx_of_old, n));
     const u32 gb = (u32)((n + 255) / 256);
-    const bool sharded = c->shard.kind >= 0;   // sharded hand-over: no CSR yet -- degrees were counted by its first sweep
-    if (sharded) {
-        PREP_HIP(hipMemcpyAsync(d_deg, c->d_shard_deg, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_shard_iota, dim3(gb), dim3(256), 0, st, d_ids, n);
+    if (c->shard.kind >= 0) {   // sharded hand-over: no CSR yet -- degrees were counted by its first sweep
+        LZX_HIP(hipMemcpyAsync(s.d_deg, c->d_shard_deg, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_shard_iota, dim3(gb), dim3(256), 0, st, s.d_ids, n);
     } else {
-        hipLaunchKernelGGL(k_degrees, dim3(gb), dim3(256), 0, st, c->d_row_ptr, d_deg, d_ids, n);
+        hipLaunchKernelGGL(k_degrees, dim3(gb), dim3(256), 0, st, c->d_row_ptr, s.d_deg, s.d_ids, n);
     }
-    size_t tmp_bytes = 0;
-    PREP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp_bytes, d_deg, d_sdeg, d_ids, d_sids,
-                                                         (u64)n, 0, 32, st));
-    PREP_HIP(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
-    PREP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(d_tmp, tmp_bytes, d_deg, d_sdeg, d_ids, d_sids,
-                                                         (u64)n, 0, 32, st));
-    {
-        u32 md = 0;
-        unsigned long long *d_cnt = nullptr, h_cnt = 0;
-        PREP_HIP(hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long)));
-        hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_count_active, dim3(gb), dim3(256), 0, st, d_sdeg, n, d_cnt);
-            e = hipMemcpyAsync(&h_cnt, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&md, d_sdeg, sizeof(u32), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(d_cnt);
-        PREP_HIP(e);
-        c->max_degree = md;
-        c->n_active = h_cnt;
-        // How many x values to stage is a per-GRAPH choice, not a per-size one (round 3): on a uniform graph the 16 Ki
-        // highest-degree columns hold next to nothing (Erdos-Renyi, 10 M vertices / 200 M entries: 0.25 % of the entries), yet
-        // the staged-columns kernel still sweeps every row for them, and 16 Ki fewer columns are what the blocked passes
-        // would have taken anyway.  Measured (profiles/r3_er_probe.txt, SpMV ms with 16384 / 1024 staged): ER 10 M 1.31 /
-        // 1.05, ER 4 M 0.474 / 0.437, ER 1 M (2.5 % of the entries staged) 0.102 / 0.109; R-MAT (31 %) needs them all.
-        // Rule: below 1 % of the entries in the staged columns, stage 1 Ki.  Every rank holds the whole graph and computes
-        // the same share, so all ranks agree without talking.
-        if (pb && c->hub_opt < 0 && c->nnz > 0) {
-            const u32 top = (u32)std::min<u64>(c->hub_real, n);
-            std::vector<u32> hd(top);
-            PREP_HIP(hipMemcpy(hd.data(), d_sdeg, sizeof(u32) * top, hipMemcpyDeviceToHost));
-            u64 staged = 0;
-            for (u32 dgr : hd) staged += dgr;
-            if (staged * 100 < c->nnz && n > 2048) {
-                c->hub_real = 1024;
-                c->hub = c->hub_real + 2;
-                c->spmv_lds = ((size_t)c->hub + LZX_SPMV_BLOCK / 64) * sizeof(double);
-            }
-        }
-        const u64 live = h_cnt > rank ? (h_cnt - rank + world - 1) / world : 0;
-        c->rows_live = std::min<u32>(c->n_loc_pad, round_up((u32)live, LZX_SLICE));
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, s.tmp_bytes, s.d_deg, s.d_sdeg, s.d_ids, s.d_sids,
+                                                        (u64)n, 0, 32, st));
+    LZX_HIP(hipMalloc(&s.d_tmp, s.tmp_bytes ? s.tmp_bytes : 16));
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairsDescending(s.d_tmp, s.tmp_bytes, s.d_deg, s.d_sdeg, s.d_ids, s.d_sids,
+                                                        (u64)n, 0, 32, st));
+    u32 md = 0;
+    unsigned long long *d_cnt = nullptr, h_cnt = 0;
+    LZX_HIP(hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_count_active, dim3(gb), dim3(256), 0, st, s.d_sdeg, n, d_cnt);
+        e = hipMemcpyAsync(&h_cnt, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     }
-    // Only vertices with at least one edge are ever gathered by an SpMV, and (degree-sorted, dealt round-robin)
-    // they are a prefix of every rank's slice: the per-iteration exchange moves just that prefix.  (R-MAT: 41 % of
-    // the 10 M-vertex benchmark graph is isolated.)  One rank exchanges nothing and gathers from the basis itself.
-    if (world > 1) {
-        c->xs = std::max<u32>(LZX_SLICE, round_up((u32)((c->n_active + world - 1) / world), LZX_SLICE));
-        c->xs = std::min(c->xs, c->n_loc_pad);
-        c->xlen = (u64)world * c->xs + LZX_TAIL;
+    if (e == hipSuccess) e = hipMemcpyAsync(&md, s.d_sdeg, sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d_cnt);
+    LZX_HIP(e);
+    c->max_degree = md;
+    c->n_active = h_cnt;
+    u64 hub_share = 0;   // the entries in the columns that would be staged: what the planner's 1 % rule asks for
+    if (const u32 top = lzx_plan_hub_share_rows(P)) {
+        std::vector<u32> hd(top);
+        LZX_HIP(hipMemcpy(hd.data(), s.d_sdeg, sizeof(u32) * top, hipMemcpyDeviceToHost));
+        for (u32 dgr : hd) hub_share += dgr;
     }
-    // Two chunks (see lzx_internal.h: xs0) when the blocked SpMV will run on several ranks: chunk 0 is the first eighth
-    // of every slice, rounded so that chunk 0 ends on a column-band boundary, and must hold the LDS-staged hub entries.
-    c->xs0 = c->xs;
-    c->overlap = false;
-    c->xfp32 = (world > 1 || c->force_multi) && c->xfp32_opt > 0;   // N4: fp32 exchange uses the single all-gather
-    // (over RCCL only on request: the two-chunk exchange with its sparse second chunk -- a grouped ncclSend / ncclRecv on
-    //  the exchange stream -- has never run on two or more physical GPUs; bench.py asks for it in its guarded tuning
-    //  phase.  In-process groups take it by default: every form of it is covered there, tests/test_gpu_parity.py.)
-    const bool overlap_wanted = c->overlap_opt > 0 || (c->overlap_opt < 0 && c->comm_kind != 2);
-    if ((world > 1 || c->force_multi) && pb && overlap_wanted && !c->xfp32) {
-        // (rounded to the column band the blocked passes will take -- lzx_pb.hip: 18 Ki unless 16 Ki is forced or x is small)
-        const u32 band = (c->pb_cb_opt == 8192 || c->pb_cb_opt == 16384 || c->xlen * sizeof(double) <= (16u << 20)) ? LZX_PB_CB : LZX_PB_CB_WIDE;
-        u32 x0 = round_up(std::max<u32>(c->xs / 8, (c->hub_real + world - 1) / world), band);
-        if (x0 < c->xs) {
-            c->xs0 = x0;
-            c->overlap = true;
-        }
-    }
-    if (c->hub_real > c->n_active) {
-        // staged slots beyond the vertices that have edges would never be referenced (and, with several ranks, would
-        // lie outside the exchanged prefix)
-        c->hub_real = (u32)(c->n_active & ~1ull);
-        if (c->hub_real == 0) pb = false;
-        c->hub = c->hub_real + (pb ? 2 : 0);
-        c->spmv_lds = ((size_t)c->hub + LZX_SPMV_BLOCK / 64) * sizeof(double);
-    }
-    if (c->hub_real >= c->n_active) pb = false;   // every referenced column is staged: nothing left to block
-    if (!pb) {
-        c->xs0 = c->xs;
-        c->overlap = false;
-    }
-    if (pb && c->n_active > c->hub_real && c->tie_sort_opt != 0) {
-        // ---- 1a. ties of the degree ranking broken by the staged-column count (see k_staged_key); d_code is free until
-        //          k_rank_maps fills it and serves as the rank-of-vertex scratch, d_ids as the second value buffer
-        u64 *d_key = nullptr, *d_skey = nullptr;
-        rc = dev_alloc(&d_key, n);
-        if (rc == LZX_OK) rc = dev_alloc(&d_skey, n);
-        if (rc != LZX_OK) { dev_free(d_key); dev_free(d_skey); cleanup(); return rc; }
-        hipLaunchKernelGGL(k_rank_of_old, dim3(gb), dim3(256), 0, st, d_sids, d_code, n);
-        if (sharded) {   // sweep 2: every vertex's count of staged columns, d_ids (free until the sort below) as the scratch
-            rc = shard_count_sweep(c, 1, d_code, c->hub_real, d_ids);
-            if (rc != LZX_OK) { dev_free(d_key); dev_free(d_skey); cleanup(); return rc; }
-            hipLaunchKernelGGL(k_staged_key_counted, dim3(gb), dim3(256), 0, st, d_sids, d_sdeg, d_ids, c->n_active, n, c->hub_real,
-                               c->tie_sort_opt == 2 ? 1 : 0, d_key);
-        } else {
-            hipLaunchKernelGGL(k_staged_key, dim3((u32)std::min<u64>(n, 1u << 20)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx, d_sids,
-                               d_sdeg, d_code, c->n_active, n, c->hub_real, c->tie_sort_opt == 2 ? 1 : 0, d_key);
-        }
-        size_t tb = 0;
-        hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, d_key, d_skey, d_sids, d_ids, (u64)n, 0, 64, st);
-        if (e == hipSuccess && tb > tmp_bytes) {
-            (void)hipFree(d_tmp);
-            d_tmp = nullptr;
-            e = hipMalloc(&d_tmp, tb);
-            if (e == hipSuccess) tmp_bytes = tb;
-        }
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairsDescending(d_tmp, tb, d_key, d_skey, d_sids, d_ids, (u64)n, 0, 64, st);
-        if (e == hipSuccess) {
-            e = hipMemcpyAsync(d_sids, d_ids, sizeof(u32) * n, hipMemcpyDeviceToDevice, st);
-            hipLaunchKernelGGL(k_degree_of, dim3(gb), dim3(256), 0, st, d_deg, d_sids, d_sdeg, n);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        dev_free(d_key); dev_free(d_skey);
-        PREP_HIP(e);
-    }
-    const u32 sentinel = pb ? c->hub_real : c->hub + (u32)((u64)world * c->xs);
-    hipLaunchKernelGGL(k_rank_maps, dim3(gb), dim3(256), 0, st, d_sids, c->d_gidx_of_old, d_code, n,
-                       world, c->n_loc_pad, c->xs, c->xs0, c->hub_real);
-    if (sharded) {   // sweep 3: the ranking is final, so ownership is: this rank's rows become its CSR
-        PREP_HIP(hipStreamSynchronize(st));
-        PREP(shard_build_rows(c));
-    }
+    lzx_plan_ranked(P, h_cnt, md, hub_share);
+    slices_to_ctx(c, P);
+    staging_to_ctx(c, P);
+    c->rows_live = P.rows_live;
+    c->xs0 = P.xs0;
+    c->overlap = P.overlap;
+    c->xfp32 = P.xfp32;
+    return LZX_OK;
+}
 
-    // ---- 1b. sparse exchange of chunk 1: this rank's packed x layout and its send lists (see k_sx_mark) ----
-    c->sparse = false;
-    if (c->overlap && (world > 1 || c->force_multi) && c->sparse_opt != 0 && c->xs > c->xs0) {
-        const u32 L1 = c->xs - c->xs0;
-        const u64 cnt = (u64)world * L1;
-        uint8_t *d_ref = nullptr, *d_want = nullptr;
-        u32 *d_w32 = nullptr, *d_pos = nullptr, *d_spos = nullptr;
-        auto sx_free = [&]() { dev_free(d_ref); dev_free(d_want); dev_free(d_w32); dev_free(d_pos); dev_free(d_spos); };
-#define SX(call) do { rc = (call); if (rc != LZX_OK) { sx_free(); cleanup(); return rc; } } while (0)
-#define SX_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-        lzx_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); sx_free(); cleanup(); \
-        return e_ == hipErrorOutOfMemory ? LZX_ERR_NOMEM : LZX_ERR_HIP; } } while (0)
-        SX(dev_alloc(&d_ref, cnt)); SX(dev_alloc(&d_want, cnt));
-        SX(dev_alloc(&d_w32, cnt + 1)); SX(dev_alloc(&d_pos, cnt + 1)); SX(dev_alloc(&d_spos, cnt + 1));
-        SX_HIP(hipMemsetAsync(d_ref, 0, cnt, st));
-        SX_HIP(hipMemsetAsync(d_want, 0, cnt, st));
-        if (sharded && world > 1)
-            hipLaunchKernelGGL(k_sx_mark_own, dim3((u32)std::min<u64>(std::max<u64>(c->n_active / world + 1, 1), 1u << 20)), dim3(64), 0, st, c->d_row_ptr,
-                               c->d_col_idx, d_sids, d_code, c->d_gidx_of_old, c->n_active, world, rank, c->hub_real, c->xs0, L1, c->n_loc_pad, d_ref, d_want);
-        else
-            hipLaunchKernelGGL(k_sx_mark, dim3((u32)std::min<u64>(std::max<u64>(c->n_active, 1), 1u << 20)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx,
-                               d_sids, d_code, c->n_active, world, rank, c->hub_real, c->xs0, L1, d_ref, d_want);
-        auto scan = [&](const uint8_t *flags, u32 *out) -> int {
-            hipLaunchKernelGGL(k_widen_u8, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, st, flags, cnt, d_w32);
-            LZX_HIP(hipMemsetAsync(d_w32 + cnt, 0, sizeof(u32), st));
-            size_t sb = 0;
-            LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_w32, out, cnt + 1, st));
-            void *tmp = nullptr;
-            LZX_HIP(hipMalloc(&tmp, sb ? sb : 16));
-            hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, sb, d_w32, out, cnt + 1, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            (void)hipFree(tmp);
-            LZX_HIP(e);
-            return LZX_OK;
-        };
-        SX(scan(d_ref, d_pos));
-        SX(scan(d_want, d_spos));
-        c->sx_recv_off.assign(world + 1, 0);
-        c->sx_send_off.assign(world + 1, 0);
-        for (u32 p = 0; p <= world; ++p) {
-            SX_HIP(hipMemcpyAsync(&c->sx_recv_off[p], d_pos + (u64)p * L1, sizeof(u32), hipMemcpyDeviceToHost, st));
-            SX_HIP(hipMemcpyAsync(&c->sx_send_off[p], d_spos + (u64)p * L1, sizeof(u32), hipMemcpyDeviceToHost, st));
-        }
-        SX_HIP(hipStreamSynchronize(st));
-        c->xc1 = c->sx_recv_off[world];
-        SX(dev_alloc(&c->d_sx_map, std::max<u64>(c->xc1, 1)));
-        SX(dev_alloc(&c->d_sx_send_idx, std::max<u32>(c->sx_send_off[world], 1)));
-        SX(dev_alloc(&c->d_sx_sendbuf, std::max<u32>(c->sx_send_off[world], 1)));
-        hipLaunchKernelGGL(k_sx_remap, dim3((u32)((c->n_active + 255) / 256)), dim3(256), 0, st, d_sids, d_code, c->n_active, world,
-                           c->hub_real, c->xs0, L1, c->n_loc_pad, d_ref, d_pos, c->d_sx_map);
-        hipLaunchKernelGGL(k_sx_lists, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, st, d_want, d_spos, cnt, L1, c->xs0, c->d_sx_send_idx);
-        SX_HIP(hipStreamSynchronize(st));
-        // What travels is agreed on by CONTENT, not only by length (round 5, ADVICE r4: with the sharded hand-over the send lists come
-        // from this rank's own rows through the matrix's symmetry, so a caller's CSR that is not symmetric could give lists of the
-        // right lengths and the wrong members): one order-dependent 64-bit hash per peer of what this rank packs for it and of
-        // what it expects from it, compared pairwise beside the counts (lzx_comm_check_sparse; in-process groups: lzx_api.hip).
-        {
-            std::vector<u32> h_idx(c->sx_send_off[world]), h_map(c->xc1);
-            if (!h_idx.empty()) SX_HIP(hipMemcpy(h_idx.data(), c->d_sx_send_idx, sizeof(u32) * h_idx.size(), hipMemcpyDeviceToHost));
-            if (!h_map.empty()) SX_HIP(hipMemcpy(h_map.data(), c->d_sx_map, sizeof(u32) * h_map.size(), hipMemcpyDeviceToHost));
-            c->sx_send_hash.assign(world, 0);
-            c->sx_recv_hash.assign(world, 0);
-            for (u32 p = 0; p < world; ++p) {
-                u64 hs = 0, hr = 0;
-                for (u32 i = c->sx_send_off[p]; i < c->sx_send_off[p + 1]; ++i) hs += lzx_mix64((u64)h_idx[i] + ((u64)(i - c->sx_send_off[p]) << 32));
-                for (u32 i = c->sx_recv_off[p]; i < c->sx_recv_off[p + 1]; ++i)
-                    hr += lzx_mix64((u64)(h_map[i] - p * c->n_loc_pad) + ((u64)(i - c->sx_recv_off[p]) << 32));
-                c->sx_send_hash[p] = hs;
-                c->sx_recv_hash[p] = hr;
-            }
-        }
-        sx_free();
-#undef SX
-#undef SX_HIP
-        c->sparse = true;
-        c->xlen = (u64)world * c->xs0 + round_up((u32)c->xc1, LZX_SLICE) + LZX_TAIL;
+// ---- 1a. ties of the degree ranking broken by the staged-column count (see k_staged_key); d_code is free until
+//          k_rank_maps fills it and serves as the rank-of-vertex scratch, d_ids as the second value buffer
+struct TieKeys {
+    u64 *d_key = nullptr, *d_skey = nullptr;
+    ~TieKeys() { dev_free(d_key); dev_free(d_skey); }
+};
+
+static int prep_break_ties(lzx_ctx *c, const lzx_plan &P, PrepScratch &s)
+{
+    const u64 n = c->n;
+    hipStream_t st = c->stream;
+    const u32 gb = (u32)((n + 255) / 256);
+    TieKeys k;
+    LZX_TRY(dev_alloc(&k.d_key, n));
+    LZX_TRY(dev_alloc(&k.d_skey, n));
+    hipLaunchKernelGGL(k_rank_of_old, dim3(gb), dim3(256), 0, st, s.d_sids, s.d_code, n);
+    if (c->shard.kind >= 0) {   // sweep 2: every vertex's count of staged columns, d_ids (free until the sort below) as the scratch
+        LZX_TRY(shard_count_sweep(c, 1, s.d_code, P.hub_real, s.d_ids));
+        hipLaunchKernelGGL(k_staged_key_counted, dim3(gb), dim3(256), 0, st, s.d_sids, s.d_sdeg, s.d_ids, c->n_active, n, c->hub_real,
+                           c->tie_sort_opt == 2 ? 1 : 0, k.d_key);
+    } else {
+        hipLaunchKernelGGL(k_staged_key, dim3((u32)std::min<u64>(n, 1u << 20)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx, s.d_sids,
+                           s.d_sdeg, s.d_code, c->n_active, n, c->hub_real, c->tie_sort_opt == 2 ? 1 : 0, k.d_key);
     }
-    // ---- RCCL: the hand-over's one sync point.  Everything above is rank-local (allocations, sorts, scans) and may fail on
-    //      one rank alone; what follows it for the sparse chunk is a collective.  Every rank votes here -- one that failed
-    //      earlier through its hand-over entry point's lzx_agree_guard -- and all of them go on, or none does.
+    size_t tb = 0;
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, k.d_key, k.d_skey, s.d_sids, s.d_ids, (u64)n, 0, 64, st));
+    if (tb > s.tmp_bytes) {
+        s.drop_tmp();
+        LZX_HIP(hipMalloc(&s.d_tmp, tb));
+        s.tmp_bytes = tb;
+    }
+    LZX_HIP(hipcub::DeviceRadixSort::SortPairsDescending(s.d_tmp, tb, k.d_key, k.d_skey, s.d_sids, s.d_ids, (u64)n, 0, 64, st));
+    LZX_HIP(hipMemcpyAsync(s.d_sids, s.d_ids, sizeof(u32) * n, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_degree_of, dim3(gb), dim3(256), 0, st, s.d_deg, s.d_sids, s.d_sdeg, n);
+    LZX_HIP(hipStreamSynchronize(st));
+    return LZX_OK;
+}
+
+// The rank maps: where every vertex of the caller's order lies, and its column code.  Sharded hand-over, sweep 3: the ranking is
+// final, so ownership is: this rank's rows become its CSR.
+static int prep_rank_maps(lzx_ctx *c, PrepScratch &s)
+{
+    const u64 n = c->n;
+    hipLaunchKernelGGL(k_rank_maps, dim3((u32)((n + 255) / 256)), dim3(256), 0, c->stream, s.d_sids, c->d_gidx_of_old, s.d_code, n,
+                       (u32)c->world, c->n_loc_pad, c->xs, c->xs0, c->hub_real);
+    if (c->shard.kind >= 0) {
+        LZX_HIP(hipStreamSynchronize(c->stream));
+        LZX_TRY(shard_build_rows(c));
+    }
+    return LZX_OK;
+}
+
+// ---- 1b. sparse exchange of chunk 1: this rank's packed x layout and its send lists (see k_sx_mark) ----
+struct SparseMarks {
+    uint8_t *d_ref = nullptr, *d_want = nullptr;
+    u32 *d_w32 = nullptr, *d_pos = nullptr, *d_spos = nullptr;
+    ~SparseMarks() { dev_free(d_ref); dev_free(d_want); dev_free(d_w32); dev_free(d_pos); dev_free(d_spos); }
+};
+
+static int prep_sparse_lists(lzx_ctx *c, lzx_plan &P, PrepScratch &s)
+{
+    hipStream_t st = c->stream;
+    const u32 world = (u32)c->world, rank = (u32)c->rank;
+    const u32 L1 = c->xs - c->xs0;
+    const u64 cnt = (u64)world * L1;
+    SparseMarks m;
+    LZX_TRY(dev_alloc(&m.d_ref, cnt)); LZX_TRY(dev_alloc(&m.d_want, cnt));
+    LZX_TRY(dev_alloc(&m.d_w32, cnt + 1)); LZX_TRY(dev_alloc(&m.d_pos, cnt + 1)); LZX_TRY(dev_alloc(&m.d_spos, cnt + 1));
+    LZX_HIP(hipMemsetAsync(m.d_ref, 0, cnt, st));
+    LZX_HIP(hipMemsetAsync(m.d_want, 0, cnt, st));
+    if (c->shard.kind >= 0 && world > 1)
+        hipLaunchKernelGGL(k_sx_mark_own, dim3((u32)std::min<u64>(std::max<u64>(c->n_active / world + 1, 1), 1u << 20)), dim3(64), 0, st, c->d_row_ptr,
+                           c->d_col_idx, s.d_sids, s.d_code, c->d_gidx_of_old, c->n_active, world, rank, c->hub_real, c->xs0, L1, c->n_loc_pad, m.d_ref, m.d_want);
+    else
+        hipLaunchKernelGGL(k_sx_mark, dim3((u32)std::min<u64>(std::max<u64>(c->n_active, 1), 1u << 20)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx,
+                           s.d_sids, s.d_code, c->n_active, world, rank, c->hub_real, c->xs0, L1, m.d_ref, m.d_want);
+    auto scan = [&](const uint8_t *flags, u32 *out) -> int {
+        hipLaunchKernelGGL(k_widen_u8, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, st, flags, cnt, m.d_w32);
+        LZX_HIP(hipMemsetAsync(m.d_w32 + cnt, 0, sizeof(u32), st));
+        size_t sb = 0;
+        LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, m.d_w32, out, cnt + 1, st));
+        void *tmp = nullptr;
+        LZX_HIP(hipMalloc(&tmp, sb ? sb : 16));
+        hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, sb, m.d_w32, out, cnt + 1, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(tmp);
+        LZX_HIP(e);
+        return LZX_OK;
+    };
+    LZX_TRY(scan(m.d_ref, m.d_pos));
+    LZX_TRY(scan(m.d_want, m.d_spos));
+    c->sx_recv_off.assign(world + 1, 0);
+    c->sx_send_off.assign(world + 1, 0);
+    for (u32 p = 0; p <= world; ++p) {
+        LZX_HIP(hipMemcpyAsync(&c->sx_recv_off[p], m.d_pos + (u64)p * L1, sizeof(u32), hipMemcpyDeviceToHost, st));
+        LZX_HIP(hipMemcpyAsync(&c->sx_send_off[p], m.d_spos + (u64)p * L1, sizeof(u32), hipMemcpyDeviceToHost, st));
+    }
+    LZX_HIP(hipStreamSynchronize(st));
+    c->xc1 = c->sx_recv_off[world];
+    LZX_TRY(dev_alloc(&c->d_sx_map, std::max<u64>(c->xc1, 1)));
+    LZX_TRY(dev_alloc(&c->d_sx_send_idx, std::max<u32>(c->sx_send_off[world], 1)));
+    LZX_TRY(dev_alloc(&c->d_sx_sendbuf, std::max<u32>(c->sx_send_off[world], 1)));
+    hipLaunchKernelGGL(k_sx_remap, dim3((u32)((c->n_active + 255) / 256)), dim3(256), 0, st, s.d_sids, s.d_code, c->n_active, world,
+                       c->hub_real, c->xs0, L1, c->n_loc_pad, m.d_ref, m.d_pos, c->d_sx_map);
+    hipLaunchKernelGGL(k_sx_lists, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, st, m.d_want, m.d_spos, cnt, L1, c->xs0, c->d_sx_send_idx);
+    LZX_HIP(hipStreamSynchronize(st));
+    std::vector<u32> h_idx(c->sx_send_off[world]), h_map(c->xc1);
+    if (!h_idx.empty()) LZX_HIP(hipMemcpy(h_idx.data(), c->d_sx_send_idx, sizeof(u32) * h_idx.size(), hipMemcpyDeviceToHost));
+    if (!h_map.empty()) LZX_HIP(hipMemcpy(h_map.data(), c->d_sx_map, sizeof(u32) * h_map.size(), hipMemcpyDeviceToHost));
+    lzx_plan_sx_hashes(world, c->n_loc_pad, c->sx_send_off, c->sx_recv_off, h_idx, h_map, c->sx_send_hash, c->sx_recv_hash);
+    c->sparse = true;
+    c->xlen = P.xlen = lzx_plan_sparse_xlen(world, c->xs0, c->xc1);
+    return LZX_OK;
+}
+
+// ---- RCCL: the hand-over's one sync point.  Everything before it is rank-local (allocations, sorts, scans) and may fail on
+//      one rank alone; what follows it for the sparse chunk is a collective.  Every rank votes here -- one that failed
+//      earlier through its hand-over entry point's lzx_agree_guard -- and all of them go on, or none does.
+static int prep_sync_point(lzx_ctx *c)
+{
     if (c->agree_pending) {
         bool all_ok = false;
         c->agree_pending = false;
-        rc = lzx_comm_agree(c, true, &all_ok);
-        if (rc != LZX_OK) { cleanup(); return rc; }
-        if (!all_ok) { cleanup(); LZX_FAIL(LZX_ERR_STATE, "graph hand-over: a peer rank failed while reshaping its share (see that rank's error)"); }
+        LZX_TRY(lzx_comm_agree(c, true, &all_ok));
+        if (!all_ok) LZX_FAIL(LZX_ERR_STATE, "graph hand-over: a peer rank failed while reshaping its share (see that rank's error)");
     }
-    if (c->sparse) {
-        rc = lzx_comm_check_sparse(c);   // RCCL, peer windows: every pair of ranks agrees on what travels, or all of them fail here
-        if (rc != LZX_OK) { cleanup(); return rc; }
-    }
+    if (c->sparse) LZX_TRY(lzx_comm_check_sparse(c));   // RCCL, peer windows: every pair of ranks agrees on what travels, or all of them fail here
     // peer windows: the hand-over ends with a second collective (the receive buffers allocated below become reachable for the
     // peers); a rank that fails before it still takes part, through the entry point's lzx_agree_guard
     c->publish_pending = c->comm_kind == 3 && lzx_exchanges(c);
+    return LZX_OK;
+}
 
-    // ---- 2. this rank's rows ----
-    PREP(dev_alloc(&d_old_of_local, c->n_loc_real)); PREP(dev_alloc(&d_deg_local, c->n_loc_real));
+// ---- 2. this rank's rows ----
+static int prep_local_rows(lzx_ctx *c, const lzx_plan &P, PrepScratch &s)
+{
+    hipStream_t st = c->stream;
+    LZX_TRY(dev_alloc(&s.d_old_of_local, c->n_loc_real)); LZX_TRY(dev_alloc(&s.d_deg_local, c->n_loc_real));
     if (c->n_loc_real) {
-        hipLaunchKernelGGL(k_local_rows, dim3((c->n_loc_real + 255) / 256), dim3(256), 0, st, d_sids, d_sdeg,
-                           d_old_of_local, d_deg_local, c->n_loc_real, world, rank);
+        hipLaunchKernelGGL(k_local_rows, dim3((c->n_loc_real + 255) / 256), dim3(256), 0, st, s.d_sids, s.d_sdeg,
+                           s.d_old_of_local, s.d_deg_local, c->n_loc_real, (u32)c->world, (u32)c->rank);
     }
-    degl.assign(c->n_loc_pad, 0);
+    s.degl.assign(c->n_loc_pad, 0);
     if (c->n_loc_real)
-        PREP_HIP(hipMemcpyAsync(degl.data(), d_deg_local, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
-    PREP_HIP(hipStreamSynchronize(st));
+        LZX_HIP(hipMemcpyAsync(s.degl.data(), s.d_deg_local, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
     c->nnz_local = 0;
-    for (u32 l = 0; l < c->n_loc_real; ++l) c->nnz_local += degl[l];
+    for (u32 l = 0; l < c->n_loc_real; ++l) c->nnz_local += s.degl[l];
     // the whole graph may hold more than 2^32 entries (every rank keeps all of it: C5's 4e9 entries are 17 GB of the
     // 288 GB); a rank's own share is indexed with 32 bits
-    if (c->nnz_local >= (1ull << 32)) { cleanup(); LZX_FAIL(LZX_ERR_LIMIT, "%llu entries in this rank's rows: use more ranks (limit 2^32 per rank)", (unsigned long long)c->nnz_local); }
+    if (c->nnz_local >= (1ull << 32)) LZX_FAIL(LZX_ERR_LIMIT, "%llu entries in this rank's rows: use more ranks (limit 2^32 per rank)", (unsigned long long)c->nnz_local);
 
     // propagation-blocking mode: k_spmv keeps only the hub entries of each row; `degl` becomes that count
-    u64 pb_total = 0;
-    if (pb && c->n_loc_real) {
-        PREP(dev_alloc(&d_hub_deg, c->n_loc_real)); PREP(dev_alloc(&d_nh_deg, (u64)c->n_loc_real + 1));
-        PREP(dev_alloc(&d_nh_off, (u64)c->n_loc_real + 1));
-        PREP_HIP(hipMemsetAsync(d_nh_deg, 0, sizeof(u32) * ((u64)c->n_loc_real + 1), st));
-        hipLaunchKernelGGL(k_row_hub_count, dim3(std::min<u32>(c->n_loc_real, 1u << 22)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx,
-                           d_code, d_old_of_local, d_deg_local, c->n_loc_real, c->hub_real, d_hub_deg, d_nh_deg);
-        h_nh.assign(c->n_loc_real, 0);
-        PREP_HIP(hipMemcpyAsync(degl.data(), d_hub_deg, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
-        PREP_HIP(hipMemcpyAsync(h_nh.data(), d_nh_deg, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
-        PREP_HIP(hipStreamSynchronize(st));
-        u64 hub_total = 0;
-        for (u32 l = 0; l < c->n_loc_real; ++l) hub_total += degl[l];
-        pb_total = c->nnz_local - hub_total;
-        if (pb_total >= LZX_PB_SLOT_LIMIT) {
-            lzx_set_error("propagation blocking: %llu entries on this rank exceed the 32-bit slot range", (unsigned long long)pb_total);
-            cleanup();
-            return LZX_ERR_LIMIT;
-        }
-        // pb_total == 0: every entry of this rank's rows has a staged column -- the hub-only structures are the whole
-        // matrix and no blocked tables are built (the layout decisions above stay as they are: other ranks block).
-        if (pb_total > 0) {
-            size_t sb = 0;
-            PREP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_nh_deg, d_nh_off, (u64)c->n_loc_real + 1, st));
-            if (d_tmp) { (void)hipFree(d_tmp); d_tmp = nullptr; }
-            PREP_HIP(hipMalloc(&d_tmp, sb ? sb : 16));
-            PREP_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, sb, d_nh_deg, d_nh_off, (u64)c->n_loc_real + 1, st));
-        }
+    if (!P.pb || !c->n_loc_real) return LZX_OK;
+    LZX_TRY(dev_alloc(&s.d_hub_deg, c->n_loc_real)); LZX_TRY(dev_alloc(&s.d_nh_deg, (u64)c->n_loc_real + 1));
+    LZX_TRY(dev_alloc(&s.d_nh_off, (u64)c->n_loc_real + 1));
+    LZX_HIP(hipMemsetAsync(s.d_nh_deg, 0, sizeof(u32) * ((u64)c->n_loc_real + 1), st));
+    hipLaunchKernelGGL(k_row_hub_count, dim3(std::min<u32>(c->n_loc_real, 1u << 22)), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx,
+                       s.d_code, s.d_old_of_local, s.d_deg_local, c->n_loc_real, c->hub_real, s.d_hub_deg, s.d_nh_deg);
+    s.h_nh.assign(c->n_loc_real, 0);
+    LZX_HIP(hipMemcpyAsync(s.degl.data(), s.d_hub_deg, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipMemcpyAsync(s.h_nh.data(), s.d_nh_deg, sizeof(u32) * c->n_loc_real, hipMemcpyDeviceToHost, st));
+    LZX_HIP(hipStreamSynchronize(st));
+    u64 hub_total = 0;
+    for (u32 l = 0; l < c->n_loc_real; ++l) hub_total += s.degl[l];
+    s.pb_total = c->nnz_local - hub_total;
+    if (s.pb_total >= LZX_PB_SLOT_LIMIT)
+        LZX_FAIL(LZX_ERR_LIMIT, "propagation blocking: %llu entries on this rank exceed the 32-bit slot range", (unsigned long long)s.pb_total);
+    // pb_total == 0: every entry of this rank's rows has a staged column -- the hub-only structures are the whole
+    // matrix and no blocked tables are built (the layout decisions stay as they are: other ranks block).
+    if (s.pb_total > 0) {
+        size_t sb = 0;
+        LZX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, s.d_nh_deg, s.d_nh_off, (u64)c->n_loc_real + 1, st));
+        s.drop_tmp();
+        LZX_HIP(hipMalloc(&s.d_tmp, sb ? sb : 16));
+        LZX_HIP(hipcub::DeviceScan::ExclusiveSum(s.d_tmp, sb, s.d_nh_deg, s.d_nh_off, (u64)c->n_loc_real + 1, st));
     }
+    return LZX_OK;
+}
 
-    // ---- 3. host: split rows / slices (local rows are sorted by degree, descending) ----
-    // blocked mode: the tables hold staged columns only and a lane's packets come from LDS-only sums, so wider slices
-    // cost less than more split-row items: 256 staged entries per row -- and 1024 where a wavefront has many slices to
-    // even out the long ones (from 2 Mi rows with an edge per rank).  Round 4, parity-controlled A/B (every configuration in
-    // both process states, profiles/r4_long_row.txt): 10 M vertices 0.572 -> 0.556 ms per SpMV (768: 0.551; 512 and
-    // 1536: - 1 %), 4 M vertices 0.213 -> 0.206; the 1 M-vertex graph (2.5 slices per wavefront) LOSES with wider slices
-    // (512: + 4 %, 1024: + 42 %: a wavefront's one long slice is the launch's tail), hence the size rule.
-    const u32 long_thr = c->long_row_opt > 0 ? (u32)c->long_row_opt
-                         : (pb ? (c->rows_live >= (1u << 21) ? 8 * LZX_LONG_ROW : 2 * LZX_LONG_ROW) : LZX_LONG_ROW);
-    u32 n_long = 0;
-    for (u32 l = 0; l < c->n_loc_real; ++l)
-        if (degl[l] > long_thr) n_long = l + 1;
-    c->n_long_true = n_long;
-    c->n_long64 = std::min(round_up(n_long, LZX_SLICE), c->n_loc_pad);
-    c->n_slices = (c->n_loc_pad - c->n_long64) / LZX_SLICE;
+// ---- 3. host: split rows / slices: lzx_plan_rows (lzx_prepare_plan.h); what it counted goes on the handle ----
+static void rows_to_ctx(lzx_ctx *c, const lzx_row_plan &R)
+{
+    c->n_long_true = R.n_long_true;
+    c->n_long64 = R.n_long64;
+    c->n_slices = R.n_slices;
+    c->n_items = R.n_items;
+    c->long_elems = R.long_elems;
+    c->sell_elems = R.sell_elems;
+}
 
-    h_long_ptr.assign((size_t)c->n_long64 + 1, 0);
-    h_item_first.assign((size_t)c->n_long64 + 1, 0);
-    for (u32 r = 0; r < c->n_long64; ++r) {
-        const u32 dp = round_up(degl[r], 4);
-        h_long_ptr[r + 1] = h_long_ptr[r] + dp;
-        h_item_first[r] = (u32)h_item_beg.size();
-        const u32 item_cap = c->item_opt > 0 ? (u32)c->item_opt : LZX_ITEM;
-        for (u32 b = 0; b < dp; b += item_cap) {
-            h_item_beg.push_back(h_long_ptr[r] + b);
-            h_item_len.push_back(std::min(item_cap, dp - b));
-        }
-    }
-    h_item_first[c->n_long64] = (u32)h_item_beg.size();
-    c->n_items = (u32)h_item_beg.size();
-    c->long_elems = h_long_ptr[c->n_long64];
-
-    h_slice_off.assign(c->n_slices, 0);
-    h_slice_w.assign(c->n_slices, 0);
-    u64 off = 0;
-    for (u32 s = 0; s < c->n_slices; ++s) {
-        u32 widest = 0;  // rows are degree-sorted, but in PB mode `degl` counts hub entries only: take the max
-        for (u32 l = 0; l < LZX_SLICE; ++l) widest = std::max(widest, degl[c->n_long64 + s * LZX_SLICE + l]);
-        const u32 w = round_up(widest, 4);
-        h_slice_off[s] = off;
-        h_slice_w[s] = w;
-        off += (u64)w * LZX_SLICE;
-    }
-    c->sell_elems = off;
-
-    // ---- 4. upload tables, fill column codes ----
-    PREP(dev_alloc(&c->d_slice_off, c->n_slices)); PREP(dev_alloc(&c->d_slice_w, c->n_slices));
+// ---- 4. upload tables, fill column codes ----
+static int prep_upload_and_fill(lzx_ctx *c, lzx_plan &P, PrepScratch &s)
+{
+    hipStream_t st = c->stream;
+    const bool pb = P.pb;
+    const lzx_row_plan &R = P.rows;
+    LZX_TRY(dev_alloc(&c->d_slice_off, c->n_slices)); LZX_TRY(dev_alloc(&c->d_slice_w, c->n_slices));
     // + 1 KiB: the SpMV's pipelined loads read one (clamped) packet row past a zero-width last slice / short item
     // (staged-only tables of the propagation-blocking mode hold 16-bit codes: half the bytes)
     c->codes16 = pb;
-    PREP(dev_alloc(&c->d_sell_cols, pb ? (c->sell_elems + 1025) / 2 + 512 : c->sell_elems + 1024));
-    PREP(dev_alloc(&c->d_long_cols, pb ? (c->long_elems + 1025) / 2 + 512 : c->long_elems + 1024));
-    PREP(dev_alloc(&c->d_item_beg, c->n_items)); PREP(dev_alloc(&c->d_item_len, c->n_items));
-    PREP(dev_alloc(&c->d_item_first, (u64)c->n_long64 + 1));
-    PREP(dev_alloc(&c->d_long_partial, c->n_items));
-    PREP(dev_alloc(&d_long_ptr, (u64)c->n_long64 + 1));
-    {   // processing order of the slices: by class in blocked mode (k_spmv), as they lie otherwise
-        std::vector<u32> perm;
-        perm.reserve(c->n_slices);
-        c->h_slice_w0.clear();
-        // classes pay from a few slices per wavefront on (each class loop starts with its own descriptor round trips:
-        // on the 1 M-vertex graph, 2.4 slices per wavefront, they cost 1.6 us)
-        const bool classes = pb && c->narrow_opt != 0 && (c->narrow_opt > 0 || c->n_slices >= 8u * (u32)c->cu_count * (LZX_SPMV_BLOCK / 64));
-        for (u32 s2 = 0; s2 < c->n_slices; ++s2)
-            if (!classes || h_slice_w[s2] > 8) perm.push_back(s2);
-        c->ns_wide = (u32)perm.size();
-        for (u32 s2 = 0; classes && s2 < c->n_slices; ++s2)
-            if (h_slice_w[s2] == 8) perm.push_back(s2);
-        c->ns_w8 = (u32)perm.size() - c->ns_wide;
-        for (u32 s2 = 0; classes && s2 < c->n_slices; ++s2)
-            if (h_slice_w[s2] == 4) perm.push_back(s2);
-        c->ns_w4 = (u32)perm.size() - c->ns_wide - c->ns_w8;
-        for (u32 s2 = 0; classes && s2 < c->n_slices; ++s2)
-            if (h_slice_w[s2] == 0) { perm.push_back(s2); c->h_slice_w0.push_back(s2); }
-        PREP(dev_alloc(&c->d_slice_perm, c->n_slices));
-        if (c->n_slices)
-            PREP_HIP(hipMemcpyAsync(c->d_slice_perm, perm.data(), sizeof(u32) * c->n_slices, hipMemcpyHostToDevice, st));
-        PREP_HIP(hipStreamSynchronize(st));   // perm is a local
-    }
+    LZX_TRY(dev_alloc(&c->d_sell_cols, pb ? (c->sell_elems + 1025) / 2 + 512 : c->sell_elems + 1024));
+    LZX_TRY(dev_alloc(&c->d_long_cols, pb ? (c->long_elems + 1025) / 2 + 512 : c->long_elems + 1024));
+    LZX_TRY(dev_alloc(&c->d_item_beg, c->n_items)); LZX_TRY(dev_alloc(&c->d_item_len, c->n_items));
+    LZX_TRY(dev_alloc(&c->d_item_first, (u64)c->n_long64 + 1));
+    LZX_TRY(dev_alloc(&c->d_long_partial, c->n_items));
+    LZX_TRY(dev_alloc(&s.d_long_ptr, (u64)c->n_long64 + 1));
+    lzx_plan_slice_order(P);   // processing order of the slices: by class in blocked mode (k_spmv), as they lie otherwise
+    c->ns_wide = R.ns_wide;
+    c->ns_w8 = R.ns_w8;
+    c->ns_w4 = R.ns_w4;
+    c->h_slice_w0 = R.h_slice_w0;
+    LZX_TRY(dev_alloc(&c->d_slice_perm, c->n_slices));
     if (c->n_slices) {
-        PREP_HIP(hipMemcpyAsync(c->d_slice_off, h_slice_off.data(), sizeof(u64) * c->n_slices, hipMemcpyHostToDevice, st));
-        PREP_HIP(hipMemcpyAsync(c->d_slice_w, h_slice_w.data(), sizeof(u32) * c->n_slices, hipMemcpyHostToDevice, st));
+        LZX_HIP(hipMemcpyAsync(c->d_slice_perm, R.perm.data(), sizeof(u32) * c->n_slices, hipMemcpyHostToDevice, st));
+        LZX_HIP(hipMemcpyAsync(c->d_slice_off, R.h_slice_off.data(), sizeof(u64) * c->n_slices, hipMemcpyHostToDevice, st));
+        LZX_HIP(hipMemcpyAsync(c->d_slice_w, R.h_slice_w.data(), sizeof(u32) * c->n_slices, hipMemcpyHostToDevice, st));
     }
     if (c->n_items) {
-        PREP_HIP(hipMemcpyAsync(c->d_item_beg, h_item_beg.data(), sizeof(u64) * c->n_items, hipMemcpyHostToDevice, st));
-        PREP_HIP(hipMemcpyAsync(c->d_item_len, h_item_len.data(), sizeof(u32) * c->n_items, hipMemcpyHostToDevice, st));
+        LZX_HIP(hipMemcpyAsync(c->d_item_beg, R.h_item_beg.data(), sizeof(u64) * c->n_items, hipMemcpyHostToDevice, st));
+        LZX_HIP(hipMemcpyAsync(c->d_item_len, R.h_item_len.data(), sizeof(u32) * c->n_items, hipMemcpyHostToDevice, st));
     }
-    PREP_HIP(hipMemcpyAsync(c->d_item_first, h_item_first.data(), sizeof(u32) * ((size_t)c->n_long64 + 1), hipMemcpyHostToDevice, st));
-    PREP_HIP(hipMemcpyAsync(d_long_ptr, h_long_ptr.data(), sizeof(u64) * ((size_t)c->n_long64 + 1), hipMemcpyHostToDevice, st));
+    LZX_HIP(hipMemcpyAsync(c->d_item_first, R.h_item_first.data(), sizeof(u32) * ((size_t)c->n_long64 + 1), hipMemcpyHostToDevice, st));
+    LZX_HIP(hipMemcpyAsync(s.d_long_ptr, R.h_long_ptr.data(), sizeof(u64) * ((size_t)c->n_long64 + 1), hipMemcpyHostToDevice, st));
     if (c->n_slices) {
         const u32 rows = c->n_loc_pad - c->n_long64;
         if (pb)
             hipLaunchKernelGGL(k_fill_sell_hub, dim3((rows + 255) / 256), dim3(256), 0, st, c->d_row_ptr, c->d_col_idx,
-                               d_code, d_old_of_local, d_deg_local, c->n_loc_real, c->n_long64, c->n_loc_pad,
-                               c->d_slice_off, c->d_slice_w, reinterpret_cast<uint16_t *>(c->d_sell_cols), c->hub_real, sentinel);
+                               s.d_code, s.d_old_of_local, s.d_deg_local, c->n_loc_real, c->n_long64, c->n_loc_pad,
+                               c->d_slice_off, c->d_slice_w, reinterpret_cast<uint16_t *>(c->d_sell_cols), c->hub_real, P.sentinel);
         else
             hipLaunchKernelGGL(k_fill_sell, dim3((rows + 255) / 256), dim3(256), 0, st, c->d_row_ptr, c->d_col_idx,
-                               d_code, d_old_of_local, d_deg_local, c->n_loc_real, c->n_long64, c->n_loc_pad,
-                               c->d_slice_off, c->d_slice_w, c->d_sell_cols, sentinel);
+                               s.d_code, s.d_old_of_local, s.d_deg_local, c->n_loc_real, c->n_long64, c->n_loc_pad,
+                               c->d_slice_off, c->d_slice_w, c->d_sell_cols, P.sentinel);
     }
     if (c->n_long64) {
         if (pb)
-            hipLaunchKernelGGL(k_fill_long_hub, dim3(c->n_long64), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx, d_code,
-                               d_old_of_local, d_deg_local, c->n_loc_real, d_long_ptr, reinterpret_cast<uint16_t *>(c->d_long_cols),
-                               c->hub_real, sentinel);
+            hipLaunchKernelGGL(k_fill_long_hub, dim3(c->n_long64), dim3(64), 0, st, c->d_row_ptr, c->d_col_idx, s.d_code,
+                               s.d_old_of_local, s.d_deg_local, c->n_loc_real, s.d_long_ptr, reinterpret_cast<uint16_t *>(c->d_long_cols),
+                               c->hub_real, P.sentinel);
         else
-            hipLaunchKernelGGL(k_fill_long, dim3(c->n_long64), dim3(256), 0, st, c->d_row_ptr, c->d_col_idx, d_code,
-                               d_old_of_local, d_deg_local, c->n_loc_real, d_long_ptr, c->d_long_cols, sentinel);
+            hipLaunchKernelGGL(k_fill_long, dim3(c->n_long64), dim3(256), 0, st, c->d_row_ptr, c->d_col_idx, s.d_code,
+                               s.d_old_of_local, s.d_deg_local, c->n_loc_real, s.d_long_ptr, c->d_long_cols, P.sentinel);
     }
-    PREP_HIP(hipGetLastError());
-    if (pb && pb_total > 0) {
-        if (d_tmp) { (void)hipFree(d_tmp); d_tmp = nullptr; }
-        PREP(lzx_pb_prepare(c, d_code, d_old_of_local, d_deg_local, d_nh_off, h_nh, pb_total));
-    }
+    LZX_HIP(hipGetLastError());
+    return LZX_OK;
+}
 
-    // ---- 5. vectors ----
-    PREP(dev_alloc(&c->d_v, c->ldq));
-    {
-        PREP(dev_alloc(&c->d_u[0], c->ldq)); PREP(dev_alloc(&c->d_u[1], c->ldq));
-        PREP_HIP(hipMemsetAsync(c->d_u[0], 0, sizeof(double) * c->ldq, st));
-        PREP_HIP(hipMemsetAsync(c->d_u[1], 0, sizeof(double) * c->ldq, st));
-    }
-    PREP(dev_alloc(&c->d_xbuf, c->xlen)); PREP(dev_alloc(&c->d_ybuf, c->iolen));
-    if (c->xfp32) { PREP(dev_alloc(&c->d_xf32_send, c->xs)); PREP(dev_alloc(&c->d_xf32_full, (u64)world * c->xs)); }
-    PREP(dev_alloc(&c->d_io, n));
-    PREP_HIP(hipMemsetAsync(c->d_v, 0, sizeof(double) * c->ldq, st));
-    PREP_HIP(hipMemsetAsync(c->d_xbuf, 0, sizeof(double) * c->xlen, st));
-    PREP_HIP(hipMemsetAsync(c->d_ybuf, 0, sizeof(double) * c->iolen, st));
+// The blocked tables (lzx_pb.hip) for every entry whose column is not staged; the sorts' temporary storage goes first.
+static int prep_blocked_tables(lzx_ctx *c, const lzx_plan &P, PrepScratch &s)
+{
+    if (!P.pb || s.pb_total == 0) return LZX_OK;
+    s.drop_tmp();
+    return lzx_pb_prepare(c, s.d_code, s.d_old_of_local, s.d_deg_local, s.d_nh_off, s.h_nh, s.pb_total);
+}
 
-    // launch shape: persistent workgroups, as many as stay resident (LDS-limited), never more than
-    // there is work for.
-    // 4 workgroups per CU: two are resident at the default 64 KiB of staged x, the rest queue behind them, which evens
-    // out the tail (measured: C3 2.16 -> 2.15 ms, C2 0.141 -> 0.133 ms against exactly-resident grids).
-    // In propagation-blocking mode the kernel stages 128 KiB per workgroup and only one is resident: one per CU.
-    u32 per_cu = pb ? 1 : 4;
-    if (c->wgs_per_cu_opt > 0) per_cu = (u32)c->wgs_per_cu_opt;
-    const u32 units = c->n_slices + c->n_items;
-    const u32 waves_per_wg = LZX_SPMV_BLOCK / 64;
-    u32 grid = (u32)c->cu_count * per_cu;
-    grid = std::min(grid, std::max(1u, (units + waves_per_wg - 1) / waves_per_wg));
-    // Blocked mode, little staged-columns work per workgroup (below 512 slices + items each: graphs up to a few million vertices,
-    // rank shares from P = 2): half as many, twice as long.  They share the scatter pass's launch; the CUs they leave free start on scatter units
-    // at once, and 128 KiB of staged x are fetched half as often (1 M-vertex graph: SpMV 0.0652 -> 0.0595 ms; rank 0 of 8 / of 4:
-    // 0.109 -> 0.100, 0.179 -> 0.173 ms; 4 M vertices and rank 0 of 2: - 2 %; neutral on the 10 M-vertex graph -- profiles/r3_small_units.txt)
-    if (pb && units < (u32)c->cu_count * 512u) grid = std::min(grid, std::max(1u, (u32)c->cu_count / 2));
-    if (c->spmv_wgs_opt > 0) grid = std::min<u32>((u32)c->cu_count * per_cu, std::min<u32>(std::max(1u, (units + waves_per_wg - 1) / waves_per_wg), (u32)c->spmv_wgs_opt));   // test shape spmv_wgs
-    c->spmv_grid = grid;
-    c->fin_grid = (c->n_long64 + LZX_VEC_BLOCK - 1) / LZX_VEC_BLOCK;
+// ---- 5. vectors, and the launch shape (lzx_plan_grid) ----
+static int prep_vectors_and_grid(lzx_ctx *c, lzx_plan &P)
+{
+    hipStream_t st = c->stream;
+    LZX_TRY(dev_alloc(&c->d_v, c->ldq));
+    LZX_TRY(dev_alloc(&c->d_u[0], c->ldq)); LZX_TRY(dev_alloc(&c->d_u[1], c->ldq));
+    LZX_HIP(hipMemsetAsync(c->d_u[0], 0, sizeof(double) * c->ldq, st));
+    LZX_HIP(hipMemsetAsync(c->d_u[1], 0, sizeof(double) * c->ldq, st));
+    LZX_TRY(dev_alloc(&c->d_xbuf, c->xlen)); LZX_TRY(dev_alloc(&c->d_ybuf, c->iolen));
+    if (c->xfp32) { LZX_TRY(dev_alloc(&c->d_xf32_send, c->xs)); LZX_TRY(dev_alloc(&c->d_xf32_full, (u64)c->world * c->xs)); }
+    LZX_TRY(dev_alloc(&c->d_io, c->n));
+    LZX_HIP(hipMemsetAsync(c->d_v, 0, sizeof(double) * c->ldq, st));
+    LZX_HIP(hipMemsetAsync(c->d_xbuf, 0, sizeof(double) * c->xlen, st));
+    LZX_HIP(hipMemsetAsync(c->d_ybuf, 0, sizeof(double) * c->iolen, st));
+    lzx_plan_grid(P);
+    c->spmv_grid = P.rows.spmv_grid;
+    c->fin_grid = P.rows.fin_grid;
     c->np_cap = std::max<u32>(c->spmv_grid + c->fin_grid + lzx_pb_partials(c), (u32)c->cu_count * 8) + 8;
-    PREP(dev_alloc(&c->d_partials, c->np_cap)); PREP(dev_alloc(&c->d_partials2, c->np_cap)); PREP(dev_alloc(&c->d_partials3, c->np_cap));
+    LZX_TRY(dev_alloc(&c->d_partials, c->np_cap)); LZX_TRY(dev_alloc(&c->d_partials2, c->np_cap)); LZX_TRY(dev_alloc(&c->d_partials3, c->np_cap));
+    return LZX_OK;
+}
 
-    PREP_HIP(hipStreamSynchronize(st));
-    cleanup();
-#undef PREP
-#undef PREP_HIP
-    rc = lzx_pb_place_values(c);   // option placement_trials: the value stream where the SpMV runs fastest (rank-local, no collective)
-    if (c->publish_pending) {
+int lzx_graph_prepare(lzx_ctx *c)
+{
+    if (c->n == 0) LZX_FAIL(LZX_ERR_ARG, "graph has no vertices");
+    lzx_plan P;                                                      // plan
+    P.in = plan_inputs(c);
+    const char *limit = lzx_plan_layout(P);
+    if (P.n_loc_pad) slices_to_ctx(c, P);   // (n itself past the limit: nothing was laid out)
+    if (limit) LZX_FAIL(LZX_ERR_LIMIT, limit, (unsigned long long)c->n);
+    staging_to_ctx(c, P);
+    {
+        PrepScratch s;
+        LZX_TRY(prep_rank_by_degree(c, P, s));                       // rank by degree (1)
+        if (P.tie_sort) LZX_TRY(prep_break_ties(c, P, s));           // break ties (1a)
+        LZX_TRY(prep_rank_maps(c, s));                               // rank maps, and the sharded sweep 3
+        c->sparse = false;
+        if (P.try_sparse) LZX_TRY(prep_sparse_lists(c, P, s));       // sparse exchange lists (1b)
+        LZX_TRY(prep_sync_point(c));                                 // sync point
+        LZX_TRY(prep_local_rows(c, P, s));                           // local rows and staged counts (2)
+        lzx_plan_rows(P, s.degl);                                    // plan rows (3)
+        rows_to_ctx(c, P.rows);
+        LZX_TRY(prep_upload_and_fill(c, P, s));                      // upload and fill (4)
+        LZX_TRY(prep_blocked_tables(c, P, s));                       // blocked tables
+        LZX_TRY(prep_vectors_and_grid(c, P));                        // vectors and grid (5)
+        LZX_HIP(hipStreamSynchronize(c->stream));
+    }                                                                // release scratch: before the placement, whose trials time the SpMV where its buffers land
+    const int rc = lzx_pb_place_values(c);   // placement -- option placement_trials: the value stream where the SpMV runs fastest (rank-local, no collective)
+    if (c->publish_pending) {                                        // publish
         c->publish_pending = false;
         const int rp = lzx_comm_ipc_publish(c, rc == LZX_OK);
         return rc != LZX_OK ? rc : rp;
     }
     return rc;
 }
+
 
 // --------------------------------------------------------------------------------------------------
 // ingest: sorted unique directed keys (row << 32 | col) -> CSR

@@ -12,9 +12,8 @@
 #include <vector>
 
 #include "lzx.h"
+#include "lzx_prepare_plan.h"   // u32, u64, the layout constants of the hand-over, its host-side decisions
 
-typedef uint32_t u32;
-typedef uint64_t u64;
 typedef unsigned long long ull;   // what the 64-bit atomics and shuffles take
 
 // ---- error plumbing -------------------------------------------------------------------------------
@@ -42,23 +41,9 @@ void lzx_set_error(const char *fmt, ...);
     } while (0)
 
 // ---- layout constants -----------------------------------------------------------------------------
-// Sliced-ELL body: slices of 64 rows (one wavefront), column indices stored so that lane l of the
-// wave reads 16 contiguous bytes (4 indices of ITS row) per step and the wave reads 1 KiB contiguous.
-static constexpr u32 LZX_SLICE = 64;
-// Rows with more entries than this leave the sliced-ELL body and are split into wave-sized items.
-static constexpr u32 LZX_LONG_ROW = 128;
-// Entries one wavefront sums per split-row item (multiple of 256 = 64 lanes x 4 indices).
-static constexpr u32 LZX_ITEM = 2048;
-// Threads per workgroup of the SpMV kernel (16 wavefronts share one LDS copy of the hub entries).
-static constexpr u32 LZX_SPMV_BLOCK = 1024;
-static constexpr u32 LZX_VEC_BLOCK = 256;
-// Zero tail behind every full-length vector: the padding column index points here.
-static constexpr u32 LZX_TAIL = 64;
-// Propagation blocking (csrc/lzx_pb.hip): column band staged in LDS by the scatter phase (doubles),
-// rows per wavefront-private LDS y tile in the gather phase.
-static constexpr u32 LZX_PB_CB = 16384;
-static constexpr u32 LZX_PB_CB_WIDE = 18432;   // test shape pb_column_band: 144 KiB of x per tile (nine 2 Ki-value staging rounds of the 1 024 threads)
-static constexpr u32 LZX_PB_RB = 1024;
+// (those the hand-over's decisions use -- LZX_SLICE, LZX_LONG_ROW, LZX_ITEM, LZX_SPMV_BLOCK, LZX_VEC_BLOCK, LZX_TAIL, LZX_PB_CB, LZX_PB_CB_WIDE --
+//  are in lzx_prepare_plan.h, with round_up and lzx_mix64)
+static constexpr u32 LZX_PB_RB = 1024;       // propagation blocking: rows per wavefront-private LDS y tile in the gather phase
 static constexpr u32 LZX_PB_TARGET = 32768;   // upper limit of the values per gather item (one wavefront each)
 static constexpr u32 LZX_PB_ALIGN = 4;        // (row band, column band) runs are padded to this many values: one plain quad's two 16-byte stores (round 5; 8 = a 64-byte line until then: 4 % more values on the 10 M-vertex R-MAT graph, 5 % on the uniform one, profiles/r5_align_sweep.txt)
 static constexpr u32 LZX_PB_GATHER_BLOCK = 512;
@@ -624,13 +609,6 @@ __host__ __device__ __forceinline__ double lzx_probe_value(u64 seed, u64 p, u64 
 
 // ---- lzx_comm.hip ----
 // does the Lanczos loop exchange vectors / reduce scalars through the communicator?
-// splitmix64 finaliser: the hash of the sparse exchange's index lists (lzx_graph.hip, lzx_comm_check_sparse)
-inline u64 lzx_mix64(u64 z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 // One rank's message of the sparse-exchange check, 6 * world words: [send counts | receive counts | send hashes (lo, hi) | receive
 // hashes (lo, hi)]; lzx_sx_check_pairs: every pair of ranks agrees on how many entries travel AND on which ones, or an error that
 // is the same on every rank (all of them hold all messages).

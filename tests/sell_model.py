@@ -1,5 +1,6 @@
 """Host model of the table formation of the SpMV's other half -- the sliced-ELL body and the split rows that spmv_body
-(csrc/lzx_spmv_body.h) takes: lzx_graph_prepare steps 3 to 5 of csrc/lzx_graph.hip -- in numpy.  No GPU and no import of the
+(csrc/lzx_spmv_body.h) takes: lzx_graph_prepare steps 3 to 5 of csrc/lzx_graph.hip (their arithmetic: csrc/lzx_prepare_plan.h, which
+tests/test_prepare_plan_host.py runs on a CPU against this model) -- in numpy.  No GPU and no import of the
 package: the tests hand it the CSR, the row order the library chose and the shape values, and compare what it counts with
 what the library reports (tests/test_gpu_staged_tables.py), or with numbers counted by hand (tests/test_sell_model_host.py).
 
